@@ -17,6 +17,10 @@ batch i+1 (ctcdecode_amd.distributed.ResultGatherer), all gathers complete befor
         4 = configs[4]: B=1024, beam 100, T=1500, with the LM scorer on tests/data/test.arpa (alpha 0.5, beta 1.0), strong scaling.
 
 Rank 0 prints ONE JSON line (see DESIGN.md "Measurement" for the definition of every field).
+
+    python bench.py ... --dump-outputs DIR   also writes what the last timed step returned (beam_results, beam_scores,
+        timesteps, out_lens) as DIR/<name>.npy in float32 -- the inputs are seeded, so two builds can be compared output
+        for output; over 64 MB the [B, K, T] pair is a fixed sample of utterances, listed in sample_utterances.npy.
 """
 import argparse
 import json
@@ -76,7 +80,39 @@ def parse():
     ap.add_argument("--cpu-seconds", type=float, default=15.0, help="target CPU time of the cpu_baseline sample")
     ap.add_argument("--traffic-json", default=os.path.join(ROOT, "profiles", "traffic_latest.json"),
                     help="per-launch HBM bytes of the decode kernel from a rocprofv3 --pmc pass (tools/rocprof_summary.py)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write what the last timed step returned (rank 0: the gathered batch) as DIR/<name>.npy "
+                         "in float32, at most 64 MB in all (a fixed, seeded sample of the utterances for the [B, K, T] tensors)")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
+
+
+DUMP_BUDGET = 64 * 10**6  # bytes of .npy payload --dump-outputs may write
+
+
+def dump_outputs(np, outs, out_dir, budget=DUMP_BUDGET):
+    """(beam_results [B,K,T], beam_scores [B,K], timesteps [B,K,T], out_lens [B,K]) -> out_dir/<name>.npy as float32 (exact:
+    labels, timesteps and lengths are far below 2**24).  When the two [B, K, T] tensors do not fit in the budget next to the
+    [B, K] ones, they are written for a sample of the utterances drawn with a fixed seed (the same rows for the same shape);
+    sample_utterances.npy lists which.  Returns a summary for the JSON line."""
+    tokens, scores, timesteps, lens = (t.cpu().numpy() for t in outs)
+    B, K, T = tokens.shape
+    room = budget - 2 * B * K * 4 - 4 * B - 4096  # (less the [B, K] pair, the sample's index and the .npy headers)
+    per_utt = 2 * K * T * 4
+    n = B if B * per_utt <= room else max(0, min(B, room // max(per_utt, 1)))
+    idx = np.arange(B) if n == B else np.sort(np.random.default_rng(0).choice(B, size=n, replace=False))
+    arrays = {"beam_results": tokens[idx], "beam_scores": scores, "timesteps": timesteps[idx], "out_lens": lens,
+              "sample_utterances": idx}
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, arr in arrays.items():
+        arr = np.ascontiguousarray(arr, dtype=np.float32)
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+        total += arr.nbytes
+    return {"dir": out_dir, "files": sorted(name + ".npy" for name in arrays), "bytes": total,
+            "utterances_sampled": int(n), "utterances": int(B)}
 
 
 def measure_traffic(a):
@@ -748,6 +784,20 @@ def main():
         res = step()
     fence()
     elapsed = time.perf_counter() - t0
+    # what the last timed step handed its caller: rank 0's gathered batch with a gather, else this rank's own four tensors
+    # (the launches below, outside the timed region, allocate their own outputs and leave these untouched)
+    last_outputs = res
+    if a.dump_outputs and gatherer is not None and rank == 0:
+        if a.gather_format == "compact":
+            last_outputs = gatherer.last
+        else:  # the padded shards of the last slot, each cut to its rank's utterances
+            from ctcdecode_amd.distributed import shard_bounds
+
+            parts = gatherer.received((gatherer._n - 1) % gatherer.depth)
+            sizes = [B] * world
+            if strong:
+                sizes = [hi - lo for lo, hi in (shard_bounds(B_total, world, r, a.min_shard) for r in range(world))]
+            last_outputs = tuple(torch.cat([p[r][:sizes[r]].cpu() for r in range(world)], 0) for p in parts)
     if use_dist:
         tt = torch.tensor([elapsed], dtype=torch.float64, device=dev if backend == "nccl" else "cpu")
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -898,6 +948,8 @@ def main():
                 line["other_configs"] = {"error": str(e)[:300]}
         if not a.no_cpu_baseline:  # (rank 0's host cores, on rank 0's own shard; outside the timed region)
             line["cpu_baseline"] = cpu_baseline(lp_cpu.numpy(), K, a.cpu_seconds, lm=(labels,) + cfg["lm"] if cfg["lm"] else None)
+        if a.dump_outputs:
+            line["dump_outputs"] = dump_outputs(np, last_outputs, a.dump_outputs)
         os.write(json_fd, (json.dumps(line) + "\n").encode())
     if use_dist:
         dist.barrier(device_ids=[dev.index]) if backend == "nccl" else dist.barrier()

@@ -1,8 +1,11 @@
 """Loader for the committed reference fixtures (tests/golden/*.npz, made by tests/golden/make_golden.py)."""
 import glob
+import hashlib
 import os
 
 import numpy as np
+
+import oracle_util as ou
 
 GOLDEN_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
@@ -39,3 +42,37 @@ def load_lm(name):
               labels=[str(x) for x in z["labels"]], meta=tuple(int(v) for v in z["meta"]))
     want = dict(tokens=z["tokens"], timesteps=z["timesteps"], scores=z["scores"], lens=z["lens"], nres=z["nres"])
     return args, lm, want
+
+
+# The reference's results for the inputs of the live differential tests (tests/golden/make_golden_live.py): where oracle/_ref
+# is not built those tests compare against these instead of skipping.
+LIVE_DIR = os.path.join(GOLDEN_DIR, "live")
+
+
+def input_digest(x, **kw):
+    """sha256 of one decode call's inputs: the array (as float32) with its shape, then the keyword arguments by name."""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    h = hashlib.sha256(repr(x.shape).encode())
+    h.update(x.tobytes())
+    for k in sorted(kw):
+        v = kw[k].tolist() if isinstance(kw[k], np.ndarray) else kw[k]
+        h.update(("%s=%r;" % (k, v)).encode())
+    return h.hexdigest()
+
+
+def reference_result(name, x, **kw):
+    """The reference's ``ou.decode(x, **kw)`` (no LM): run by oracle/_ref where it is built -- and then also checked against
+    the stored copy -- else read from tests/golden/live/<name>.npz, which must have been made from the same inputs."""
+    path = os.path.join(LIVE_DIR, name + ".npz")
+    stored = None
+    if os.path.exists(path):
+        z = np.load(path)
+        assert str(z["input_sha256"]) == input_digest(x, **kw), "%s: the stored reference result belongs to other inputs" % name
+        stored = {k: z[k] for k in ("tokens", "timesteps", "scores", "lens", "nres")}
+    if not ou.have_reference():
+        assert stored is not None, "%s: oracle/_ref is not built and there is no stored result %s" % (name, path)
+        return stored
+    live = ou.decode(x, which="reference", **kw)
+    if stored is not None:
+        ou.assert_same(live, stored, name + " (stored reference result vs live reference)")
+    return live

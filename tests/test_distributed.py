@@ -340,3 +340,41 @@ def test_bench_gather_behind_next_decode_rccl_one_rank():
     assert len(lines) == 1, r.stdout
     d = json.loads(lines[0])
     assert d["value"] > 0 and "gather=overlap/compact, backend=nccl" in d["config"]["parallelism"]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("ranks,extra", [(1, []), (2, []), (2, ["--gather-format", "full"]), (1, ["--force-dist", "--backend", "nccl"])],
+                         ids=["single_gpu", "two_ranks_compact_gather", "two_ranks_full_gather", "rccl_one_rank_gather_behind_next_decode"])
+def test_bench_dump_outputs_are_what_the_timed_path_returned(tmp_path, ranks, extra):
+    """`bench.py --dump-outputs DIR`: the four tensors of the last timed step (rank 0: the gathered batch) as float32 .npy
+    files, equal to the oracle's decode of the seeded inputs (rank r: seed 1234 + r, weak scaling)."""
+    import json
+    import subprocess
+
+    import torch
+
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import oracle_util as ou
+
+    B, T, V, K = 6, 60, 29, 100
+    out = str(tmp_path / "dump")
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(ranks), "--steps", "3", "--warmup", "1", "--batch", str(B),
+                        "--frames", str(T), "--no-extras", "--no-pmc", "--no-cpu-baseline", "--dump-outputs", out] + extra,
+                       capture_output=True, text=True, timeout=600, env=env)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["ms_per_step"] > 0
+    files = sorted(os.listdir(out))
+    assert files == d["dump_outputs"]["files"] == ["beam_results.npy", "beam_scores.npy", "out_lens.npy", "sample_utterances.npy", "timesteps.npy"]
+    got = {f[:-4]: np.load(os.path.join(out, f)) for f in files}
+    assert all(a.dtype == np.float32 for a in got.values())
+    assert sum(os.path.getsize(os.path.join(out, f)) for f in files) <= 64 * 10**6
+    assert got["sample_utterances"].tolist() == list(range(B * ranks))
+    lp = torch.cat([torch.randn((B, T, V), generator=torch.Generator(device="cpu").manual_seed(1234 + k), dtype=torch.float32).log_softmax(-1)
+                    for k in range(ranks)]).numpy()
+    want = ou.decode(lp, beam=K, cutoff_top_n=V)
+    ou.assert_same(dict(tokens=got["beam_results"].astype(np.int32), timesteps=got["timesteps"].astype(np.int32), scores=got["beam_scores"],
+                        lens=got["out_lens"].astype(np.int32), nres=want["nres"]), want, "bench.py --dump-outputs")
