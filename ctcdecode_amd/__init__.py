@@ -163,6 +163,28 @@ class KenlmScorer(CallbackScorer):
         CallbackScorer.__init__(self, cond_log10, vocabulary, model.order, labels, alpha, beta, device)
 
 
+# include/ctcdecode_amd.h CTCD_DTYPE_*: device tensors of these dtypes go to the library as they are (its kernels widen them)
+DTYPE_F32, DTYPE_F16, DTYPE_BF16 = 0, 1, 2
+_HALF_DTYPES = {torch.float16: DTYPE_F16, torch.bfloat16: DTYPE_BF16}
+
+
+def _input_rows(owner, probs):
+    """``probs`` as the library reads it: on the owner's device and contiguous; a HIP tensor of dtype float16 / bfloat16 keeps its
+    dtype -- the decoder reads half rows itself, exactly as it would read their float32 copy, and no copy is made -- and every other
+    tensor becomes float32, as in the reference.  Sets the decoder's input dtype for the call (``ctcd_set_input_dtype``): it is state
+    of the decoder object, so threads that share one decoder and pass different dtypes must not interleave their calls."""
+    code = _HALF_DTYPES.get(probs.dtype, DTYPE_F32) if probs.is_cuda else DTYPE_F32
+    probs = probs.to(device=owner._device, dtype=probs.dtype if code else torch.float32).contiguous()
+    _set_input_dtype(owner, code)
+    return probs
+
+
+def _set_input_dtype(owner, code):
+    if getattr(owner, "_in_dtype", DTYPE_F32) != code:
+        _native.check(_native.lib.ctcd_set_input_dtype(owner._handle, code))
+        owner._in_dtype = code
+
+
 def _to_host(tensors):
     """Device -> host copy of the result tensors through page-locked memory (PyTorch's caching host allocator recycles
     the blocks), all copies in flight together, one synchronisation: several times faster than ``.cpu()`` on pageable
@@ -299,12 +321,21 @@ class CTCBeamDecoder(object):
         _native.check(_native.lib.ctcd_last_prune_ms(self._handle, ctypes.byref(ms)))
         return float(ms.value)
 
+    def last_resolve_ms(self):
+        """(set_timing) the flagged frames' replay behind the prune pass of the last call: from the end of the prune pass to the
+        start of the decode kernel."""
+        ms = ctypes.c_float()
+        _native.check(_native.lib.ctcd_last_resolve_ms(self._handle, ctypes.byref(ms)))
+        return float(ms.value)
+
     def decode_device(self, probs, seq_lens=None, check=True):
         """``probs``: [B, T, V] tensor (any device / float dtype).  Returns (beam_results, beam_scores, timesteps,
-        out_lens) as tensors in HBM on the decoder's device; asynchronous on the current stream when ``check`` is False."""
+        out_lens) as tensors in HBM on the decoder's device; asynchronous on the current stream when ``check`` is False.
+        A HIP tensor of dtype bfloat16 / float16 is decoded as it is, without a float32 copy: the results are those of
+        ``probs.float()``, bit for bit.  Other dtypes are cast to float32 first."""
         if probs.dim() != 3:
             raise ValueError("probs must be [batch, time, labels]")
-        probs = probs.to(device=self._device, dtype=torch.float32).contiguous()
+        probs = _input_rows(self, probs)
         B, T, V = probs.shape
         if V != self._num_labels:
             raise ValueError("probs.shape[2] (%d) does not match the number of labels (%d)" % (V, self._num_labels))
@@ -337,14 +368,18 @@ class CTCBeamDecoder(object):
         """Drop-in for ctcdecode/__init__.py:53-123: returns CPU tensors (output, scores, timesteps, out_seq_len).
 
         The results leave the GPU in compact form (every beam only the labels it does not share with its neighbour in the
-        trie, include/ctcdecode_amd.h) and ``num_processes`` host threads expand them into the four tensors."""
+        trie, include/ctcdecode_amd.h) and ``num_processes`` host threads expand them into the four tensors.
+
+        A HIP tensor of dtype bfloat16 / float16 is decoded without a float32 copy (the results of ``probs.float()``, bit for
+        bit); a CPU tensor of any dtype is cast to float32 on the host, as the reference does (ctcdecode/__init__.py:77)."""
         if probs.dim() != 3:
             raise ValueError("probs must be [batch, time, labels]")
         on_dev = probs.is_cuda
         if on_dev:
-            probs = probs.to(device=self._device, dtype=torch.float32).contiguous()
+            probs = _input_rows(self, probs)
         else:
             probs = probs.to(dtype=torch.float32).contiguous()  # ctcdecode/__init__.py:77
+            _set_input_dtype(self, DTYPE_F32)
         B, T, V = probs.shape
         if V != self._num_labels:
             raise ValueError("probs.shape[2] (%d) does not match the number of labels (%d)" % (V, self._num_labels))
@@ -369,15 +404,16 @@ class CTCBeamDecoder(object):
 
     def log_softmax(self, logits, seq_lens=None):
         """The float32 log_softmax that ``logits_input=True`` applies before decoding, as a tensor in HBM ([B, T, V]; frames at
-        or beyond ``seq_lens`` are left 0).  Bit-reproducible: see include/ctcdecode_amd.h ctcd_log_softmax."""
+        or beyond ``seq_lens`` are left 0).  Bit-reproducible: see include/ctcdecode_amd.h ctcd_log_softmax.  bfloat16 / float16
+        logits on the device are read as they are (the result is that of ``logits.float()``); the output is float32."""
         if logits.dim() != 3:
             raise ValueError("logits must be [batch, time, labels]")
-        logits = logits.to(device=self._device, dtype=torch.float32).contiguous()
+        logits = _input_rows(self, logits)
         B, T, V = logits.shape
         if seq_lens is not None:
             seq_lens = seq_lens.to(device=self._device, dtype=torch.int32).contiguous()
         with torch.cuda.device(self._device):
-            out = torch.zeros_like(logits)
+            out = torch.zeros((B, T, V), dtype=torch.float32, device=self._device)
             stream = torch.cuda.current_stream(self._device).cuda_stream
             _native.check(_native.lib.ctcd_log_softmax(self._handle, logits.data_ptr(), seq_lens.data_ptr() if seq_lens is not None else None,
                                                        B, T, V, out.data_ptr(), stream))
@@ -392,7 +428,7 @@ class CTCBeamDecoder(object):
         what a rank ships to the gathering rank; ``expand_compact`` rebuilds the padded tensors there."""
         if probs.dim() != 3:
             raise ValueError("probs must be [batch, time, labels]")
-        probs = probs.to(device=self._device, dtype=torch.float32).contiguous()
+        probs = _input_rows(self, probs)
         B, T, V = probs.shape
         if V != self._num_labels:
             raise ValueError("probs.shape[2] (%d) does not match the number of labels (%d)" % (V, self._num_labels))
@@ -428,7 +464,7 @@ class CTCBeamDecoder(object):
         With a callback scorer the call BLOCKS until the decode is done: the callback is served on the calling thread."""
         if probs.dim() != 3:
             raise ValueError("probs must be [batch, time, labels]")
-        probs = probs.to(device=self._device, dtype=torch.float32).contiguous()
+        probs = _input_rows(self, probs)
         B, T, V = probs.shape
         if V != self._num_labels:
             raise ValueError("probs.shape[2] (%d) does not match the number of labels (%d)" % (V, self._num_labels))
@@ -661,7 +697,7 @@ class OnlineCTCBeamDecoder(object):
             raise ValueError("probs.shape[2] (%d) does not match the number of labels (%d)" % (V, self._num_labels))
         if len(states) != B or len(is_eos_s) != B:
             raise ValueError("states and is_eos_s need one entry per batch item")
-        probs = probs.to(device=self._device, dtype=torch.float32).contiguous()
+        probs = _input_rows(self, probs)  # (bfloat16 / float16 chunks on the device: decoded as they are, as their float32 copies)
         lens_cpu = None
         if seq_lens is not None:
             lens_cpu = seq_lens.detach().cpu().to(torch.int32).contiguous()

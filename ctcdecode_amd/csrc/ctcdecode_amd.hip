@@ -45,6 +45,25 @@ using namespace ctcdk;
 // conversion evaluate exactly what the reference's C library evaluates (decoder_utils.cpp:16,29,42), on the device.
 #define g_t64 (ctcmath::tables64())
 
+// Element type of the caller's rows (ctcd_set_input_dtype): float32, or IEEE binary16 / bfloat16 (the "half" kernels further down read
+// those and widen every element to float as they read it).  Widening is exact, so they compute on the very float values the float32
+// kernels would read from x.float(); nothing behind the pre-passes (candidate lists, the decode kernels) sees the type.  Four half
+// elements are read with one 8-byte load where the float32 kernels read a float4: the thread-to-label mapping, and with it the
+// summation order that defines the log-softmax, stays as it is.
+enum InDtype { kInF32 = CTCD_DTYPE_F32, kInF16 = CTCD_DTYPE_F16, kInBF16 = CTCD_DTYPE_BF16 };
+template <int DT> struct InElem { using T = uint16_t; };  // (DT = kInF16 / kInBF16)
+template <int DT> __device__ __forceinline__ float widen_in(uint16_t u) {
+  if (DT == kInBF16) return __uint_as_float((uint32_t)u << 16);
+  return (float)__builtin_bit_cast(_Float16, u);
+}
+template <int DT, typename I> __device__ __forceinline__ float in_at(const uint16_t *row, I i) { return widen_in<DT>(row[i]); }
+// elements 4 * i4 .. 4 * i4 + 3 of a row (8-byte aligned)
+template <int DT> __device__ __forceinline__ float4 in_load4(const uint16_t *row, int i4) {
+  const uint2 w = reinterpret_cast<const uint2 *>(row)[i4];
+  return make_float4(widen_in<DT>((uint16_t)(w.x & 0xffffu)), widen_in<DT>((uint16_t)(w.x >> 16)), widen_in<DT>((uint16_t)(w.y & 0xffffu)),
+                     widen_in<DT>((uint16_t)(w.y >> 16)));
+}
+
 // prob -> log-prob exactly as decoder_utils.cpp:42 : float(log(double(p) + FLT_MIN)), every element, bit for bit.
 // (Rounds 1-3 used the device library's log() and sent the elements whose float rounding it could not guarantee through
 //  the host's libm; the restated routine needs no second opinion.)
@@ -922,6 +941,716 @@ __global__ void __launch_bounds__(kResolveThreads) prune_resolve_kernel(PruneArg
   }
 }
 
+// ------------------------------------------------------------------------------------------------ half rows
+// The pre-pass kernels above, instantiated for rows of IEEE binary16 / bfloat16 (DT = kInF16 / kInBF16: ctcd_set_input_dtype) -- the
+// same code with every element widened to float as it is read (in_at / in_load4), and, for the prune, the half-row tie rule below.
+// The float32 kernels above are left as they are (their machine code included); the decode kernels only ever read float32.
+template <int DT>
+__global__ void prob_to_log_half_kernel(const float *in_, float *out, size_t n, const int32_t *seq_lens, int T, int V) {
+  const typename InElem<DT>::T *in = reinterpret_cast<const typename InElem<DT>::T *>(in_);
+  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t stride = (size_t)gridDim.x * blockDim.x;
+  const size_t tv = (size_t)T * V;
+  for (; i < n; i += stride) {
+    if (seq_lens) {  // frames beyond the utterance's length are never read by the reference (binding.cpp:64-65)
+      const size_t b = i / tv;
+      const int t = (int)((i - b * tv) / (size_t)V);
+      if (t >= seq_lens[b]) continue;
+    }
+    out[i] = (float)ctcmath::log_f64((double)in_at<DT>(in, i) + (double)FLT_MIN, g_t64);
+  }
+}
+
+// Half rows widened to float32 into the decoder's workspace, where a decode kernel reads the caller's rows itself (log-probability
+// rows without pruning; the LM tier's blank values).  Frames past an utterance's end are skipped as above.
+
+template <int DT>
+__global__ void widen_rows_kernel(const float *in_, float *out, size_t n, const int32_t *seq_lens, int T, int V) {
+  const typename InElem<DT>::T *in = reinterpret_cast<const typename InElem<DT>::T *>(in_);
+  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t stride = (size_t)gridDim.x * blockDim.x;
+  const size_t tv = (size_t)T * V;
+  for (; i < n; i += stride) {
+    if (seq_lens) {
+      const size_t b = i / tv;
+      const int t = (int)((i - b * tv) / (size_t)V);
+      if (t >= seq_lens[b]) continue;
+    }
+    out[i] = in_at<DT>(in, i);
+  }
+}
+
+template <int DT>
+__global__ void __launch_bounds__(256) log_softmax_rows_half_kernel(const float *in_, float *out, long long rows, const int32_t *seq_lens, int T, int V,
+                                                               const uint64_t *tables) {
+  const typename InElem<DT>::T *in = reinterpret_cast<const typename InElem<DT>::T *>(in_);
+  __shared__ uint64_t tbl[64];
+  if (threadIdx.x < 64) tbl[threadIdx.x] = tables[threadIdx.x];
+  __syncthreads();
+  const int lane = (int)threadIdx.x & 63;
+  const long long wave0 = (long long)blockIdx.x * 4 + (threadIdx.x >> 6), nwaves = (long long)gridDim.x * 4;
+  for (long long r = wave0; r < rows; r += nwaves) {
+    if (seq_lens) {  // frames beyond the utterance's length are never read (binding.cpp:64-65)
+      const long long b = r / T;
+      if ((int)(r - b * T) >= seq_lens[b]) continue;
+    }
+    const typename InElem<DT>::T *x = in + (size_t)r * V;
+    float *y = out + (size_t)r * V;
+    float m = -INFINITY;
+    for (int j = lane; j < V; j += 64) { const float v = in_at<DT>(x, j); m = v > m ? v : m; }
+    for (int off = 1; off < 64; off <<= 1) { const float o = __shfl_xor(m, off, 64); m = o > m ? o : m; }
+    m += 0.0f;  // (a zero maximum is +0)
+    if (!(m > -INFINITY)) {
+      for (int j = lane; j < V; j += 64) y[j] = -INFINITY;
+      continue;
+    }
+    float part = 0.0f;
+    for (int j = lane; j < V; j += 64) part += ctcmath::expf_nonpos(in_at<DT>(x, j) - m, tbl);
+    for (int off = 1; off < 64; off <<= 1) part += __shfl_xor(part, off, 64);
+    const float ls = ctcmath::logf_normal(part, tbl);
+    for (int j = lane; j < V; j += 64) y[j] = (in_at<DT>(x, j) - m) - ls;
+  }
+}
+
+template <int F4, int DT>
+__global__ void __launch_bounds__(256, F4 <= 10 ? 5 : 4) log_softmax_rows_wg_half_kernel(const float *in_, float *out, long long rows, const int32_t *seq_lens, int T,
+                                                                                     int V, const uint64_t *tables) {
+  __shared__ uint64_t tbl[64];
+  __shared__ __attribute__((aligned(16))) LsmLds s;
+  const typename InElem<DT>::T *in = reinterpret_cast<const typename InElem<DT>::T *>(in_);
+  const int tid = (int)threadIdx.x, nv4 = V >> 2;
+  if (tid < 64) tbl[tid] = tables[tid];
+  __syncthreads();
+  for (long long r = blockIdx.x; r < rows; r += gridDim.x) {
+    if (seq_lens) {  // frames beyond the utterance's length are never read (binding.cpp:64-65)
+      const long long b = r / T;
+      if ((int)(r - b * T) >= seq_lens[b]) continue;
+    }
+    const typename InElem<DT>::T *x4 = in + (size_t)r * V;
+    float4 *y4 = reinterpret_cast<float4 *>(out + (size_t)r * V);
+    int tq = tid;  // (opaque per frame: the chunks' predicates and offsets are recomputed, not kept across the frame loop)
+    asm volatile("" : "+v"(tq));
+    float4 v[F4];
+#pragma unroll
+    for (int u = 0; u < F4; ++u) {
+      const int i4 = tq + 256 * u;
+      v[u] = i4 < nv4 ? in_load4<DT>(x4, i4) : make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
+    }
+    float mine = -INFINITY;
+#pragma unroll
+    for (int u = 0; u < F4; ++u) {
+      mine = v[u].x > mine ? v[u].x : mine; mine = v[u].y > mine ? v[u].y : mine;
+      mine = v[u].z > mine ? v[u].z : mine; mine = v[u].w > mine ? v[u].w : mine;
+    }
+    const float m = wg_row_max(mine, s, tid);
+    if (!(m > -INFINITY)) {
+#pragma unroll
+      for (int u = 0; u < F4; ++u)
+        if (tq + 256 * u < nv4) y4[tq + 256 * u] = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
+    } else {
+      const float ls = ctcmath::logf_normal(wg_exp_sum<F4>(v, nv4, m, s, tbl, tq), tbl);
+#pragma unroll
+      for (int u = 0; u < F4; ++u)
+        if (tq + 256 * u < nv4) y4[tq + 256 * u] = make_float4((v[u].x - m) - ls, (v[u].y - m) - ls, (v[u].z - m) - ls, (v[u].w - m) - ls);
+    }
+    __syncthreads();  // (the chunk buffers and wmax are reused by the next frame)
+  }
+}
+
+// Half rows (DT != kInF32): rows of fp16 / bf16 values tie in almost every frame, and a tie flags a frame here only if it can change
+// the result.  The kept length after the cumulative cut (decoder_utils.cpp:26-31) does not depend on the order std::sort gives equal
+// values: cum_prob adds the sorted values, and equal values give the same partial sums in any order.  So the cut is computed first
+// and a group of equal values flags the frame only when one of its members lies inside the kept length -- it then either straddles
+// that length or has two members inside it; with a single member inside, the group reaches beyond.  Put the other way: with first_tie
+// the first sorted position that belongs to a group of equal values, the frame is settled here iff the cut stops at or before
+// first_tie, and positions [0, first_tie) hold distinct values whose order and conversion are fixed.  The cut can only stop early for
+// cutoff_prob < ln 2 (cum_prob starts at 0.0 = log 1: PruneArgs::cut_exp); at the default 0.99 the kept length is cutoff_top_n and
+// the rule flags exactly what the float32 rule flags.  (float32 rows keep the rule that flags every tie inside cutoff_top_n.)
+
+template <int R, int DT>
+__global__ void __launch_bounds__(256) prune_rows_half_kernel(PruneArgs a) {
+  const typename InElem<DT>::T *in = reinterpret_cast<const typename InElem<DT>::T *>(a.in);
+  extern __shared__ __attribute__((aligned(16))) char psm[];
+  const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6, wpb = (int)blockDim.x >> 6;
+  const int n = a.top_n < a.V ? a.top_n : a.V;
+  // per wave: kept keys, labels, labels in final order (stride each); pre-filter candidates (keys, labels)
+  uint32_t *lkey = (uint32_t *)psm + (size_t)wave * (3 * a.stride + 2 * kPruneCand);
+  int *lidx = (int *)lkey + a.stride;
+  int *sidx = lidx + a.stride;
+  uint32_t *ckey = (uint32_t *)(sidx + a.stride);
+  int *cidx = (int *)ckey + kPruneCand;
+  for (long long r = (long long)blockIdx.x * wpb + wave; r < a.rows; r += (long long)gridDim.x * wpb) {
+    if (a.seq_lens) {  // frames beyond the utterance's length are never read (binding.cpp:64-65)
+      const long long b = r / a.T;
+      int len = a.seq_lens[b];
+      len = len < 0 ? 0 : len;
+      if ((int)(r - b * a.T) >= len) continue;
+    }
+    const typename InElem<DT>::T *x = in + (size_t)r * a.V;
+    bool flag = false;
+    bool tie = false;     // (half rows: equal values inside cutoff_top_n -- flag the frame only if the cut reaches them)
+    int first_tie = a.V;  // ... the first sorted position of such a group
+    uint32_t keys[R > 0 ? R : 1];
+    if (R > 0) {
+#pragma unroll
+      for (int u = 0; u < R; ++u) keys[u] = lane + 64 * u < a.V ? prune_key(in_at<DT>(x, lane + 64 * u)) : 0u;  // 0 < every real key
+    }
+    uint32_t tau = 0;
+    int g = 0, e = 0, base = 0;
+    bool done = false;
+    if (R > 0 && n <= 64) {
+      // Pre-filter: tau is at least the n-th largest of the 64 per-lane maxima (those are n elements >= it), so only
+      // keys >= that bound (a few dozen of V) can be among the top n.  They are listed in LDS and ranked exactly.
+      uint32_t lmax = 0;
+#pragma unroll
+      for (int u = 0; u < R; ++u) lmax = keys[u] > lmax ? keys[u] : lmax;
+      uint32_t bound = 0;
+      for (int bit = 31; bit >= 0; --bit) {
+        const uint32_t trial = bound | (1u << bit);
+        if (__popcll(__ballot(lmax >= trial)) >= n) bound = trial;
+      }
+      int ns = 0;
+#pragma unroll
+      for (int u = 0; u < R; ++u) {
+        const bool in = keys[u] >= bound && keys[u] != 0u;
+        const unsigned long long m = __ballot(in);
+        if (m) {
+          const int p = ns + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+          if (in && p < kPruneCand) { ckey[p] = keys[u]; cidx[p] = lane + 64 * u; }
+          ns += __popcll(m);
+        }
+      }
+      if (ns <= kPruneCand) {
+        // exact n-th largest among the ns candidates (every lane ranks its own candidates against all of them)
+        uint32_t found = 0;
+        for (int q = lane; q < ns; q += 64) {
+          const uint32_t mine = ckey[q];
+          int gg = 0, ee = 0;
+          for (int o = 0; o < ns; ++o) {
+            const uint32_t k = ckey[o];
+            gg += k > mine;
+            ee += k == mine;
+          }
+          if (gg < n && n <= gg + ee) found = mine;
+        }
+        const unsigned long long mf = __ballot(found != 0u);
+        tau = (uint32_t)__builtin_amdgcn_readlane((int)found, __ffsll((long long)mf) - 1);
+        for (int q = lane; q < ns; q += 64) { g += ckey[q] > tau; e += ckey[q] == tau; }
+        g = wave_sum(g);
+        e = wave_sum(e);
+        if (e > n - g) {  // equal values straddle the cut: std::sort decides which of them are kept
+          tie = true; first_tie = g;
+        }
+        for (int q0 = 0; q0 < ns; q0 += 64) {
+          const int q = q0 + lane;
+          const uint32_t k = q < ns ? ckey[q] : 0u;
+          const bool keep = q < ns && (k > tau || (k == tau && !(flag || tie)));
+          const unsigned long long m = __ballot(keep);
+          if (keep) {
+            const int p = base + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+            lkey[p] = k;
+            lidx[p] = cidx[q];
+          }
+          base += __popcll(m);
+        }
+        done = true;
+      }
+    }
+    if (!done) {
+      // n-th largest key, bit by bit, over all V values
+      for (int bit = 31; bit >= 0; --bit) {
+        const uint32_t trial = tau | (1u << bit);
+        int c = 0;
+        if (R > 0) {
+#pragma unroll
+          for (int u = 0; u < R; ++u) c += keys[u] >= trial;
+        } else {
+          for (int i = lane; i < a.V; i += 64) c += prune_key(in_at<DT>(x, i)) >= trial;
+        }
+        if (wave_sum(c) >= n) tau = trial;
+      }
+      if (R > 0) {
+#pragma unroll
+        for (int u = 0; u < R; ++u) { g += keys[u] > tau; e += keys[u] == tau; }
+      } else {
+        for (int i = lane; i < a.V; i += 64) {
+          const uint32_t k = prune_key(in_at<DT>(x, i));
+          g += k > tau;
+          e += k == tau;
+        }
+      }
+      g = wave_sum(g);
+      e = wave_sum(e);
+      if (e > n - g) {  // equal values straddle the cut: std::sort decides which of them are kept
+        tie = true; first_tie = g;
+      }
+      // gather the kept values
+      auto take = [&](int i, uint32_t k, bool valid) {
+        const bool keep = valid && (k > tau || (k == tau && !(flag || tie)));
+        const unsigned long long m = __ballot(keep);
+        if (keep) {
+          const int p = base + __popcll(m & ((1ull << lane) - 1ull));
+          lkey[p] = k;
+          lidx[p] = i;
+        }
+        base += __popcll(m);
+      };
+      if (R > 0) {
+#pragma unroll
+        for (int u = 0; u < R; ++u) take(lane + 64 * u, keys[u], lane + 64 * u < a.V);
+      } else {
+        for (int i0 = 0; i0 < a.V; i0 += 64) {
+          const int i = i0 + lane;
+          take(i, i < a.V ? prune_key(in_at<DT>(x, i)) : 0u, i < a.V);
+        }
+      }
+    }
+    const int kept = base;  // == n unless flagged
+    __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): the wave's own LDS writes are visible to its other lanes
+    // rank (descending); equal kept values -> their order is std::sort's business
+    int *och = a.ch + (size_t)r * a.stride;
+    float *olp = a.lp + (size_t)r * a.stride;
+    for (int q = lane; q < kept; q += 64) {
+      const uint32_t mine = lkey[q];
+      int rank = 0, dup = 0;
+      for (int o = 0; o < kept; ++o) {
+        const uint32_t k = lkey[o];
+        rank += k > mine;
+        dup += k == mine;
+      }
+      if (dup > 1) {
+        tie = true; first_tie = rank < first_tie ? rank : first_tie;
+      }
+      const int idx = lidx[q];
+      float v = in_at<DT>(x, idx);
+      if (!a.log_input) {  // decoder_utils.cpp:42
+        v = (float)ctcmath::log_f64((double)v + (double)FLT_MIN, g_t64);
+      }
+      if (dup <= 1) { och[rank] = idx; olp[rank] = v; sidx[rank] = idx; }
+    }
+    flag = __ballot(flag) != 0ull;
+    int len = kept;
+    int cut_n = kept;  // entries the cut may walk: half rows with a tie stop before its first member
+    tie = __ballot(tie) != 0ull;
+    first_tie = wave_min(first_tie);
+    if (tie && !flag) {
+      if (a.cutoff_prob < 1.0) cut_n = first_tie;
+      else flag = true;  // (no cut: the kept length is cutoff_top_n, and the tie lies inside it)
+    }
+    bool cut_hit = false;
+    if (a.cutoff_prob < 1.0 && !flag) {
+      // decoder_utils.cpp:25-32: cum = log_sum_exp(cum, log p_i) starting from cum = 0.0 (sic), i.e. after i+1 terms
+      // cum = log(1 + p_0 + ... + p_i); keep going until cum >= cutoff_prob or cutoff_top_n entries.  Evaluated here
+      // as a wave-parallel prefix sum (differs from the reference's sequential double chain by ~1e-14 relative); a
+      // frame where any partial sum comes within 1e-9 of the threshold is left to prune_resolve_kernel's exact chain.
+      int stop = cut_n;  // number of entries kept
+      double carry = 0.0;
+      for (int i0 = 0; i0 < cut_n && stop == cut_n; i0 += 64) {
+        const int i = i0 + lane;
+        double p = 0.0;
+        if (i < cut_n) {
+          const double v = (double)in_at<DT>(x, sidx[i]);
+          p = a.log_input ? exp(v) : v;
+        }
+        double incl = p;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+          const double o = __shfl_up(incl, off, 64);
+          if (lane >= off) incl += o;
+        }
+        const double cum = log(1.0 + carry + incl);
+        const bool near = i < cut_n && (fabs(cum - a.cutoff_prob) <= 1e-9 * (1.0 + fabs(cum)) || !(cum == cum));
+        const bool hit = i < cut_n && (cum >= a.cutoff_prob || i + 1 >= a.top_n);
+        const unsigned long long mh = __ballot(hit), mn = __ballot(near);
+        const int firsthit = mh ? __ffsll((long long)mh) - 1 : 64;
+        if (mn && (__ffsll((long long)mn) - 1) <= firsthit) flag = true;  // ambiguous before (or at) the stopping point
+        if (mh) { stop = i0 + firsthit + 1; cut_hit = true; }
+        carry += f64_from_lane(incl, 63);
+      }
+      len = stop;
+      flag = __ballot(flag) != 0ull;
+    }
+    if (tie && !cut_hit) flag = true;  // the kept length reaches the first group of equal values
+    if (lane == 0) {
+      a.cnt[r] = len;
+      if (flag) {
+        const unsigned k = atomicAdd(a.n_flag, 1u);
+        if (k < a.flag_cap) a.flag_rows[k] = (unsigned)r;
+      }
+    }
+  }
+}
+
+// The kept length of a frame ranked by one of the workgroup kernels (wave 0), for half rows with equal values inside cutoff_top_n
+// (prune_rows_kernel says why this is exact): the cut walks the distinct values before the first such group only, and the frame is
+// flagged unless it stops there.  Every lane of the wave passes its own (tie, first_tie).
+
+__device__ __forceinline__ int prune_half_tie_cut(const PruneArgs &a, const float *sval, int kept, int lane, bool &flag, bool tie, int first_tie,
+                                                  const uint64_t *tbl) {
+  tie = __ballot(tie) != 0ull;
+  if (!tie || flag) {
+    flag = flag || tie;
+    return a.cutoff_prob < 1.0 && !flag ? prune_cumulative_cut(a, sval, nullptr, kept, lane, flag, tbl) : kept;
+  }
+  if (!(a.cutoff_prob < 1.0)) { flag = true; return kept; }
+  // the walk goes through the first tied position as well (sval holds the group's common value there -- or, where a listed label may
+  // tie an unlisted one, a value that can only delay a stop past first_tie): a cut that stops at or before first_tie settles the frame,
+  // one that reaches first_tie + 1 or runs on leaves it to prune_resolve_kernel.  (first_tie < kept: it is the rank of a kept label.)
+  const int ft = wave_min(first_tie);
+  const int len = prune_cumulative_cut(a, sval, nullptr, ft + 1, lane, flag, tbl);
+  if (len > ft) flag = true;
+  return len;
+}
+
+template <int F4, bool REG, int DT>
+__global__ void __launch_bounds__(256, REG ? (F4 <= 4 ? 8 : F4 <= 10 ? CTC_PRUNE_REG_OCC : 3) : CTC_PRUNE_WG_OCC) prune_rows_wg_half_kernel(PruneArgs a) {
+  const typename InElem<DT>::T *in = reinterpret_cast<const typename InElem<DT>::T *>(a.in);
+  extern __shared__ __attribute__((aligned(16))) char psm[];
+  __shared__ uint32_t s_bound[4];
+  __shared__ int s_cnt;
+  const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int n = a.top_n < a.V ? a.top_n : a.V;
+  const int nq = (n + 3) >> 2;  // per-wave share
+  // LDS: the kept values in final order (for the cumulative cut) | spare | (unused) | candidate keys | their labels | their values
+  float *sval = (float *)psm;
+  uint32_t *ckey = (uint32_t *)(sval + ((3 * a.stride + 3) & ~3));  // (16-byte aligned: read four keys at a time)
+  int *cidx = (int *)ckey + kPruneCand;
+  float *cval = (float *)(cidx + kPruneCand);
+  const int nv4 = a.V >> 2;
+  constexpr int kChunk = F4 < 5 ? F4 : 5;  // 128-bit loads in flight per thread (measured: 2, 4 and 10 are slower)
+  for (long long r = blockIdx.x; r < a.rows; r += gridDim.x) {
+    if (a.seq_lens) {
+      const long long b = r / a.T;
+      int len = a.seq_lens[b];
+      len = len < 0 ? 0 : len;
+      if ((int)(r - b * a.T) >= len) continue;
+    }
+    const typename InElem<DT>::T *x4 = in + (size_t)r * a.V;
+    if (tid == 0) s_cnt = 0;
+    uint32_t lmax = 0;
+    float4 vr[REG ? F4 : 1];
+    int tq = tid;
+    if (REG) {
+      asm volatile("" : "+v"(tq));  // (opaque per frame: prune_logits_wg_kernel says why)
+#pragma unroll
+      for (int u = 0; u < F4; ++u) {
+        const int i4 = tq + 256 * u;
+        vr[u] = i4 < nv4 ? in_load4<DT>(x4, i4) : make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
+      }
+#pragma unroll
+      for (int u = 0; u < F4; ++u) {
+        const int i4 = tq + 256 * u;
+        if (i4 < nv4) {
+          const uint32_t k0 = prune_key(vr[u].x), k1 = prune_key(vr[u].y), k2 = prune_key(vr[u].z), k3 = prune_key(vr[u].w);
+          const uint32_t m01 = k0 > k1 ? k0 : k1, m23 = k2 > k3 ? k2 : k3, m = m01 > m23 ? m01 : m23;
+          lmax = m > lmax ? m : lmax;
+        }
+      }
+    }
+    for (int u0 = 0; !REG && u0 < F4; u0 += kChunk) {
+      float4 v[kChunk];
+#pragma unroll
+      for (int u = 0; u < kChunk; ++u) {
+        const int i4 = tid + 256 * (u0 + u);
+        v[u] = (u0 + u < F4 && i4 < nv4) ? in_load4<DT>(x4, i4) : make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
+      }
+#pragma unroll
+      for (int u = 0; u < kChunk; ++u) {
+        const int i4 = tid + 256 * (u0 + u);
+        if (u0 + u < F4 && i4 < nv4) {
+          const uint32_t k0 = prune_key(v[u].x), k1 = prune_key(v[u].y), k2 = prune_key(v[u].z), k3 = prune_key(v[u].w);
+          const uint32_t m01 = k0 > k1 ? k0 : k1, m23 = k2 > k3 ? k2 : k3, m = m01 > m23 ? m01 : m23;
+          lmax = m > lmax ? m : lmax;
+        }
+      }
+    }
+    uint32_t bw = 0;
+    for (int bit = 31; bit >= 12; --bit) {
+      const uint32_t trial = bw | (1u << bit);
+      if (__popcll(__ballot(lmax >= trial)) >= nq) bw = trial;
+    }
+    if (lane == 0) s_bound[wave] = bw;
+    __syncthreads();
+    uint32_t bound = s_bound[0];
+    bound = s_bound[1] < bound ? s_bound[1] : bound;
+    bound = s_bound[2] < bound ? s_bound[2] : bound;
+    bound = s_bound[3] < bound ? s_bound[3] : bound;
+    if (REG) {
+      if (lmax >= bound && lmax != 0u) {
+#pragma unroll
+        for (int u = 0; u < F4; ++u) {
+          const int i4 = tq + 256 * u;
+          if (i4 < nv4) {
+            const float4 v = vr[u];
+            const uint32_t kk[4] = {prune_key(v.x), prune_key(v.y), prune_key(v.z), prune_key(v.w)};
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+              if (kk[e] >= bound && kk[e] != 0u) {
+                const int p = atomicAdd(&s_cnt, 1);
+                if (p < kPruneCand) { ckey[p] = kk[e]; cidx[p] = 4 * i4 + e; cval[p] = e == 0 ? v.x : e == 1 ? v.y : e == 2 ? v.z : v.w; }
+              }
+          }
+        }
+      }
+    } else if (lmax >= bound && lmax != 0u) {  // (only the few threads that hold a value at or above the bound sweep again)
+      for (int u = 0; u < F4; ++u) {
+        const int i4 = tid + 256 * u;
+        if (i4 >= nv4) break;
+        const float4 v = in_load4<DT>(x4, i4);
+        const uint32_t kk[4] = {prune_key(v.x), prune_key(v.y), prune_key(v.z), prune_key(v.w)};
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+          if (kk[e] >= bound && kk[e] != 0u) {
+            const int p = atomicAdd(&s_cnt, 1);
+            if (p < kPruneCand) { ckey[p] = kk[e]; cidx[p] = 4 * i4 + e; cval[p] = e == 0 ? v.x : e == 1 ? v.y : e == 2 ? v.z : v.w; }
+          }
+      }
+    }
+    __syncthreads();
+    const int ns = s_cnt;
+    if (wave == 0) {
+      bool flag = ns > kPruneCand;  // more values above the bound than the list holds: prune_resolve_kernel decides this frame
+      bool tie = false;     // (half rows: prune_half_tie_cut)
+      int first_tie = n;
+      int kept = 0;
+      int *och = a.ch + (size_t)r * a.stride;
+      float *olp = a.lp + (size_t)r * a.stride;
+      if (!flag) {
+        // every lane ranks its own candidates among all of them: rank = #greater; the n-th largest has rank < n <= rank + #equal
+        // (everything this wave needs from here on sits in LDS -- the other three waves of the workgroup wait for it, so a
+        //  global access or a chain of dependent LDS reads here is paid by the whole row: the keys are read four at a
+        //  time, the values come from the list the second sweep filled)
+        for (int p = ns + lane; p < ((ns + 3) & ~3); p += 64) ckey[p] = 0u;  // pad to a multiple of four, below every real key
+        __builtin_amdgcn_s_waitcnt(0xc07f);
+        for (int q0 = 0; q0 < ns; q0 += 64) {
+          const int q = q0 + lane;
+          const uint32_t mine = q < ns ? ckey[q] : 0xFFFFFFFFu;
+          int gg = 0, ee = 0;
+          for (int o = 0; o < ns; o += 4) {
+            const uint4 k4 = *reinterpret_cast<const uint4 *>(ckey + o);
+            gg += (k4.x > mine) + (k4.y > mine) + (k4.z > mine) + (k4.w > mine);
+            ee += (k4.x == mine) + (k4.y == mine) + (k4.z == mine) + (k4.w == mine);
+          }
+          const bool keep = q < ns && gg < n;
+          if (keep && ee > 1) {  // (a straddling group has ee > 1; every member writes the group's value: prune_half_tie_cut reads it)
+            tie = true; first_tie = gg < first_tie ? gg : first_tie;
+            sval[gg] = cval[q];
+          }
+          if (keep && ee == 1) {
+            const int idx = cidx[q];
+            float v = cval[q];
+            if (!a.log_input) {  // decoder_utils.cpp:42
+              v = (float)ctcmath::log_f64((double)v + (double)FLT_MIN, g_t64);
+            }
+            och[gg] = idx; olp[gg] = v; sval[gg] = cval[q];  // (sval: the row's own value, before any prob -> log conversion)
+          }
+          kept += __popcll(__ballot(keep));
+        }
+        if (kept > n) kept = n;
+      }
+      __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): the wave's own LDS writes are visible to its other lanes
+      flag = __ballot(flag) != 0ull;
+      int len = kept;
+      len = prune_half_tie_cut(a, sval, kept, lane, flag, tie, first_tie, a.tables);
+      if (lane == 0) {
+        a.cnt[r] = len;
+        if (flag) {
+          const unsigned k = atomicAdd(a.n_flag, 1u);
+          if (k < a.flag_cap) a.flag_rows[k] = (unsigned)r;
+        }
+      }
+    }
+    __syncthreads();  // the lists are reused by the next frame
+  }
+}
+
+template <int F4, int DT>
+__global__ void __launch_bounds__(256, F4 <= 4 ? 6 : F4 <= 10 ? CTC_PRUNE_LOGITS_OCC : 3) prune_logits_wg_half_kernel(PruneArgs a, const uint64_t *tables) {
+  const typename InElem<DT>::T *in = reinterpret_cast<const typename InElem<DT>::T *>(a.in);
+  extern __shared__ __attribute__((aligned(16))) char psm[];
+  __shared__ uint64_t tbl[64];
+  __shared__ __attribute__((aligned(16))) LsmLds s;
+  __shared__ uint32_t s_bound[4];
+  __shared__ int s_cnt;
+  const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int n = a.top_n < a.V ? a.top_n : a.V;
+  const int nq = (n + 3) >> 2;  // per-wave share
+  float *sval = (float *)psm;
+  uint32_t *ckey = (uint32_t *)(sval + ((3 * a.stride + 3) & ~3));
+  int *cidx = (int *)ckey + kPruneCand;
+  float *cval = (float *)(cidx + kPruneCand);
+  const int nv4 = a.V >> 2;
+  if (tid < 64) tbl[tid] = tables[tid];
+  __syncthreads();
+  for (long long r = blockIdx.x; r < a.rows; r += gridDim.x) {
+    if (a.seq_lens) {
+      const long long b = r / a.T;
+      int len = a.seq_lens[b];
+      len = len < 0 ? 0 : len;
+      if ((int)(r - b * a.T) >= len) continue;
+    }
+    const typename InElem<DT>::T *x4 = in + (size_t)r * a.V;
+    // (the thread index, opaque per frame: derived from the hoisted one, every chunk's predicate and offsets would be kept in
+    //  registers across the frame loop -- thirty-odd of them, spilled)
+    int tq = tid;
+    asm volatile("" : "+v"(tq));
+    float4 v[F4];
+#pragma unroll
+    for (int u = 0; u < F4; ++u) {
+      const int i4 = tq + 256 * u;
+      v[u] = i4 < nv4 ? in_load4<DT>(x4, i4) : make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
+    }
+    if (tid == 0) s_cnt = 0;
+    // (maxima on the values themselves -- a NaN is skipped, as by the one-wave kernel; the key of the thread's maximum is the
+    //  maximum of its keys whenever the row holds no NaN, and rows that do are flagged below)
+    float mine = -INFINITY;
+#pragma unroll
+    for (int u = 0; u < F4; ++u) mine = fmaxf(fmaxf(fmaxf(mine, v[u].x), fmaxf(v[u].y, v[u].z)), v[u].w);
+    const uint32_t lmax = prune_key(mine);
+    uint32_t bw = 0;
+    for (int bit = 31; bit >= 12; --bit) {
+      const uint32_t trial = bw | (1u << bit);
+      if (__popcll(__ballot(lmax >= trial)) >= nq) bw = trial;
+    }
+    if (lane == 0) s_bound[wave] = bw;
+    const float m = wg_row_max(mine, s, tid);  // (contains a barrier: s_bound is in place)
+    uint32_t bound = s_bound[0];
+    bound = s_bound[1] < bound ? s_bound[1] : bound;
+    bound = s_bound[2] < bound ? s_bound[2] : bound;
+    bound = s_bound[3] < bound ? s_bound[3] : bound;
+    float ls = 0.0f;
+    bool rowflag = !(m > -INFINITY);
+    if (!rowflag) {
+      const float sum = wg_exp_sum<F4>(v, nv4, m, s, tbl, tq);
+      rowflag = !(sum == sum);  // a NaN or +inf among the logits: (x - m) is a NaN for it, and so is the sum
+      ls = ctcmath::logf_normal(sum, tbl);
+    }
+    if (tid == 0) { a.row_max[r] = m; a.row_lse[r] = ls; }
+    // the labels at or above the bound, compared as values: for numbers, x >= value(bound) <=> key(x) >= bound (the key is monotone
+    // and value(bound)'s key is bound itself); a bound below every number's key decodes to a NaN pattern: everything is listed
+    const float bf = prune_key_value(bound);
+    const bool all = bound <= prune_key(-INFINITY);
+    if (!rowflag && (all || mine >= bf)) {
+#pragma unroll
+      for (int u = 0; u < F4; ++u) {
+        const int i4 = tq + 256 * u;
+        if (i4 < nv4) {
+          const float xs[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            if (all || xs[e] >= bf) {
+              const int p = atomicAdd(&s_cnt, 1);
+              if (p < kPruneCand) { const float y = (xs[e] - m) - ls; ckey[p] = prune_key(y); cidx[p] = 4 * i4 + e; cval[p] = y; }
+            }
+          }
+        }
+      }
+    }
+    __syncthreads();
+    const int ns = s_cnt;
+    if (wave == 0) {
+      bool flag = rowflag || ns > kPruneCand;
+      bool tie = false;     // (half rows: prune_half_tie_cut)
+      int first_tie = n;
+      int kept = 0;
+      int *och = a.ch + (size_t)r * a.stride;
+      float *olp = a.lp + (size_t)r * a.stride;
+      if (!flag) {
+        // the image of the bound: no label outside the list has a larger y
+        const uint32_t ybkey = bound ? prune_key((prune_key_value(bound) - m) - ls) : 0u;
+        for (int p = ns + lane; p < ((ns + 3) & ~3); p += 64) ckey[p] = 0u;
+        __builtin_amdgcn_s_waitcnt(0xc07f);
+        for (int q0 = 0; q0 < ns; q0 += 64) {
+          const int q = q0 + lane;
+          const uint32_t mine_k = q < ns ? ckey[q] : 0xFFFFFFFFu;
+          int gg = 0, ee = 0;
+          for (int o = 0; o < ns; o += 4) {
+            const uint4 k4 = *reinterpret_cast<const uint4 *>(ckey + o);
+            gg += (k4.x > mine_k) + (k4.y > mine_k) + (k4.z > mine_k) + (k4.w > mine_k);
+            ee += (k4.x == mine_k) + (k4.y == mine_k) + (k4.z == mine_k) + (k4.w == mine_k);
+          }
+          const bool keep = q < ns && gg < n;
+          // (a label outside the list that could tie with this one: a group that may begin at gg -- and unlisted labels that rank
+          //  above it may exist too: positions from gg on are uncertain, the ones before it exact)
+          if (keep && (ee > 1 || mine_k <= ybkey)) {
+            tie = true; first_tie = gg < first_tie ? gg : first_tie;
+            sval[gg] = cval[q];
+          }
+          if (keep && ee == 1) { och[gg] = cidx[q]; olp[gg] = cval[q]; sval[gg] = cval[q]; }
+          kept += __popcll(__ballot(keep));
+        }
+        if (kept > n) kept = n;
+      }
+      __builtin_amdgcn_s_waitcnt(0xc07f);
+      flag = __ballot(flag) != 0ull;
+      int len = kept;
+      len = prune_half_tie_cut(a, sval, kept, lane, flag, tie, first_tie, tbl);
+      if (lane == 0) {
+        a.cnt[r] = len;
+        if (flag) {
+          const unsigned k = atomicAdd(a.n_flag, 1u);
+          if (k < a.flag_cap) a.flag_rows[k] = (unsigned)r;
+        }
+      }
+    }
+    __syncthreads();  // the lists are reused by the next frame
+  }
+}
+
+template <int DT>
+__device__ int prune_exact_cut_half(const PruneArgs &a, const typename InElem<DT>::T *row, const int *sidx, int n, float m, float ls) {
+  double cum = 0.0;
+  int keep = 0;
+  for (int i = 0; i < n; ++i) {
+    const double v = (double)prune_row_value(a, in_at<DT>(row, sidx[i]), m, ls);
+    cum = ctcmath::lse_f64(cum, a.log_input ? v : ctcmath::log_f64(v, g_t64), g_t64);
+    ++keep;
+    if (cum >= a.cutoff_prob || keep >= a.top_n) break;
+  }
+  return keep;
+}
+
+template <int DT>
+__global__ void __launch_bounds__(kResolveThreads) prune_resolve_half_kernel(PruneArgs a, char *far, size_t far_stride) {
+  extern __shared__ __attribute__((aligned(16))) char rsm_lds[];
+  __shared__ uint32_t s_wsum[kResolveThreads / 64];
+  char *rsm = far ? far + (size_t)blockIdx.x * far_stride : rsm_lds;
+  const int tid = (int)threadIdx.x, lane = tid & 63;
+  const int V = a.V, n = a.top_n < V ? a.top_n : V;
+  const int tcap = prune_resolve_task_cap(V);
+  unsigned long long *v = (unsigned long long *)rsm;
+  uint16_t *Lp = (uint16_t *)(v + V), *Rp = Lp + (V + 2), *cur = Rp + (V + 2), *nxt = cur + 3 * tcap, *small = nxt + 3 * tcap;
+  int *bstack = (int *)(((uintptr_t)(small + 2 * (V / 2 + 1)) + 15) & ~(uintptr_t)15);
+  int *cnt = bstack + 3 * 64, *sidx = cnt + 4;
+  const unsigned raw = *a.n_flag, nf = raw < a.flag_cap ? raw : a.flag_cap;
+  WgSortX x{s_wsum};
+  for (unsigned k = blockIdx.x; k < nf; k += gridDim.x) {
+    const long long r = (long long)a.flag_rows[k];
+    const typename InElem<DT>::T *row = reinterpret_cast<const typename InElem<DT>::T *>(a.in) + (size_t)r * V;
+    const float m = a.log_input == 2 ? a.row_max[r] : 0.0f, ls = a.log_input == 2 ? a.row_lse[r] : 0.0f;  // (raw logits: prune_logits_wg_kernel)
+    __syncthreads();
+    for (int i = tid; i < V; i += kResolveThreads) v[i] = ((unsigned long long)prune_key(prune_row_value(a, in_at<DT>(row, i), m, ls)) << 32) | (unsigned)i;
+    __syncthreads();
+    // decoder_utils.cpp:19-20: (index, double) pairs in index order, std::sort on the value alone, descending
+    // (stl_emul.h: long ranges split by the whole workgroup, the rest by one thread per range; only the ranges that reach
+    //  the first n places -- the prune pass keeps the best top_n of a row)
+    stlemu::sort_prefix_parallel(x, v, V, n, kResolveBigCut, [](unsigned long long e) { return (uint32_t)(e >> 32); }, Lp, Rp, cur, nxt, small,
+                                 cnt, bstack);
+    if (tid < 64) {
+      int *och = a.ch + (size_t)r * a.stride;
+      float *olp = a.lp + (size_t)r * a.stride;
+      for (int q = lane; q < n; q += 64) {
+        const int idx = (int)(uint32_t)v[q];
+        float val = prune_row_value(a, in_at<DT>(row, idx), m, ls);
+        if (!a.log_input) val = (float)ctcmath::log_f64((double)val + (double)FLT_MIN, g_t64);  // decoder_utils.cpp:42
+        och[q] = idx; olp[q] = val; sidx[q] = idx;
+      }
+      __threadfence_block();  // the wave's own writes (LDS or global) are visible to its lane 0
+      if (lane == 0) a.cnt[r] = a.cutoff_prob < 1.0 ? prune_exact_cut_half<DT>(a, row, sidx, n, m, ls) : n;
+    }
+  }
+}
+
 // Compact results (beam_core.h OutRefs::c_*) -> the reference's tensors: tokens / timesteps [B, K, T], zero outside the
 // valid prefixes.  HBM-bound (it writes 8 B per label position of the padded pair).  One workgroup per item; every wave
 // takes whole rows, its lanes consecutive label positions (coalesced 256-byte stores).  Label q of DFS entry j is held
@@ -1132,6 +1861,8 @@ struct ctcd_decoder {
   bool no_hook_wait = false;     // tests: a callback scorer's launches end at a miss (the form of rounds 4-5) instead of waiting for the answer
   int last_cb_waits = 0;         // answer batches the last call's launches were handed while they waited
   bool no_fused_logits = false;  // tests: raw logits always through the one-wave log_softmax pass and the separate prune
+  int in_dtype = CTCD_DTYPE_F32;       // ctcd_set_input_dtype: the element type of probs / logits on every entry point
+  int last_in_dtype = CTCD_DTYPE_F32;  // the element type the last call's pre-passes read (ctcd_last_input_dtype)
   Buf prof, dbg, tl;
   int tl_f0 = 0, tl_nf = 0;
   int status_items = 0;          // items of the launch whose status words (and shape statistic) are in d->status
@@ -1419,6 +2150,14 @@ int ctcd_set_subtree_search(ctcd_decoder *d, int mode) {
 }
 int ctcd_last_subtree_search(const ctcd_decoder *d) { return d ? d->last_subtree_search : -1; }
 
+int ctcd_set_input_dtype(ctcd_decoder *d, int dtype) {
+  if (!d || (dtype != CTCD_DTYPE_F32 && dtype != CTCD_DTYPE_F16 && dtype != CTCD_DTYPE_BF16))
+    return fail(CTCD_EINVAL, "dtype must be CTCD_DTYPE_F32, CTCD_DTYPE_F16 or CTCD_DTYPE_BF16");
+  d->in_dtype = dtype;
+  return CTCD_OK;
+}
+int ctcd_last_input_dtype(ctcd_decoder *d) { return d ? d->last_in_dtype : -1; }
+
 int ctcd_set_threads(ctcd_decoder *d, int t) {
   if (!d || t < 0 || t > 1024 || (t && (t < 64 || (t & (t - 1))))) return fail(CTCD_EINVAL, "threads must be 0 (automatic) or a power of two in [64, 1024]");
   d->threads = t;
@@ -1450,21 +2189,104 @@ static const void *streamed_input_twin(const void *fn) {
 }
 
 // log_softmax of every frame (ctcd_log_softmax's definition): long rows by a workgroup each, short ones by a wave each
-static int launch_log_softmax(ctcd_decoder *d, const float *in, float *out, long long rows, const int32_t *lens, int T, int V, hipStream_t stream) {
+extern "C++" {  // (host helpers of the pre-pass launches, one template instantiation per input dtype)
+// the element size of an input dtype, and the alignment the workgroup pre-pass kernels need of a row base (four elements per load)
+static size_t in_elem_bytes(int dt) { return dt == CTCD_DTYPE_F32 ? 4 : 2; }
+
+// the log-softmax kernels of one input dtype (the float32 ones, or their half instantiations)
+template <int DT> static const void *lsm_wg_fn(int V) {
+  if constexpr (DT == kInF32)
+    return V <= 1024 ? (const void *)log_softmax_rows_wg_kernel<1> : V <= 2048 ? (const void *)log_softmax_rows_wg_kernel<2>
+         : V <= 4096 ? (const void *)log_softmax_rows_wg_kernel<4> : V <= 10240 ? (const void *)log_softmax_rows_wg_kernel<10>
+         : (const void *)log_softmax_rows_wg_kernel<16>;
+  else
+    return V <= 1024 ? (const void *)log_softmax_rows_wg_half_kernel<1, DT> : V <= 2048 ? (const void *)log_softmax_rows_wg_half_kernel<2, DT>
+         : V <= 4096 ? (const void *)log_softmax_rows_wg_half_kernel<4, DT> : V <= 10240 ? (const void *)log_softmax_rows_wg_half_kernel<10, DT>
+         : (const void *)log_softmax_rows_wg_half_kernel<16, DT>;
+}
+template <int DT> static const void *lsm_wave_fn() {
+  if constexpr (DT == kInF32) return (const void *)log_softmax_rows_kernel;
+  else return (const void *)log_softmax_rows_half_kernel<DT>;
+}
+template <int DT>
+static int launch_log_softmax_t(ctcd_decoder *d, const float *in, float *out, long long rows, const int32_t *lens, int T, int V, hipStream_t stream) {
   const uint64_t *tb = (const uint64_t *)d->tables.p;
-  if (V % 4 == 0 && V > 256 && V <= 16384 && (((uintptr_t)in | (uintptr_t)out) & 15) == 0 && !d->no_fused_logits) {
+  void *args[] = {(void *)&in, (void *)&out, (void *)&rows, (void *)&lens, (void *)&T, (void *)&V, (void *)&tb};
+  if (V % 4 == 0 && V > 256 && V <= 16384 && (((uintptr_t)in & (4 * in_elem_bytes(DT) - 1)) | ((uintptr_t)out & 15)) == 0 && !d->no_fused_logits) {
     const dim3 grid((unsigned)std::min<long long>(rows, 256 * 32));
-    if (V <= 1024) hipLaunchKernelGGL(log_softmax_rows_wg_kernel<1>, grid, dim3(256), 0, stream, in, out, rows, lens, T, V, tb);
-    else if (V <= 2048) hipLaunchKernelGGL(log_softmax_rows_wg_kernel<2>, grid, dim3(256), 0, stream, in, out, rows, lens, T, V, tb);
-    else if (V <= 4096) hipLaunchKernelGGL(log_softmax_rows_wg_kernel<4>, grid, dim3(256), 0, stream, in, out, rows, lens, T, V, tb);
-    else if (V <= 10240) hipLaunchKernelGGL(log_softmax_rows_wg_kernel<10>, grid, dim3(256), 0, stream, in, out, rows, lens, T, V, tb);
-    else hipLaunchKernelGGL(log_softmax_rows_wg_kernel<16>, grid, dim3(256), 0, stream, in, out, rows, lens, T, V, tb);
+    HIP_TRY(hipLaunchKernel(lsm_wg_fn<DT>(V), grid, dim3(256), args, 0, stream));
   } else {
-    hipLaunchKernelGGL(log_softmax_rows_kernel, dim3((unsigned)std::min<long long>((rows + 3) / 4, 256 * 64)), dim3(256), 0, stream, in, out, rows, lens, T, V, tb);
+    HIP_TRY(hipLaunchKernel(lsm_wave_fn<DT>(), dim3((unsigned)std::min<long long>((rows + 3) / 4, 256 * 64)), dim3(256), args, 0, stream));
+  }
+  return CTCD_OK;
+}
+static int launch_log_softmax(ctcd_decoder *d, const float *in, float *out, long long rows, const int32_t *lens, int T, int V, hipStream_t stream,
+                              int dt = CTCD_DTYPE_F32) {
+  const int rc = dt == CTCD_DTYPE_F16 ? launch_log_softmax_t<kInF16>(d, in, out, rows, lens, T, V, stream)
+                 : dt == CTCD_DTYPE_BF16 ? launch_log_softmax_t<kInBF16>(d, in, out, rows, lens, T, V, stream)
+                                         : launch_log_softmax_t<kInF32>(d, in, out, rows, lens, T, V, stream);
+  if (rc) return rc;
+  HIP_TRY(hipGetLastError());
+  return CTCD_OK;
+}
+
+// The elementwise pre-passes into the decoder's workspace: prob -> log (to_log), or half rows widened as they are.
+static int launch_elementwise(const float *in, float *out, size_t n, const int32_t *lens, int T, int V, hipStream_t stream, int dt, bool to_log) {
+  const int blocks = (int)std::min<size_t>((n + 255) / 256, 4096);
+  if (to_log) {
+    const void *fn = dt == CTCD_DTYPE_F16 ? (const void *)prob_to_log_half_kernel<kInF16> : dt == CTCD_DTYPE_BF16 ? (const void *)prob_to_log_half_kernel<kInBF16>
+                                                                                                               : (const void *)prob_to_log_kernel;
+    void *args[] = {(void *)&in, (void *)&out, (void *)&n, (void *)&lens, (void *)&T, (void *)&V};
+    HIP_TRY(hipLaunchKernel(fn, dim3(blocks), dim3(256), args, 0, stream));
+  } else {
+    const void *fn = dt == CTCD_DTYPE_F16 ? (const void *)widen_rows_kernel<kInF16> : (const void *)widen_rows_kernel<kInBF16>;
+    void *args[] = {(void *)&in, (void *)&out, (void *)&n, (void *)&lens, (void *)&T, (void *)&V};
+    HIP_TRY(hipLaunchKernel(fn, dim3(blocks), dim3(256), args, 0, stream));
   }
   HIP_TRY(hipGetLastError());
   return CTCD_OK;
 }
+
+// The vocabulary-prune kernels for one input dtype (decode_common picks among them by shape)
+struct PruneFns { const void *rows, *wg, *wg_reg, *logits, *resolve; };
+template <int DT>
+static PruneFns prune_fns(int V);
+template <>
+PruneFns prune_fns<kInF32>(int V) {  // (the float32 kernels)
+  PruneFns f;
+  f.rows = V <= 64 ? (const void *)prune_rows_kernel<1> : V <= 256 ? (const void *)prune_rows_kernel<4>
+           : V <= 1024 ? (const void *)prune_rows_kernel<16> : V <= 4096 ? (const void *)prune_rows_kernel<64>
+           : V <= 10240 ? (const void *)prune_rows_kernel<160> : (const void *)prune_rows_kernel<0>;
+  f.wg = V <= 1024 ? (const void *)prune_rows_wg_kernel<1> : V <= 2048 ? (const void *)prune_rows_wg_kernel<2>
+         : V <= 4096 ? (const void *)prune_rows_wg_kernel<4> : V <= 10240 ? (const void *)prune_rows_wg_kernel<10>
+         : (const void *)prune_rows_wg_kernel<16>;
+  f.wg_reg = V <= 1024 ? (const void *)prune_rows_wg_kernel<1, true> : V <= 2048 ? (const void *)prune_rows_wg_kernel<2, true>
+             : V <= 4096 ? (const void *)prune_rows_wg_kernel<4, true> : V <= 10240 ? (const void *)prune_rows_wg_kernel<10, true> : f.wg;
+  f.logits = V <= 1024 ? (const void *)prune_logits_wg_kernel<1> : V <= 2048 ? (const void *)prune_logits_wg_kernel<2>
+             : V <= 4096 ? (const void *)prune_logits_wg_kernel<4> : V <= 10240 ? (const void *)prune_logits_wg_kernel<10>
+             : (const void *)prune_logits_wg_kernel<16>;
+  f.resolve = (const void *)prune_resolve_kernel;
+  return f;
+}
+template <int DT>
+static PruneFns prune_fns(int V) {  // (their half instantiations)
+  PruneFns f;
+  f.rows = V <= 64 ? (const void *)prune_rows_half_kernel<1, DT> : V <= 256 ? (const void *)prune_rows_half_kernel<4, DT>
+           : V <= 1024 ? (const void *)prune_rows_half_kernel<16, DT> : V <= 4096 ? (const void *)prune_rows_half_kernel<64, DT>
+           : V <= 10240 ? (const void *)prune_rows_half_kernel<160, DT> : (const void *)prune_rows_half_kernel<0, DT>;
+  f.wg = V <= 1024 ? (const void *)prune_rows_wg_half_kernel<1, false, DT> : V <= 2048 ? (const void *)prune_rows_wg_half_kernel<2, false, DT>
+         : V <= 4096 ? (const void *)prune_rows_wg_half_kernel<4, false, DT> : V <= 10240 ? (const void *)prune_rows_wg_half_kernel<10, false, DT>
+         : (const void *)prune_rows_wg_half_kernel<16, false, DT>;
+  // (the row held in registers between the two looks at it: V <= 10240; beyond, the registers run out)
+  f.wg_reg = V <= 1024 ? (const void *)prune_rows_wg_half_kernel<1, true, DT> : V <= 2048 ? (const void *)prune_rows_wg_half_kernel<2, true, DT>
+             : V <= 4096 ? (const void *)prune_rows_wg_half_kernel<4, true, DT> : V <= 10240 ? (const void *)prune_rows_wg_half_kernel<10, true, DT> : f.wg;
+  f.logits = V <= 1024 ? (const void *)prune_logits_wg_half_kernel<1, DT> : V <= 2048 ? (const void *)prune_logits_wg_half_kernel<2, DT>
+             : V <= 4096 ? (const void *)prune_logits_wg_half_kernel<4, DT> : V <= 10240 ? (const void *)prune_logits_wg_half_kernel<10, DT>
+             : (const void *)prune_logits_wg_half_kernel<16, DT>;
+  f.resolve = (const void *)prune_resolve_half_kernel<DT>;
+  return f;
+}
+}  // extern "C++"
 
 static int decode_common(ctcd_decoder *d, const float *probs, const int32_t *seq_lens, int B, int T, int V, int beam,
                          double cutoff_prob, int cutoff_top_n, int blank_id, int log_input, int32_t *out_tok, int32_t *out_ts,
@@ -1597,17 +2419,31 @@ static int decode_common(ctcd_decoder *d, const float *probs, const int32_t *seq
   }
   // the rows the pre-passes cover (resumed launches of the scorer hook start inside the rows: StreamCall::row_lens)
   const int32_t *pre_lens = (sc && sc->row_lens) ? sc->row_lens : seq_lens;
+  // half rows (ctcd_set_input_dtype): the pre-pass kernels read them; `probs` keeps pointing at the caller's rows until a pass has
+  // written float32 rows into the workspace (dt = kInF32 from there on).  The decode kernels themselves only ever read float32.
+  int dt = d->in_dtype;
+  d->last_in_dtype = dt;
+  if (dt != CTCD_DTYPE_F32 && scorer && log_input != 2 && T > 0) {
+    // the LM tier reads the blank's value from the caller's rows (KernelArgs::raw): one widening pass into the workspace, then the
+    // float32 route (raw logits are normalised into the workspace below anyway)
+    if ((rc = d->lsm.ensure((size_t)B * T * V * 4))) return rc;
+    if (pre_lens) HIP_TRY(hipMemsetAsync(d->lsm.p, 0, (size_t)B * T * V * 4, stream));
+    if ((rc = launch_elementwise(probs, (float *)d->lsm.p, (size_t)B * T * V, pre_lens, T, V, stream, dt, false))) return rc;
+    probs = (const float *)d->lsm.p;
+    dt = CTCD_DTYPE_F32;
+  }
 
   // raw logits in front of a vocabulary prune: one pass does both (prune_logits_wg_kernel -- the normalised rows are never written).
   // Not with a scorer: the LM tier reads the blank's log-probability from the rows themselves (ctc_beam_search_decoder.cpp:78).
   const bool fuse_logits = log_input == 2 && dims.use_rank_table && T > 0 && !scorer && !d->no_fused_logits && V % 4 == 0 && V > 256 &&
-                           V <= 16384 && std::min(cutoff_top_n, V) <= 64 && ((uintptr_t)probs & 15) == 0;
+                           V <= 16384 && std::min(cutoff_top_n, V) <= 64 && ((uintptr_t)probs & (4 * in_elem_bytes(dt) - 1)) == 0;
   if (log_input == 2 && !fuse_logits) {  // raw logits: normalise once, in HBM; everything below sees log-probabilities
     if (T > 0) {
       if ((rc = d->lsm.ensure((size_t)B * T * V * 4))) return rc;
       if (pre_lens) HIP_TRY(hipMemsetAsync(d->lsm.p, 0, (size_t)B * T * V * 4, stream));  // frames past an utterance's end stay defined
-      if ((rc = launch_log_softmax(d, probs, (float *)d->lsm.p, (long long)B * T, pre_lens, T, V, stream))) return rc;
+      if ((rc = launch_log_softmax(d, probs, (float *)d->lsm.p, (long long)B * T, pre_lens, T, V, stream, dt))) return rc;
       probs = (const float *)d->lsm.p;
+      dt = CTCD_DTYPE_F32;
     }
     log_input = 1;
   }
@@ -1633,25 +2469,18 @@ static int decode_common(ctcd_decoder *d, const float *probs, const int32_t *seq
     const size_t psm = (size_t)wpb * (3 * (size_t)stride + 2 * kPruneCand) * 4;
     if (psm > (size_t)d->max_lds) return fail(CTCD_EUNSUPPORTED, "cutoff_top_n too large for the prune pass");
     const int blocks = (int)std::min<long long>((rows + wpb - 1) / wpb, 256 * 16);
-    const void *pfn = nullptr;
-    pfn = V <= 64 ? (const void *)prune_rows_kernel<1> : V <= 256 ? (const void *)prune_rows_kernel<4>
-                    : V <= 1024 ? (const void *)prune_rows_kernel<16> : V <= 4096 ? (const void *)prune_rows_kernel<64>
-                    : V <= 10240 ? (const void *)prune_rows_kernel<160> : (const void *)prune_rows_kernel<0>;
+    const PruneFns fns = dt == CTCD_DTYPE_F16 ? prune_fns<kInF16>(V) : dt == CTCD_DTYPE_BF16 ? prune_fns<kInBF16>(V) : prune_fns<kInF32>(V);
+    const void *pfn = fns.rows;
     bool wg_kernel = false;
-    if (V % 4 == 0 && V > 256 && V <= 16384 && std::min(cutoff_top_n, V) <= 64) {  // the bandwidth-shaped variant
+    // the bandwidth-shaped variant (half rows: four elements per 8-byte load, the row base 8-byte aligned)
+    if (V % 4 == 0 && V > 256 && V <= 16384 && std::min(cutoff_top_n, V) <= 64 && (dt == CTCD_DTYPE_F32 || ((uintptr_t)probs & 7) == 0)) {
       wg_kernel = true;
-      pfn = V <= 1024 ? (const void *)prune_rows_wg_kernel<1> : V <= 2048 ? (const void *)prune_rows_wg_kernel<2>
-          : V <= 4096 ? (const void *)prune_rows_wg_kernel<4> : V <= 10240 ? (const void *)prune_rows_wg_kernel<10>
-          : (const void *)prune_rows_wg_kernel<16>;
+      pfn = fns.wg;
       static const bool reg_rows = getenv("CTCD_PRUNE_REG") ? atoi(getenv("CTCD_PRUNE_REG")) != 0 : true;
-      if (reg_rows && !d->no_prune_reg)  // the row held in registers between the two looks at it (V <= 10240: beyond, the registers run out)
-        pfn = V <= 1024 ? (const void *)prune_rows_wg_kernel<1, true> : V <= 2048 ? (const void *)prune_rows_wg_kernel<2, true>
-            : V <= 4096 ? (const void *)prune_rows_wg_kernel<4, true> : V <= 10240 ? (const void *)prune_rows_wg_kernel<10, true> : pfn;
+      if (reg_rows && !d->no_prune_reg) pfn = fns.wg_reg;  // the row held in registers between the two looks at it
     }
     if (fuse_logits) {  // (same shape conditions)
-      pfn = V <= 1024 ? (const void *)prune_logits_wg_kernel<1> : V <= 2048 ? (const void *)prune_logits_wg_kernel<2>
-          : V <= 4096 ? (const void *)prune_logits_wg_kernel<4> : V <= 10240 ? (const void *)prune_logits_wg_kernel<10>
-          : (const void *)prune_logits_wg_kernel<16>;
+      pfn = fns.logits;
       if ((rc = d->pr_ml.ensure((size_t)rows * 8))) return rc;
     }
     const size_t psm_launch = wg_kernel ? (3 * (size_t)stride + 3 * kPruneCand + 4) * 4 : psm;
@@ -1668,7 +2497,7 @@ static int decode_common(ctcd_decoder *d, const float *probs, const int32_t *seq
     const size_t rbytes = prune_resolve_lds_bytes(V, std::min(cutoff_top_n, V));
     const bool in_lds = rbytes + 1024 <= (size_t)d->max_lds && !d->resolve_in_global;
     const int rblocks = in_lds ? 256 : 64;
-    if (in_lds) HIP_TRY(hipFuncSetAttribute((const void *)prune_resolve_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)rbytes));
+    if (in_lds) HIP_TRY(hipFuncSetAttribute(fns.resolve, hipFuncAttributeMaxDynamicSharedMemorySize, (int)rbytes));
     const size_t rstride = (rbytes + 255) / 256 * 256;
     if (!in_lds && (rc = d->prune_in.ensure(rstride * rblocks))) return rc;  // (rows too long for LDS: the sort's arrays in global memory)
     HIP_TRY(hipMemsetAsync(n_flag, 0, 8, stream));
@@ -1689,20 +2518,22 @@ static int decode_common(ctcd_decoder *d, const float *probs, const int32_t *seq
     //  what guarantees they fit -- said here, next to the launch, so that the two cannot drift apart: ADVICE r4)
     static_assert(kResolveMaxV >= 32767, "prune_resolve_kernel's 16-bit positions must cover every vocabulary the prune pass accepts");
     if (V > kResolveMaxV) return fail(CTCD_EUNSUPPORTED, "vocabulary pruning: too many labels for the std::sort replay's 16-bit positions");
-    hipLaunchKernelGGL(prune_resolve_kernel, dim3(rblocks), dim3(kResolveThreads), in_lds ? rbytes : 0, stream, pa, in_lds ? (char *)nullptr : (char *)d->prune_in.p, rstride);
+    char *rfar = in_lds ? (char *)nullptr : (char *)d->prune_in.p;
+    size_t rstride_arg = rstride;
+    void *rargs[] = {&pa, (void *)&rfar, (void *)&rstride_arg};
+    HIP_TRY(hipLaunchKernel(fns.resolve, dim3(rblocks), dim3(kResolveThreads), rargs, in_lds ? rbytes : 0, stream));
     HIP_TRY(hipGetLastError());
     // (statistics only: the number of flagged frames travels to page-locked memory behind the kernels; whoever asks for it
     //  -- ctcd_last_prune_flagged_rows -- waits for the stream)
     if (!d->h_flagged) HIP_TRY(hipHostMalloc((void **)&d->h_flagged, 8, hipHostMallocDefault));
     HIP_TRY(hipMemcpyAsync(d->h_flagged, n_flag, 4, hipMemcpyDeviceToHost, stream));
     d->flagged_pending = true;
-  } else if (!log_input && T > 0) {
+  } else if ((!log_input || dt != CTCD_DTYPE_F32) && T > 0) {
+    // probabilities -> log-probabilities, or half log-probability rows widened: the decode kernel reads float32 rows
     const size_t n = (size_t)B * T * V;
     if ((rc = d->logp.ensure(n * 4))) return rc;
-    const int blocks = (int)std::min<size_t>((n + 255) / 256, 4096);
     if (pre_lens) HIP_TRY(hipMemsetAsync(d->logp.p, 0, n * 4, stream));  // frames past an utterance's end stay defined
-    hipLaunchKernelGGL(prob_to_log_kernel, dim3(blocks), dim3(256), 0, stream, probs, (float *)d->logp.p, n, pre_lens, T, V);
-    HIP_TRY(hipGetLastError());
+    if ((rc = launch_elementwise(probs, (float *)d->logp.p, n, pre_lens, T, V, stream, dt, !log_input))) return rc;
     logp = (const float *)d->logp.p;
   }
 
@@ -2697,6 +3528,7 @@ int ctcd_beam_decode_to_host(ctcd_decoder *d, const float *probs, const int32_t 
   if (!d) return fail(CTCD_EINVAL, "decoder == NULL");
   int rc = check_args(B, T, V, beam, cutoff_top_n, blank_id, probs, out_tok, out_ts, out_sc, out_len);
   if (rc) return rc;
+  if (!probs_on_device && d->in_dtype != CTCD_DTYPE_F32) return fail(CTCD_EUNSUPPORTED, "half-precision input from host memory (cast it to float32)");
   if (B == 0) return CTCD_OK;
   std::lock_guard<std::mutex> host_lock(d->mu_host);
   rc = decode_to_host_locked(d, probs, seq_lens, probs_on_device, B, T, V, beam, num_processes, cutoff_prob, cutoff_top_n, blank_id, log_input,
@@ -2928,7 +3760,13 @@ int ctcd_log_softmax(ctcd_decoder *d, const float *logits, const int32_t *seq_le
       d->tables_ready = true;
     }
   }
-  return launch_log_softmax(d, logits, out, (long long)B * T, seq_lens, T, V, stream);
+  if (d->in_dtype != CTCD_DTYPE_F32) {  // (half rows in place: the float32 rows written would overrun rows not read yet)
+    const size_t n = (size_t)B * T * V;
+    const uintptr_t x0 = (uintptr_t)logits, x1 = x0 + n * in_elem_bytes(d->in_dtype), y0 = (uintptr_t)out, y1 = y0 + n * 4;
+    if (x0 < y1 && y0 < x1) return fail(CTCD_EINVAL, "half-precision logits: `out` must not overlap them (in-place is float32 only)");
+  }
+  d->last_in_dtype = d->in_dtype;
+  return launch_log_softmax(d, logits, out, (long long)B * T, seq_lens, T, V, stream, d->in_dtype);
 }
 
 // HIP-event timing of the decode kernel alone, on the stream it is launched on (bench.py's roofline figure).
@@ -2958,6 +3796,15 @@ int ctcd_last_prune_ms(ctcd_decoder *d, float *ms) {
   CTC_ON_DEVICE(d->device);
   HIP_TRY(hipEventSynchronize(d->ev3));
   HIP_TRY(hipEventElapsedTime(ms, d->ev2, d->ev3));
+  return CTCD_OK;
+}
+// From the end of the fast prune pass to the start of the decode kernel: prune_resolve_kernel over the flagged frames (and the copy
+// of their count behind it).
+int ctcd_last_resolve_ms(ctcd_decoder *d, float *ms) {
+  if (!d || !ms || !d->ev2 || !d->prune_timed) return fail(CTCD_EINVAL, "no timed prune pass");
+  CTC_ON_DEVICE(d->device);
+  HIP_TRY(hipEventSynchronize(d->ev0));
+  HIP_TRY(hipEventElapsedTime(ms, d->ev3, d->ev0));
   return CTCD_OK;
 }
 

@@ -238,6 +238,7 @@ long long ctcd_last_prune_host_rows(ctcd_decoder *dec);
 int ctcd_set_timing(ctcd_decoder *dec, int on);
 int ctcd_last_kernel_ms(ctcd_decoder *dec, float *ms);
 int ctcd_last_prune_ms(ctcd_decoder *dec, float *ms); /* the vocabulary-prune kernel of the same call (pruned configurations) */
+int ctcd_last_resolve_ms(ctcd_decoder *dec, float *ms); /* ... and what follows it up to the decode kernel: the flagged frames' replay */
 
 /* Test hook: device expf/logf/log_sum_exp (exact_math.h; modes 0..2) and binary64 log / exp / log_sum_exp<double>
  * (exact_math_f64.h; modes 3: log(p), 4: log(p + FLT_MIN), 5: exp(x) over float bit patterns, 6: pairs) vs the host C library. */
@@ -280,6 +281,23 @@ int ctcd_debug_beam_dump(ctcd_decoder *dec, int on, int *out, int T, int beam);
  * copies its compact results into (utterances beyond it are fetched from the device buffer afterwards; -1: default size,
  * -2: leave). */
 int ctcd_debug_set_host_path(ctcd_decoder *dec, int input_streaming, long long mirror_cap_labels);
+
+/* Half-precision input.  After ctcd_set_input_dtype(dec, CTCD_DTYPE_F16 or CTCD_DTYPE_BF16) every entry point of `dec` that
+ * takes `probs` / `logits` reads them as [B, T, V] IEEE binary16 / bfloat16 elements (device memory; the pointer keeps its
+ * `const float *` spelling), until the dtype is set again.  Widening to float32 is exact: the results are those of the same
+ * call on the float32 copy, bit for bit, without that copy -- the pre-passes (vocabulary prune, log_softmax, prob -> log) read
+ * the half rows themselves; where a decode kernel reads the caller's rows (no pruning, or the LM tier) one widening pass
+ * writes float32 rows into the decoder's workspace.  Host-memory input stays float32: ctcd_beam_decode_to_host with
+ * probs_on_device == 0 (and so the *_host entry points) returns CTCD_EUNSUPPORTED while a half dtype is set.
+ * ctcd_log_softmax's output stays float32, and with a half dtype `out` must not overlap `logits` (CTCD_EINVAL: in-place is float32
+ * only).  The dtype is state of `dec`, like ctcd_set_threads: threads that share a decoder and pass different dtypes must not let
+ * a set-and-call pair of one overlap a call of the other (a half buffer read as float32 is read twice its size).
+ * ctcd_last_input_dtype: the dtype the last call of `dec` read its rows as. */
+#define CTCD_DTYPE_F32 0
+#define CTCD_DTYPE_F16 1
+#define CTCD_DTYPE_BF16 2
+int ctcd_set_input_dtype(ctcd_decoder *dec, int dtype);
+int ctcd_last_input_dtype(ctcd_decoder *dec);
 
 /* Tuning / introspection. */
 int ctcd_set_threads(ctcd_decoder *dec, int threads_per_workgroup); /* 0 = automatic (default); else a power of two in [64, 1024] */
