@@ -269,6 +269,12 @@ class CTCBeamDecoder(object):
     def last_subtree_search(self):
         return int(_native.lib.ctcd_last_subtree_search(self._handle))
 
+    def last_layout(self):
+        """Test hook: the workspace layout of the last launch's kernel (include/ctcdecode_amd.h ctcd_debug_last_layout): 0 run-time,
+        1 fixed (beam <= 128, <= 32 labels), 2 the pruned default's (beam <= 112, cutoff_top_n <= 40), 3 wide beams at a compile-time
+        size, 4-6 wide beams with HBM scratch; -1 none yet."""
+        return int(_native.lib.ctcd_debug_last_layout(self._handle))
+
     def set_host_path(self, input_streaming=None, mirror_cap_labels=None):
         """Test hook for decode(): turn the streamed input off / on; shrink the host mirror of the compact results."""
         _native.check(_native.lib.ctcd_debug_set_host_path(self._handle, -1 if input_streaming is None else int(bool(input_streaming)),
@@ -678,6 +684,10 @@ class OnlineCTCBeamDecoder(object):
     def set_threads(self, n):
         """Test hook (as CTCBeamDecoder.set_threads): threads per workgroup, 0 = the library's choice."""
         _native.check(_native.lib.ctcd_set_threads(self._handle, int(n)))
+
+    def last_layout(self):
+        """As CTCBeamDecoder.last_layout (the last chunk's launch)."""
+        return int(_native.lib.ctcd_debug_last_layout(self._handle))
 
     def set_scorer_wait(self, on=True):
         """As CTCBeamDecoder.set_scorer_wait."""

@@ -503,8 +503,9 @@ struct Decoder {
   // With a scorer S can shrink (candidates are cut, the beam may not fill): the keys between the next frame's S and this
   // frame's are then cleared after the frame's closing barrier (step()).
   // The pruned default's compile-time class (SMALLV == 2, at most 40 candidates per frame): the rank table's entries carry the frame they
-  // were written in -- (t mod 1024) << 6 | rank, 0xFFFF = never -- so that a frame's candidates need not be taken out of the table again
-  // behind the emission (a barrier and a loop per frame); the table is wiped every 1024 frames, when the tags would repeat.
+  // were written in -- (t mod 1024) << 6 | rank, 0xFFFF = never (the tag of frame 1023 with rank 63, which no candidate has: rank_of_char) --
+  // so that a frame's candidates need not be taken out of the table again behind the emission (a barrier and a loop per frame); the table
+  // is wiped every 1024 frames, when the tags would repeat (both branches of decode_utterance's frame loop), and by load_state.
   static constexpr bool kRankEpoch = SMALLV == 2 && !IDENT && X::kRankEpoch;
   CTC_HD static int16_t rank_tag(int t, int r) { return (int16_t)(uint16_t)((((uint32_t)t & 1023u) << 6) | (uint32_t)r); }
   static constexpr bool kTailZero = IDENT && SMALLV && !LAZY && X::kZeroKeyTail;
@@ -995,8 +996,11 @@ struct Decoder {
     if (c < 0) return -1;
     if (IDENT) return c < in.Vc ? c : -1;
     if (kRankEpoch) {
+      // (a never-written or wiped entry, 0xFFFF, carries the tag of frame 1023 mod 1024 with rank 63: a written entry's rank is below
+      //  this frame's candidate count, at most kMidVc = 40 -- the one compare against in.Vc turns both away)
       const uint32_t v = (uint16_t)w.rank_of[c];
-      return (v >> 6) == ((uint32_t)in.t & 1023u) ? (int)(v & 63u) : -1;
+      const int r = (int)(v & 63u);
+      return (v >> 6) == ((uint32_t)in.t & 1023u) && r < in.Vc ? r : -1;
     }
     return w.rank_of[c];
   }
@@ -2875,6 +2879,10 @@ CTC_HD int decode_utterance(X &x, Work &w, const Dims &d, int blank, const float
         }
       } else {
         in.Vc = x.uni(pr->cnt[t]);
+        if (Dec0::kRankEpoch && CTC_RARE((in.t & 1023) == 0 && t > 0)) {  // (as above: the tags written 1024 frames ago would match again)
+          for (int c = tid; c < d.V; c += nt) w.rank_of[c] = -1;
+          x.sync();
+        }
         for (int r = tid; r < in.Vc; r += nt) {
           const int c = pr->ch[(size_t)t * width + r];
           const float v = pr->lp[(size_t)t * width + r];

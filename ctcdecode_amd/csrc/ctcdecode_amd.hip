@@ -1872,6 +1872,7 @@ struct ctcd_decoder {
   int subtree_mode = -1;
   bool subtree_on = false;       // the automatic choice for the next launch
   int last_subtree_search = 0;   // what the last launch used
+  int last_layout = -1;          // the workspace layout the last launch used (ctcd_debug_last_layout; -1: none yet)
   int last_cb_rounds = 0;        // scorer hook: launches the last decode through a callback scorer took (ctcd_last_scorer_rounds)
   hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr, ev3 = nullptr;  // decode kernel | vocabulary-prune pass
   bool prune_timed = false;
@@ -2149,6 +2150,7 @@ int ctcd_set_subtree_search(ctcd_decoder *d, int mode) {
   return CTCD_OK;
 }
 int ctcd_last_subtree_search(const ctcd_decoder *d) { return d ? d->last_subtree_search : -1; }
+int ctcd_debug_last_layout(const ctcd_decoder *d) { return d ? d->last_layout : -1; }
 
 int ctcd_set_input_dtype(ctcd_decoder *d, int dtype) {
   if (!d || (dtype != CTCD_DTYPE_F32 && dtype != CTCD_DTYPE_F16 && dtype != CTCD_DTYPE_BF16))
@@ -2695,6 +2697,9 @@ static int decode_common(ctcd_decoder *d, const float *probs, const int32_t *seq
     else return fail(CTCD_EUNSUPPORTED, "this experiment build has no kernels that take streamed input");
 #endif
   }
+  // the workspace layout of the kernel chosen above (include/ctcdecode_amd.h ctcd_debug_last_layout), in the order the selection
+  // lets one override another: the HBM-scratch levels over everything but LAYOUT 3, LAYOUT 2 over LAYOUT 1 (they exclude each other)
+  d->last_layout = wide3 ? 3 : big ? 3 + far_level : fixed2 ? 2 : fixed ? 1 : 0;
   // (CTCD_LDS_FLOOR: experiments with the occupancy the LDS request allows)
   if (d->lds_floor >= 0) lds = std::max(lds, std::min((size_t)d->lds_floor, (size_t)d->max_lds - 2048));
   HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));

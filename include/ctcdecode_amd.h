@@ -314,6 +314,12 @@ int ctcd_set_cu_sharing(ctcd_decoder *dec, int mode);
  * builds.  ctcd_last_subtree_search: which build the last launch used (0 / 1). */
 int ctcd_set_subtree_search(ctcd_decoder *dec, int mode);
 int ctcd_last_subtree_search(const ctcd_decoder *dec);
+/* The workspace layout of the kernel the last decode launch used (tests prove with it which kernel ran): 0 = the run-time layout;
+ * 1 = the fixed layout (beam <= 128, <= 32 labels); 2 = the pruned default's compile-time layout (beam <= 112, <= 40 candidates of
+ * <= 10240 labels, 1024 threads, no scorer: its rank table is tagged with the frame mod 1024); 3 = the first wide-beam layout at its
+ * compile-time size (beam <= 500, <= 29 labels, no pruning); 4 / 5 / 6 = the run-time layout with HBM scratch at level 1 / 2 / 3
+ * (wide beams; level 3: more than 65535 candidate slots).  -1: no launch yet. */
+int ctcd_debug_last_layout(const ctcd_decoder *dec);
 int ctcd_workgroup_lds_bytes(int beam, int V, int cutoff_top_n, double cutoff_prob); /* LDS one utterance needs (default build) */
 const char *ctcd_last_error(void);
 const char *ctcd_version(void);

@@ -636,6 +636,48 @@ extern "C" int ctccore_decode_chunked_f32(const float *probs, int B, int T, int 
   return 1;
 }
 
+// The same with vocabulary pruning (the reference's default decoder): every chunk hands the core the pruned rows of its own frames,
+// and the stream state carries the beam across.  The instantiation is decode_impl's for these shapes -- the pruned default's
+// compile-time class (beam_core.h SMALLV == 2, whose rank table load_state wipes at every chunk start) unless CTC_HOST_NO_CLASS2
+// is set or the shape is outside it, then the run-time layout.
+extern "C" int ctccore_decode_chunked_pruned_f32(const float *probs, int B, int T, int V, int beam, double cutoff_prob, int cutoff_top_n,
+                                                 int blank_id, const int32_t *bounds, int nchunks, int32_t *out_tokens,
+                                                 int32_t *out_timesteps, float *out_scores, int32_t *out_lens, int32_t *n_results) {
+  using namespace ctcbeam;
+  Dims d;
+  d.K = beam; d.V = V; d.Vc_max = std::min(V, cutoff_top_n); d.use_rank_table = 1; d.lm = 0;
+  const bool class2 = !(beam <= 128 && V <= 32) && beam <= kMidK && d.Vc_max <= kMidVc && V <= kMidV && !getenv("CTC_HOST_NO_CLASS2");
+  Work w;
+  size_t far_bytes = 0;
+  std::vector<char> mem(carve<0>(w, nullptr, nullptr, d, &far_bytes) + 64);
+  std::vector<char> far(far_bytes + 64);
+  std::vector<int> pcnt(T), pch((size_t)T * d.Vc_max);
+  std::vector<float> plp((size_t)T * d.Vc_max);
+  for (int b = 0; b < B; ++b) {
+    std::vector<PoolNode> pool((size_t)1 + (size_t)beam * T);
+    std::vector<int> pool_up(2 * pool.size());
+    std::vector<int> hdr(SH_WORDS, 0), arrays((size_t)kStateArrays * beam, 0);
+    for (int t = 0; t < T; ++t)
+      prune_row(probs + ((size_t)b * T + t) * V, V, cutoff_prob, cutoff_top_n, &pcnt[t], &pch[(size_t)t * d.Vc_max], &plp[(size_t)t * d.Vc_max]);
+    for (int c = 0; c < nchunks; ++c) {
+      const int lo = bounds[c], hi = bounds[c + 1];
+      std::fill(mem.begin(), mem.end(), (char)0x5a);  // a fresh workspace every chunk, as a new kernel launch would have
+      std::fill(far.begin(), far.end(), (char)0x5a);
+      carve<0>(w, mem.data(), far.data(), d, nullptr);
+      HostX x;
+      StreamState ss{hdr.data(), arrays.data(), c == nchunks - 1 ? 1 : 0};
+      const OutRefs outs{out_tokens, out_timesteps, out_scores, out_lens, n_results, beam, T, nullptr, nullptr, nullptr, nullptr, 0u, nullptr, nullptr, nullptr, nullptr, 0u};
+      const PrunedRows pr{pcnt.data() + lo, pch.data() + (size_t)lo * d.Vc_max, plp.data() + (size_t)lo * d.Vc_max, d.Vc_max};
+      const int st = class2 ? decode_utterance<false, 2>(x, w, d, blank_id, (const float *)nullptr, &pr, hi - lo, pool.data(), pool_up.data(), (int)pool.size(),
+                                                         ctcmath::host_tables().w, &outs, b, &ss)
+                            : decode_utterance<false>(x, w, d, blank_id, (const float *)nullptr, &pr, hi - lo, pool.data(), pool_up.data(), (int)pool.size(),
+                                                      ctcmath::host_tables().w, &outs, b, &ss);
+      if (st != ST_OK) return -st;
+    }
+  }
+  return 1;
+}
+
 // Small helpers of beam_core.h checked exhaustively / on random patterns (tests/test_core_host.py).  Returns the
 // number of violations found.
 extern "C" long long ctccore_check_helpers(unsigned long long seed, long long n_random) {

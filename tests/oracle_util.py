@@ -305,3 +305,24 @@ def decode_core_host_chunked(probs, bounds, beam=100, blank_id=0):
     if rc != 1:
         raise RuntimeError("core returned %d" % rc)
     return dict(tokens=tok, timesteps=ts, scores=sc, lens=ln, nres=nres)
+
+
+def decode_core_host_chunked_pruned(probs, bounds, beam=100, cutoff_prob=1.0, cutoff_top_n=40, blank_id=0):
+    """decode_core_host_chunked with vocabulary pruning: the class of the pruned default (or, with CTC_HOST_NO_CLASS2=1, the run-time
+    layout) fed chunk by chunk."""
+    probs = np.ascontiguousarray(probs, dtype=np.float32)
+    B, T, V = probs.shape
+    bounds = np.ascontiguousarray([0] + [int(x) for x in bounds] + [T], dtype=np.int32)
+    tok = np.zeros((B, beam, T), np.int32)
+    ts = np.zeros((B, beam, T), np.int32)
+    sc = np.zeros((B, beam), np.float32)
+    ln = np.zeros((B, beam), np.int32)
+    nres = np.zeros((B,), np.int32)
+    lib = ctypes.CDLL(build_core_host())
+    fn = lib.ctccore_decode_chunked_pruned_f32
+    fn.argtypes = [_f32p] + [ctypes.c_int] * 4 + [ctypes.c_double, ctypes.c_int, ctypes.c_int, _i32p, ctypes.c_int, _i32p, _i32p, _f32p, _i32p, _i32p]
+    rc = fn(_ptr(probs, _f32p), B, T, V, beam, cutoff_prob, cutoff_top_n, blank_id, _ptr(bounds, _i32p), len(bounds) - 1,
+            _ptr(tok, _i32p), _ptr(ts, _i32p), _ptr(sc, _f32p), _ptr(ln, _i32p), _ptr(nres, _i32p))
+    if rc != 1:
+        raise RuntimeError("core returned %d" % rc)
+    return dict(tokens=tok, timesteps=ts, scores=sc, lens=ln, nres=nres)

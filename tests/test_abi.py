@@ -24,6 +24,11 @@ def test_library_exports_every_declared_symbol():
     lib = ctypes.CDLL(_build.LIB_PATH)
     names = _declared()
     assert "ctcd_beam_decode" in names and "ctcd_beam_decode_host" in names and len(names) >= 9
+    # the hook the GPU tests prove with which workspace layout (which kernel) a decode ran
+    assert "ctcd_debug_last_layout" in names
+    from ctcdecode_amd import _native
+
+    assert set(names) <= set(_native.SYMBOLS), sorted(set(names) - set(_native.SYMBOLS))
     for name in names:
         assert hasattr(lib, name), name
     lib.ctcd_version.restype = ctypes.c_char_p

@@ -8,6 +8,7 @@ import pytest
 import degenerate_util as du
 import golden_util as gu
 import oracle_util as ou
+import rank_epoch_util as reu
 
 
 @pytest.mark.parametrize("name", [n for n in gu.names() if "prob" not in n])
@@ -152,6 +153,69 @@ def test_core_rank_table_tags_wrap():
         want = ou.decode(lp, beam=K, cutoff_top_n=top_n)
         got = ou.decode_core_host(lp, None, beam=K, cutoff_top_n=top_n)
         ou.assert_same(got, want, "rank-table tags V=%d T=%d" % (V, T))
+
+
+# ---- the rank table of the pruned default's compile-time class across frame 1023 mod 1024 (beam_core.h kRankEpoch; the inputs:
+# rank_epoch_util.py).  The shapes are the class's (decode_impl of tests/native/core_host.cpp runs decode_utterance<false, 2> for them);
+# CTC_HOST_NO_CLASS2=1 runs the run-time layout instead, which takes every frame's candidates out of its table.
+
+
+def _class2_and_runtime_layout_match_oracle(monkeypatch, lp, what, beam=reu.K, cutoff_top_n=reu.TOP_N, **kw):
+    kw.update(beam=beam, cutoff_top_n=cutoff_top_n)
+    want = ou.decode(lp, **kw)
+    ou.assert_same(ou.decode_core_host(lp, **kw), want, what + " (class 2)")
+    with monkeypatch.context() as m:
+        m.setenv("CTC_HOST_NO_CLASS2", "1")
+        ou.assert_same(ou.decode_core_host(lp, **kw), want, what + " (run-time layout)")
+    return want
+
+
+def test_core_rank_epoch_unwritten_entry_is_not_rank_63(monkeypatch):
+    """Regression: the blank is never a candidate and at frame 1023 drops below nineteen labels at -3.0 -- its never-written entry
+    (0xFFFF) read as frame 1023's rank 63 (a log-probability past the 20 candidates, one non-blank candidate too few)."""
+    lp = reu.prune_blank(ou.synth_logprobs(2, 1100, reu.V, 501), reu.TOP_N)
+    lp[:, 1023, :20] = -3.0
+    lp[:, 1023, 0] = -3.5
+    _class2_and_runtime_layout_match_oracle(monkeypatch, lp, "seed 501, T=1100")
+
+
+@pytest.mark.parametrize("T", [1023, 1024, 1025, 2047, 2048, 2049, 3100])
+@pytest.mark.parametrize("kind", reu.KINDS)
+def test_core_rank_epoch_wraps(monkeypatch, kind, T):
+    _class2_and_runtime_layout_match_oracle(monkeypatch, reu.epoch_case(kind, T), "%s T=%d" % (kind, T))
+
+
+def test_core_rank_epoch_randomized():
+    """Bounded sweep over the class (beam <= 112, cutoff_top_n <= 40, V up to 1000) past frame 1023, the blank biased out of the
+    candidates in many frames."""
+    rng = np.random.default_rng(2024)
+    for it in range(8):
+        V = int(rng.choice([64, 300, 1000]))
+        K = int(rng.choice([8, 30, 64, 112]))
+        top_n = int(rng.choice([5, 20, 40]))
+        T = int(rng.integers(1000, 2201))
+        lp = ou.synth_logprobs(1, T, V, 9100 + it, blank_bias=float(rng.choice([-2.0, -3.0, -5.0])))
+        if it % 2:
+            reu.strong_wrap_frames(lp, top_n, it)
+        kw = dict(beam=K, cutoff_top_n=top_n)
+        ou.assert_same(ou.decode_core_host(lp, **kw), ou.decode(lp, **kw), "case %d V=%d K=%d top_n=%d T=%d" % (it, V, K, top_n, T))
+
+
+@pytest.mark.parametrize("kind,K,top_n", [("blank_pruned_at_wraps", 100, 40), ("stale_tag", reu.K, reu.TOP_N)])
+def test_core_rank_epoch_streamed(monkeypatch, kind, K, top_n):
+    """Pruned streams of the class: load_state wipes the rank table at every chunk start, so a chunk that starts at frame 1023 or 2047
+    looks up every label that is not one of its first frame's candidates in a wiped table; one-frame chunks across the wraps.  Every
+    chunking equals the one-shot oracle, in the class and in the run-time layout."""
+    T = 2100
+    lp = reu.epoch_case(kind, T, top_n=top_n)
+    kw = dict(beam=K, cutoff_top_n=top_n)
+    want = ou.decode(lp, **kw)
+    chunkings = [[1023], [1024], [2047], [1023, 2047], list(range(1020, 1028)) + list(range(2044, 2052)), [500, 1023, 1024, 1025, 2047, 2048]]
+    for bounds in chunkings:
+        ou.assert_same(ou.decode_core_host_chunked_pruned(lp, bounds, **kw), want, "%s chunks %s" % (kind, bounds))
+    with monkeypatch.context() as m:
+        m.setenv("CTC_HOST_NO_CLASS2", "1")
+        ou.assert_same(ou.decode_core_host_chunked_pruned(lp, chunkings[-1], **kw), want, "%s run-time layout, chunks %s" % (kind, chunkings[-1]))
 
 
 def test_core_streaming_equals_one_shot():

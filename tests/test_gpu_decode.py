@@ -35,7 +35,7 @@ def _decode(torch, probs, seq_lens=None, beam=100, cutoff_prob=1.0, cutoff_top_n
                                      torch.from_numpy(seq_lens) if seq_lens is not None else None)
     except NotImplementedError as e:
         pytest.skip(str(e))
-    return dict(tokens=out.numpy(), timesteps=ts.numpy(), scores=sc.numpy(), lens=ln.numpy())
+    return dict(tokens=out.numpy(), timesteps=ts.numpy(), scores=sc.numpy(), lens=ln.numpy(), layout=dec.last_layout())
 
 
 def _with_nres(got, want):
@@ -247,24 +247,30 @@ def test_wide_beam_hbm_scratch_layout(torch_mod):
 def test_rank_table_tags_wrap_offline_and_streamed(torch_mod):
     """Round 6: kernel <0,0,2,true,1024> tags its rank-table entries with the frame (mod 1024) and wipes the table when the tags repeat.
     Utterances longer than 1024 frames -- in one launch, and as streams whose chunks end before, at and behind the wrap -- equal the
-    oracle and the run-time layout's kernel (which takes the candidates out of the table every frame)."""
+    oracle and the run-time layout's kernel (which takes the candidates out of the table every frame).  K * (top_n + 2) = 660 slots:
+    the automatic choice would give this shape 512 threads and the run-time layout, so both decoders ask for 1024 (the layout's only
+    workgroup size), and the layout hook proves which kernel ran."""
     import ctcdecode_amd
 
     torch = torch_mod
     V, top_n, K, T = 300, 20, 30, 1150
     lp = ou.synth_logprobs(2, T, V, 4411)
     want = ou.decode(lp, beam=K, cutoff_top_n=top_n)
-    got = _decode(torch, lp, beam=K, cutoff_top_n=top_n)
+    got = _decode(torch, lp, beam=K, cutoff_top_n=top_n, threads=1024)
+    assert got["layout"] == 2
     ou.assert_same(_with_nres(got, want), want, "rank-table tags, one launch")
     rt = _decode(torch, lp, beam=K, cutoff_top_n=top_n, fixed_layout=False)
+    assert rt["layout"] == 0
     for key in ("tokens", "timesteps", "lens"):
         assert np.array_equal(got[key], rt[key]), key
     dec = ctcdecode_amd.OnlineCTCBeamDecoder([str(i) for i in range(V)], cutoff_top_n=top_n, beam_width=K, log_probs_input=True, device="cuda:0")
+    dec.set_threads(1024)
     states = [ctcdecode_amd.DecoderState(dec) for _ in range(2)]
     x = torch.from_numpy(lp)
     bounds = [0, 400, 1023, 1024, 1025, T]
     for a, b in zip(bounds[:-1], bounds[1:]):
         out, sc, ts, ln = dec.decode(x[:, a:b], states, [b == T] * 2)
+        assert dec.last_layout() == 2, (a, b)
     L = out.shape[2]
     chunked = dict(tokens=np.zeros((2, K, T), np.int32), timesteps=np.zeros((2, K, T), np.int32), scores=sc.numpy(), lens=ln.numpy(), nres=want["nres"])
     chunked["tokens"][:, : out.shape[1], :L] = out.numpy()
