@@ -106,9 +106,73 @@ class CallbackScorer(object):
         self.num_labels = len(labels)
         return self
 
+    @classmethod
+    def batched(cls, fn, vocabulary, max_order, labels, alpha=0.0, beta=0.0, device=None):
+        """The hook with a BATCHED Python callback (``ctcd_scorer_create_callback_batch``): ``fn(windows)`` receives a list of
+        windows -- each a tuple of ``max_order`` words, oldest first, ``"<s>"``-padded, as ``cond_log10`` receives one -- and returns a
+        sequence of as many answers, each log10 p(window[-1] | window[:-1]) or ``None`` (out of vocabulary).  Same contract as the
+        per-window form: a pure function of the words, every distinct window is asked once, an exception inside it (or an answer of
+        the wrong length) fails the decode and is re-raised from it.  One call asks up to 512 windows: the interpreter is entered
+        once per batch instead of once per window."""
+        self = cls.__new__(cls)
+        self._fn, self._error, self._keepalive = fn, None, None
+        self._c_fn = self._batch_trampoline()  # kept alive with the scorer
+        self._create_batch(vocabulary, max_order, labels, alpha, beta, device, None)
+        return self
+
+    def _batch_trampoline(self):
+        def trampoline(_user, words, n, order, probs, status):
+            try:
+                flat = [w.decode("utf-8") for w in words[: n * order]]
+                r = list(self._fn([tuple(flat[i * order:(i + 1) * order]) for i in range(n)]))
+                if len(r) != n:
+                    raise ValueError("the batched scorer callback returned %d answers for %d windows" % (len(r), n))
+                for i, v in enumerate(r):
+                    if v is None:
+                        status[i] = 1
+                    else:
+                        probs[i] = float(v)
+                        status[i] = 0
+                return 0
+            except BaseException as e:  # (an exception must not unwind through the C frames)
+                self._error = e
+                return -1
+
+        return _native.COND_LOG10_BATCH_FN(trampoline)
+
+    @classmethod
+    def from_c_batch(cls, fn_address, user_address, vocabulary, max_order, labels, alpha=0.0, beta=0.0, device=None, keepalive=None):
+        """``from_c`` for a NATIVE batched callback of type ``ctcd_cond_log10_batch_fn`` (include/ctcdecode_amd.h:
+        ``int fn(void *user, const char *const *words, int n_windows, int order, float *log10_probs, int32_t *status)``).
+        ``ctcd_scorer_cond_log10_batch`` has this very signature: any built-in scorer can sit behind the batched hook."""
+        self = cls.__new__(cls)
+        self._fn, self._error, self._keepalive = None, None, keepalive
+        self._c_fn = ctypes.cast(ctypes.c_void_p(int(fn_address)), _native.COND_LOG10_BATCH_FN)
+        self._create_batch(vocabulary, max_order, labels, alpha, beta, device, ctypes.c_void_p(int(user_address)) if user_address else None)
+        return self
+
+    def _create_batch(self, vocabulary, max_order, labels, alpha, beta, device, user):
+        if not torch.cuda.is_available():
+            raise RuntimeError("ctcdecode_amd: no HIP device visible; this decoder has no CPU path")
+        dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        index = dev.index if dev.index is not None else torch.cuda.current_device()
+        voc = [str(w).encode("utf-8") for w in vocabulary]
+        varr = (ctypes.c_char_p * max(len(voc), 1))(*voc)
+        larr = (ctypes.c_char_p * len(labels))(*[str(x).encode("utf-8") for x in labels])
+        h = ctypes.c_void_p()
+        _native.check(_native.lib.ctcd_scorer_create_callback_batch(ctypes.byref(h), float(alpha), float(beta), int(max_order), varr, len(voc), self._c_fn,
+                                                                    user, larr, len(labels), int(index)))
+        self.handle = h
+        self.device_index = int(index)
+        self.num_labels = len(labels)
+
     def callback_calls(self):
         """Distinct windows the callback has been asked for so far."""
         return int(_native.lib.ctcd_scorer_callback_calls(self.handle))
+
+    def callback_batches(self):
+        """Calls of a batched callback so far (``batched`` / ``from_c_batch``; 0 for the per-window form)."""
+        return int(_native.lib.ctcd_scorer_callback_batches(self.handle))
 
     def callback_seconds(self):
         """Time spent inside the callback so far (an estimate: every 16th call is timed)."""
@@ -117,7 +181,7 @@ class CallbackScorer(object):
     def set_callback_threads(self, threads):
         """A NATIVE callback that may be called from several threads at once (``from_c`` over a read-only model): ``threads - 1``
         helper threads ask beside the calling one while a launch waits for its answers (``ctcd_scorer_set_callback_threads``).
-        Refused for Python callables: the interpreter lock would serialise them."""
+        Refused for Python callables: the interpreter lock would serialise them; a batched callback takes no helper threads either."""
         if self._fn is not None and int(threads) != 1:
             raise ValueError("callback threads are for native callbacks (CallbackScorer.from_c): a Python callable runs under the interpreter lock")
         _native.check(_native.lib.ctcd_scorer_set_callback_threads(self.handle, int(threads)))
@@ -140,27 +204,31 @@ class CallbackScorer(object):
 class KenlmScorer(CallbackScorer):
     """A kenlm model -- binary files included -- behind the scorer hook, through the ``kenlm`` Python module (not part of
     this image: ImportError if it is missing).  ``vocabulary``: the model's words (a binary model does not list them; pass
-    the word list it was trained with, as the reference's Scorer reads them from the model, scorer.cpp:196-230)."""
+    the word list it was trained with, as the reference's Scorer reads them from the model, scorer.cpp:196-230).  The model is
+    asked through the batched hook (``CallbackScorer.batched``): one call per batch of windows, each window scored as before."""
 
     def __init__(self, model_path, vocabulary, labels, alpha=0.0, beta=0.0, device=None):
         import kenlm  # noqa: F401  (optional dependency)
 
         self._model = kenlm.Model(str(model_path))
         model = self._model
+        self._fn, self._error, self._keepalive = (lambda windows: [KenlmScorer.cond_log10(kenlm, model, w) for w in windows]), None, None
+        self._c_fn = self._batch_trampoline()
+        self._create_batch(vocabulary, model.order, labels, alpha, beta, device, None)
 
-        def cond_log10(words):
-            # Scorer::get_log_cond_prob (scorer.cpp:74-93): feed the window from the empty context, OOV if any word is unknown
-            state, out = kenlm.State(), kenlm.State()
-            model.NullContextWrite(state)
-            p = 0.0
-            for w in words:
-                if w not in model:
-                    return None
-                p = model.BaseScore(state, w, out)
-                state, out = out, state
-            return p
-
-        CallbackScorer.__init__(self, cond_log10, vocabulary, model.order, labels, alpha, beta, device)
+    @staticmethod
+    def cond_log10(kenlm, model, words):
+        """One window through a kenlm ``model`` (``kenlm``: the module): Scorer::get_log_cond_prob (scorer.cpp:74-93) -- the window
+        is fed from the empty context, None (out of vocabulary) if any word is unknown, else the last word's BaseScore."""
+        state, out = kenlm.State(), kenlm.State()
+        model.NullContextWrite(state)
+        p = 0.0
+        for w in words:
+            if w not in model:
+                return None
+            p = model.BaseScore(state, w, out)
+            state, out = out, state
+        return p
 
 
 # include/ctcdecode_amd.h CTCD_DTYPE_*: device tensors of these dtypes go to the library as they are (its kernels widen them)
@@ -196,6 +264,12 @@ def _to_host(tensors):
         outs.append(h)
     torch.cuda.current_stream(tensors[0].device).synchronize()
     return tuple(outs)
+
+
+def _last_scorer_pairs(handle):
+    q, d, r = ctypes.c_longlong(), ctypes.c_longlong(), ctypes.c_longlong()
+    _native.check(_native.lib.ctcd_last_scorer_pairs(handle, ctypes.byref(q), ctypes.byref(d), ctypes.byref(r)))
+    return int(q.value), int(d.value), int(r.value)
 
 
 def _adopt_scorer(scorer, model_path, num_labels, device_index):
@@ -292,6 +366,16 @@ class CTCBeamDecoder(object):
     def last_scorer_launches(self):
         """(launches, answer batches handed to waiting launches) of the last decode with a callback scorer."""
         return int(_native.lib.ctcd_last_scorer_rounds(self._handle)), int(_native.lib.ctcd_last_scorer_waits(self._handle))
+
+    def set_scorer_filter(self, on=True):
+        """Callback scorers: True (default) = the kernels drop a parked utterance's repeated misses on one (history, word) pair;
+        False = every miss is queued (measurements and tests: identical results, more queued pairs)."""
+        _native.check(_native.lib.ctcd_set_scorer_filter(self._handle, 1 if on else 0))
+
+    def last_scorer_pairs(self):
+        """(queued pairs, windows asked, repeats by the same item) of the last decode with a callback scorer
+        (include/ctcdecode_amd.h ctcd_last_scorer_pairs)."""
+        return _last_scorer_pairs(self._handle)
 
     def set_fused_logits(self, on=True):
         """Test hook (logits_input=True): False sends raw logits through the one-wave log_softmax pass and the separate prune
@@ -692,6 +776,14 @@ class OnlineCTCBeamDecoder(object):
     def set_scorer_wait(self, on=True):
         """As CTCBeamDecoder.set_scorer_wait."""
         _native.check(_native.lib.ctcd_set_scorer_wait(self._handle, 1 if on else 0))
+
+    def set_scorer_filter(self, on=True):
+        """As CTCBeamDecoder.set_scorer_filter."""
+        _native.check(_native.lib.ctcd_set_scorer_filter(self._handle, 1 if on else 0))
+
+    def last_scorer_pairs(self):
+        """As CTCBeamDecoder.last_scorer_pairs."""
+        return _last_scorer_pairs(self._handle)
 
     def decode(self, probs, states, is_eos_s, seq_lens=None, check=True):
         """Same contract as ctcdecode/__init__.py:189-238: returns CPU tensors (beam_results[B, R, L], beam_scores[B, K],

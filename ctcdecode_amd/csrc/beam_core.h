@@ -644,9 +644,43 @@ struct Decoder {
   // when the frame commits (st_par flips).
   CTC_HD int *fin_cur() const { return w.fin + (lm_cb ? st_par * d.K : 0); }
   CTC_HD int *fin_nxt() const { return w.fin + (lm_cb ? (st_par ^ 1) * d.K : 0); }
+  // Behind the scorer hook a parked utterance queues each (state, word) pair once: the prefixes of one frame that share a word
+  // history and complete the same word -- and the same prefix asked again by finish() -- miss on the same pair.
+  // A direct-mapped filter of pair fingerprints in LDS (1 KB, one per workgroup; a thread-local array in the host build) remembers
+  // the pairs queued since the utterance was last taken up: init() and load_state() clear it, and every resumption after a wait
+  // goes through one of them.  It needs no atomics: two lanes that miss on one pair at once may both queue it (a repeat, as
+  // without the filter), and a pair whose slot another pair took is queued again.  A pair dropped by a fingerprint collision
+  // (~2^-31 per lookup of an occupied entry) costs one more re-run of the frame, never a wait: VAR_LMQ counts the pairs actually queued,
+  // the utterance misses on the pair again after it is taken up, and the filter is empty then.  LmView::cb == 2 turns it off.
+  static constexpr int kLmqFilter = 256;
+  CTC_HD static uint32_t *lmq_filter() {
+#if defined(__HIP_DEVICE_COMPILE__)
+    __shared__ uint32_t f[kLmqFilter];
+#else
+    static thread_local uint32_t f[kLmqFilter];
+#endif
+    return f;
+  }
+  CTC_HD void lmq_filter_clear() {
+    if constexpr (lm_cb)
+      for (int i = x.tid(); i < kLmqFilter; i += x.nt()) lmq_filter()[i] = 0u;
+  }
+  // true: queue the pair (first miss on it since the utterance was taken up, or the filter is off)
+  CTC_HD bool lmq_first(uint32_t state, uint32_t word) const {
+    if constexpr (lm_cb) {
+      if (lm->cb != 1) return true;
+      const uint32_t h = ctclm::ng_hash(state, word);
+      const uint32_t fp = ((state * 0x85EBCA77u) ^ (word * 0xC2B2AE3Du) ^ (h >> 8)) | 1u;  // (0: an empty entry)
+      uint32_t *e = lmq_filter() + (h & (kLmqFilter - 1));
+      if (*e == fp) return false;
+      *e = fp;
+    }
+    return true;
+  }
   // get_log_cond_prob through the tables.  With a callback scorer a value that is not cached yet comes back as NaN: the pair
-  // is queued for the host, the frame is marked (it will not be committed: step() / finish() return ST_NEED_HOST) and the
-  // caller's state is left where it was; a cached "out of vocabulary" answer (-inf) becomes the reference's OOV_SCORE.
+  // is queued for the host (unless this utterance has queued it already: lmq_first), the frame is marked (it will not be
+  // committed: step() / finish() return ST_NEED_HOST) and the caller's state is left where it was; a cached "out of vocabulary"
+  // answer (-inf) becomes the reference's OOV_SCORE.
   CTC_HD double lm_cond_(uint32_t *st, int *cl, uint32_t word, bool *missed = nullptr) const {
     const uint32_t st0 = *st;
     const int cl0 = *cl;
@@ -654,10 +688,12 @@ struct Decoder {
     if (CTC_RARE(lm_cb)) {
       if (v != v) {
         w.vars[VAR_LMMISS] = 1;
-        unsigned i = x.global_add(lm->cb_count, 1u);
-        if (lm->cb_ring) i &= lm->cb_cap - 1;  // (a launch that waits for its answers: the host empties the list while it fills)
-        if (i < lm->cb_cap) lm->cb_miss[i] = ctclm::MissEntry{st0, word, (uint32_t)x.item(), 1u};
-        x.atomic_add(&w.vars[VAR_LMQ], 1);  // (pairs this utterance has queued since it was taken up: what its workgroup waits to see answered)
+        if (lmq_first(st0, word)) {
+          unsigned i = x.global_add(lm->cb_count, 1u);
+          if (lm->cb_ring) i &= lm->cb_cap - 1;  // (a launch that waits for its answers: the host empties the list while it fills)
+          if (i < lm->cb_cap) lm->cb_miss[i] = ctclm::MissEntry{st0, word, (uint32_t)x.item(), 1u};
+          x.atomic_add(&w.vars[VAR_LMQ], 1);  // (pairs this utterance has queued since it was taken up: what its workgroup waits to see answered)
+        }
         *st = st0; *cl = cl0;
         if (missed) *missed = true;
         return 0.0;
@@ -896,6 +932,7 @@ struct Decoder {
     st_maxkey = ord_f32(0.f);
     st_minkey = ord_f32(0.f);
     for (int i = x.tid(); i < kBins + kBins / 16; i += x.nt()) w.bins[i] = 0;
+    lmq_filter_clear();
     for (int i = x.tid(); i < 2 * d.K; i += x.nt()) w.hit[i] = 0;
     for (int i = x.tid(); i < 2 * d.K; i += x.nt()) { w.ancbuf[i] = -1; w.acntbuf[i] = 0; }
     if (d.use_rank_table)
@@ -941,6 +978,7 @@ struct Decoder {
       w.vars[VAR_LMQ] = 0;
     }
     for (int i = tid; i < kBins + kBins / 16; i += nt) w.bins[i] = 0;
+    lmq_filter_clear();
     for (int i = tid; i < 2 * K; i += nt) { w.hit[i] = 0; w.ancbuf[i] = -1; w.acntbuf[i] = 0; }
     if (d.use_rank_table)
       for (int c = tid; c < d.V; c += nt) w.rank_of[c] = -1;

@@ -1268,6 +1268,8 @@ struct ctcd_decoder {
   bool no_prune_reg = false;     // debugging / tests: the two-sweep form of the workgroup prune kernel
   bool no_hook_wait = false;     // tests: a callback scorer's launches end at a miss (the form of rounds 4-5) instead of waiting for the answer
   int last_cb_waits = 0;         // answer batches the last call's launches were handed while they waited
+  bool no_lmq_filter = false;    // tests / measurements: a callback scorer's kernels queue every miss (ctcd_set_scorer_filter; LmView::cb = 2)
+  long long last_pairs[3] = {0, 0, 0};  // scorer hook, the last decode: queued pairs | windows asked | repeats of the same item (ctcd_last_scorer_pairs)
   bool no_fused_logits = false;  // tests: raw logits always through the one-wave log_softmax pass and the separate prune
   int in_dtype = CTCD_DTYPE_F32;       // ctcd_set_input_dtype: the element type of probs / logits on every entry point
   int last_in_dtype = CTCD_DTYPE_F32;  // the element type the last call's pre-passes read (ctcd_last_input_dtype)
@@ -1405,6 +1407,9 @@ struct ctcd_scorer {
   unsigned live_miss_hw = 0;                  // miss-list entries the last launch may have written (reset to the sentinel before the next)
   std::vector<uint32_t> live_stamp;           // per cache slot: the waiting launch whose log holds it
   std::vector<unsigned long long> live_memo;  // (state, word) pairs recently put into / found in that log (direct-mapped, 512 KB)
+  std::vector<uint32_t> live_memo_at;         // ... and their slots
+  std::vector<uint64_t> pair_seen;            // per cache slot: (decode << 32 | the item that queued it first in that decode): ctcd_last_scorer_pairs
+  uint32_t pair_call = 0;
   uint32_t live_launch = 0;
   CbAskPool ask_pool;                         // helper threads of a thread-safe callback (none unless asked for)
 };
@@ -2218,9 +2223,9 @@ static int cb_sync(ctcd_scorer *s, hipStream_t stream = nullptr) {
   return CTCD_OK;
 }
 
-int ctcd_scorer_create_callback(ctcd_scorer **out, double alpha, double beta, int max_order, const char *const *vocabulary, int n_vocabulary,
-                                ctcd_cond_log10_fn fn, void *user, const char *const *labels, int V, int device_id) {
-  if (!out || !fn || !labels || V <= 0 || n_vocabulary < 0 || (n_vocabulary && !vocabulary)) return fail(CTCD_EINVAL, "bad scorer arguments");
+static int create_callback_scorer(ctcd_scorer **out, double alpha, double beta, int max_order, const char *const *vocabulary, int n_vocabulary,
+                                  ctclm::CondLog10Fn fn, ctclm::CondLog10BatchFn bfn, void *user, const char *const *labels, int V, int device_id) {
+  if (!out || (!fn && !bfn) || !labels || V <= 0 || n_vocabulary < 0 || (n_vocabulary && !vocabulary)) return fail(CTCD_EINVAL, "bad scorer arguments");
   int ndev = 0;
   HIP_TRY(hipGetDeviceCount(&ndev));
   if (device_id < 0 || device_id >= ndev) return fail(CTCD_EINVAL, "no such HIP device");
@@ -2231,7 +2236,7 @@ int ctcd_scorer_create_callback(ctcd_scorer **out, double alpha, double beta, in
   s->device = device_id;
   s->cbl = new ctclm::CallbackLm;
   s->ask_pool.cl = s->cbl;
-  if (!s->cbl->build(alpha, beta, max_order, voc, lab, (ctclm::CondLog10Fn)fn, user)) {
+  if (!s->cbl->build(alpha, beta, max_order, voc, lab, fn, user, bfn)) {
     const std::string msg = s->cbl->hs.error;
     ctcd_scorer_destroy(s);
     return fail(CTCD_EINVAL, msg);
@@ -2283,6 +2288,16 @@ int ctcd_scorer_create_callback(ctcd_scorer **out, double alpha, double beta, in
   *out = s;
   return CTCD_OK;
 }
+int ctcd_scorer_create_callback(ctcd_scorer **out, double alpha, double beta, int max_order, const char *const *vocabulary, int n_vocabulary,
+                                ctcd_cond_log10_fn fn, void *user, const char *const *labels, int V, int device_id) {
+  if (!fn) return fail(CTCD_EINVAL, "bad scorer arguments");
+  return create_callback_scorer(out, alpha, beta, max_order, vocabulary, n_vocabulary, (ctclm::CondLog10Fn)fn, nullptr, user, labels, V, device_id);
+}
+int ctcd_scorer_create_callback_batch(ctcd_scorer **out, double alpha, double beta, int max_order, const char *const *vocabulary, int n_vocabulary,
+                                      ctcd_cond_log10_batch_fn fn, void *user, const char *const *labels, int V, int device_id) {
+  if (!fn) return fail(CTCD_EINVAL, "bad scorer arguments");
+  return create_callback_scorer(out, alpha, beta, max_order, vocabulary, n_vocabulary, nullptr, (ctclm::CondLog10BatchFn)fn, user, labels, V, device_id);
+}
 int ctcd_scorer_is_character_based(const ctcd_scorer *s) { return s ? (s->host.char_based ? 1 : 0) : -1; }
 int ctcd_scorer_max_order(const ctcd_scorer *s) { return s ? s->host.order : -1; }
 int ctcd_scorer_dict_size(const ctcd_scorer *s) { return s ? s->host.dict_size : -1; }
@@ -2296,7 +2311,7 @@ double ctcd_scorer_cond_log_prob(const ctcd_scorer *s, const char *const *words,
   if (!s || !words || n < 0) return 0.0;
   if (s->cbl) {  // the callback itself, with the reference's conversion (scorer.cpp:74-93)
     float p10 = 0.f;
-    const int rc = n > 0 ? s->cbl->fn(s->cbl->user, words, n, &p10) : 1;
+    const int rc = n > 0 ? s->cbl->ask_one(words, n, &p10) : 1;
     return rc == 0 ? (double)p10 / (double)0.4342944819f : ctclm::kOovScore;
   }
   std::vector<std::string> w(n);
@@ -2307,7 +2322,7 @@ double ctcd_scorer_cond_log_prob(const ctcd_scorer *s, const char *const *words,
 // conversion; returns 1 for a window with an unknown word.  Lets the built-in tables serve as a callback (tests, adapters).
 int ctcd_scorer_cond_log10(const ctcd_scorer *s, const char *const *words, int n, float *log10_prob) {
   if (!s || !words || n <= 0 || !log10_prob) return -1;
-  if (s->cbl) return s->cbl->fn(s->cbl->user, words, n, log10_prob);
+  if (s->cbl) return s->cbl->ask_one(words, n, log10_prob);
   // (HostScorer::cond_log10 without the vector of strings: this function is what bench.py puts behind the hook as a native callback)
   const ctclm::LmView v = s->host.view();
   uint32_t st = 0;
@@ -2322,15 +2337,29 @@ int ctcd_scorer_cond_log10(const ctcd_scorer *s, const char *const *words, int n
   *log10_prob = p;
   return 0;
 }
+// ... and the batched form (ctcd_cond_log10_batch_fn): window after window through ctcd_scorer_cond_log10
+int ctcd_scorer_cond_log10_batch(const ctcd_scorer *s, const char *const *words, int n_windows, int order, float *log10_probs, int32_t *status) {
+  if (!s || !words || n_windows < 0 || order <= 0 || (n_windows && (!log10_probs || !status))) return -1;
+  for (int i = 0; i < n_windows; ++i) {
+    float p = 0.f;
+    const int rc = ctcd_scorer_cond_log10(s, words + (size_t)i * order, order, &p);
+    if (rc < 0) return rc;
+    log10_probs[i] = rc == 0 ? p : 0.f;
+    status[i] = rc;
+  }
+  return 0;
+}
 int ctcd_scorer_set_callback_threads(ctcd_scorer *s, int threads) {
   if (!s || !s->cbl) return fail(CTCD_EINVAL, "not a callback scorer");
   if (threads < 1 || threads > 64) return fail(CTCD_EINVAL, "callback threads must be in [1, 64]");
+  if (s->cbl->bfn && threads != 1) return fail(CTCD_EUNSUPPORTED, "a batched callback is called from the decoding thread only (no helper threads)");
   std::lock_guard<std::mutex> lk(s->cb_mu);
   s->ask_pool.start(threads, s->cbl);
   return CTCD_OK;
 }
 long long ctcd_scorer_callback_calls(const ctcd_scorer *s) { return s && s->cbl ? (long long)s->cbl->queries : 0; }
 double ctcd_scorer_callback_seconds(const ctcd_scorer *s) { return s && s->cbl ? s->cbl->cb_seconds : 0.0; }
+long long ctcd_scorer_callback_batches(const ctcd_scorer *s) { return s && s->cbl ? (long long)s->cbl->batches : 0; }
 
 // Decoding with a callback scorer (ctcd_scorer_create_callback).  A launch decodes until an utterance asks for a (history, word)
 // pair the device cache does not hold, parks that utterance in front of the frame it was in (every utterance runs as a stream:
@@ -2369,6 +2398,21 @@ static int cb_rounds(ctcd_decoder *d, ctcd_stream **states, const unsigned char 
   const bool live = scorer->h_live && !live_off && !d->no_hook_wait && (uint32_t)B <= kCbLiveItems;
   ctclm::CallbackLm &cl = *scorer->cbl;
   d->last_cb_waits = 0;
+  // ctcd_last_scorer_pairs: every queued pair the host reads is counted; a pair counts as a repeat of the same item when the item that
+  // queued it first in this decode queues it again (per cache slot: the stamps restart when the table moves)
+  const unsigned long long asked0 = cl.queries;
+  long long n_queued = 0, n_same = 0;
+  const uint32_t call_id = ++scorer->pair_call;
+  d->last_pairs[0] = d->last_pairs[1] = d->last_pairs[2] = 0;
+  auto note_pair = [&](uint32_t at, uint32_t item) {
+    ++n_queued;
+    if (scorer->pair_seen.size() != cl.hs.ng.size()) scorer->pair_seen.assign(cl.hs.ng.size(), 0ull);
+    if (at >= scorer->pair_seen.size()) return;
+    uint64_t &e = scorer->pair_seen[at];
+    if ((uint32_t)(e >> 32) == call_id) n_same += (uint32_t)e == item;
+    else e = ((uint64_t)call_id << 32) | item;
+  };
+  const bool filter_off = d->no_lmq_filter;
   for (int round = 0;; ++round) {
     d->last_cb_rounds = round;
     if (round > 4 * T + 64) return fail(CTCD_EINTERNAL, "scorer hook: the decode does not make progress");
@@ -2391,6 +2435,7 @@ static int cb_rounds(ctcd_decoder *d, ctcd_stream **states, const unsigned char 
     if (!left) break;
     HIP_TRY(hipMemcpyAsync(d_off, done.data(), (size_t)B * 4, hipMemcpyHostToDevice, stream));
     HIP_TRY(hipMemsetAsync(scorer->cb_miss, 0, 4, stream));
+    scorer->dview.cb = filter_off ? 2 : 1;  // (beam_core.h lm_cond_: 2 = queue every miss, without the per-utterance filter)
     StreamCall sc{states, eos.data(), out_T, rem.data(), any_eos};
     sc.no_clear = round > 0;
     sc.frame_off = d_off;
@@ -2426,6 +2471,8 @@ static int cb_rounds(ctcd_decoder *d, ctcd_stream **states, const unsigned char 
       if (scorer->live_stamp.size() != cl.hs.ng.size()) scorer->live_stamp.assign(cl.hs.ng.size(), 0u);
       const uint32_t launch_id = ++scorer->live_launch;
       scorer->live_memo.assign((size_t)1 << 16, 0ull);
+      scorer->live_memo_at.assign((size_t)1 << 16, 0u);
+      if (scorer->pair_seen.size() != cl.hs.ng.size()) scorer->pair_seen.assign(cl.hs.ng.size(), 0ull);
       unsigned log_n = 0;
       bool give_up = false;
       std::vector<unsigned> ans_local((size_t)B, 0u);
@@ -2444,13 +2491,15 @@ static int cb_rounds(ctcd_decoder *d, ctcd_stream **states, const unsigned char 
           // the words of a new window are looked up and the line of its next state requested; (2) ask the callback about the new windows
           // (the scorer's helper threads take a share each when it has any); (3) in the order of the list: cache the answers, append to
           // the log, publish per item.
+          // (a batched callback: up to ctclm::kBatchWindows pairs per pass, their new windows in one call)
           enum { kMemo = 0, kHave = 1, kNew = 2, kDup = 3 };
-          constexpr int kBatch = 128;
-          struct Pend { uint32_t st, wd, item, at; size_t ring; int kind; } pend[kBatch];
-          ctclm::CallbackLm::Ask asks[kBatch];
+          constexpr int kBatch = 128, kBatchMax = ctclm::kBatchWindows > kBatch ? ctclm::kBatchWindows : kBatch;
+          const int batch = cl.bfn ? kBatchMax : kBatch;
+          struct Pend { uint32_t st, wd, item, at; size_t ring; int kind; } pend[kBatchMax];
+          ctclm::CallbackLm::Ask asks[kBatchMax];
           int np = 0, na = 0;
           const uint32_t mask = (uint32_t)cl.hs.ng.size() - 1;
-          while (np < kBatch) {
+          while (np < batch) {
             const size_t at_ring = (size_t)((seen + (unsigned)np) & (kCbMissCap - 1));
             if (h_miss[4 * at_ring + 3] == 0xFFFFFFFFu) { more = false; break; }  // (the flag word: the pair's 16 bytes arrive in one piece)
             std::atomic_thread_fence(std::memory_order_acquire);
@@ -2458,6 +2507,7 @@ static int cb_rounds(ctcd_decoder *d, ctcd_stream **states, const unsigned char 
             const uint32_t hh = ctclm::ng_hash(pend[np].st, pend[np].wd) & mask;
             __builtin_prefetch(&cl.hs.ng[hh]);
             __builtin_prefetch(&scorer->live_stamp[hh]);
+            __builtin_prefetch(&scorer->pair_seen[hh]);
             ++np;
           }
           bool bad = false;
@@ -2468,7 +2518,8 @@ static int cb_rounds(ctcd_decoder *d, ctcd_stream **states, const unsigned char 
             // and utterances want the same windows): a small direct-mapped memo of the pairs already in this launch's log answers
             // those without touching the table
             const unsigned long long key = ((unsigned long long)e.st << 32) | e.wd;
-            if (scorer->live_memo[(size_t)((key * 0x9E3779B97F4A7C15ull) >> 48)] == key) continue;  // kMemo
+            const size_t mi = (size_t)((key * 0x9E3779B97F4A7C15ull) >> 48);
+            if (scorer->live_memo[mi] == key) { e.at = scorer->live_memo_at[mi]; continue; }  // kMemo
             const long long have = cl.find_slot(e.st, e.wd);
             if (have >= 0) { e.kind = kHave; e.at = (uint32_t)have; continue; }
             e.kind = kNew;
@@ -2482,7 +2533,8 @@ static int cb_rounds(ctcd_decoder *d, ctcd_stream **states, const unsigned char 
           }
           if (!bad && na) {
             const auto t0 = std::chrono::steady_clock::now();
-            scorer->ask_pool.ask_all(asks, na);
+            if (cl.bfn) cl.ask_many(asks, na);
+            else scorer->ask_pool.ask_all(asks, na);
             cl.cb_seconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
           }
           int ia = 0;
@@ -2492,6 +2544,7 @@ static int cb_rounds(ctcd_decoder *d, ctcd_stream **states, const unsigned char 
             const size_t at_ring = e.ring;
             if (log_full && e.kind == kMemo) continue;
             const unsigned long long key = ((unsigned long long)e.st << 32) | e.wd;
+            if (e.kind == kMemo) note_pair(e.at, e.item);
             if (e.kind != kMemo) {
               uint32_t at = e.at;
               if (e.kind == kNew) {
@@ -2500,6 +2553,7 @@ static int cb_rounds(ctcd_decoder *d, ctcd_stream **states, const unsigned char 
                 at = (uint32_t)cl.find_slot(e.st, e.wd);
               }
               if (log_full) continue;  // (the answers that have been paid for are cached; their pairs stay on the list for the next launch)
+              note_pair(at, e.item);
               if (scorer->live_stamp[at] != launch_id) {
                 if (log_n >= kCbLogCap) { give_up = true; log_full = true; continue; }
                 scorer->live_stamp[at] = launch_id;
@@ -2510,7 +2564,9 @@ static int cb_rounds(ctcd_decoder *d, ctcd_stream **states, const unsigned char 
                 std::atomic_thread_fence(std::memory_order_release);
                 *h_len = log_n;  // (published entry by entry: the stores of this thread arrive in order)
               }
-              scorer->live_memo[(size_t)((key * 0x9E3779B97F4A7C15ull) >> 48)] = key;  // (in the log from here on)
+              const size_t mi = (size_t)((key * 0x9E3779B97F4A7C15ull) >> 48);
+              scorer->live_memo[mi] = key;  // (in the log from here on)
+              scorer->live_memo_at[mi] = at;
             }
             if (e.item < (uint32_t)B) {  // the item's workgroup goes on when every pair it queued has been dealt with
               std::atomic_thread_fence(std::memory_order_release);
@@ -2563,8 +2619,13 @@ static int cb_rounds(ctcd_decoder *d, ctcd_stream **states, const unsigned char 
     if (need) {
       if (nmiss == 0) return fail(CTCD_EINTERNAL, "scorer hook: an utterance waits for the host but queued nothing");
       if (live) {  // what the ring still holds (the launch has ended: every pair queued is written)
+        miss.clear();
         for (size_t i = 0; i < (size_t)kCbMissCap; ++i)
-          if (h_miss[4 * i + 3] != 0xFFFFFFFFu && !scorer->cbl->resolve(h_miss[4 * i], h_miss[4 * i + 1])) return fail(CTCD_EINVAL, scorer->cbl->hs.error);
+          if (h_miss[4 * i + 3] != 0xFFFFFFFFu) miss.insert(miss.end(), {h_miss[4 * i], h_miss[4 * i + 1], h_miss[4 * i + 2], h_miss[4 * i + 3]});
+        const size_t take = miss.size() / 4;
+        std::vector<uint32_t> at(take);
+        if (!cl.resolve_many(miss.data(), take, 4, at.data())) return fail(CTCD_EINVAL, cl.hs.error);
+        for (size_t i = 0; i < take; ++i) note_pair(at[i], miss[4 * i + 2]);
       } else {
         const unsigned take = nmiss < kCbMissCap ? nmiss : kCbMissCap;  // (pairs beyond the list's capacity are asked for again next round)
         miss.resize((size_t)4 * take);
@@ -2573,11 +2634,15 @@ static int cb_rounds(ctcd_decoder *d, ctcd_stream **states, const unsigned char 
         } else {
           HIP_TRY(hipMemcpy(miss.data(), scorer->cb_miss + 256, (size_t)take * sizeof(ctclm::MissEntry), hipMemcpyDeviceToHost));
         }
-        for (unsigned i = 0; i < take; ++i)
-          if (!scorer->cbl->resolve(miss[4 * i], miss[4 * i + 1])) return fail(CTCD_EINVAL, scorer->cbl->hs.error);
+        std::vector<uint32_t> at(take);
+        if (!cl.resolve_many(miss.data(), take, 4, at.data())) return fail(CTCD_EINVAL, cl.hs.error);
+        for (unsigned i = 0; i < take; ++i) note_pair(at[i], miss[4 * i + 2]);
       }
     }
   }
+  d->last_pairs[0] = n_queued;
+  d->last_pairs[1] = (long long)(cl.queries - asked0);
+  d->last_pairs[2] = n_same;
   return CTCD_OK;
 }
 
@@ -3278,6 +3343,18 @@ int ctcd_last_scorer_waits(ctcd_decoder *d) { return d ? d->last_cb_waits : -1; 
 int ctcd_set_scorer_wait(ctcd_decoder *d, int on) {
   if (!d) return fail(CTCD_EINVAL, "decoder == NULL");
   d->no_hook_wait = on == 0;
+  return CTCD_OK;
+}
+int ctcd_set_scorer_filter(ctcd_decoder *d, int on) {
+  if (!d) return fail(CTCD_EINVAL, "decoder == NULL");
+  d->no_lmq_filter = on == 0;
+  return CTCD_OK;
+}
+int ctcd_last_scorer_pairs(ctcd_decoder *d, long long *queued, long long *distinct, long long *repeat_same_item) {
+  if (!d) return fail(CTCD_EINVAL, "decoder == NULL");
+  if (queued) *queued = d->last_pairs[0];
+  if (distinct) *distinct = d->last_pairs[1];
+  if (repeat_same_item) *repeat_same_item = d->last_pairs[2];
   return CTCD_OK;
 }
 // ... and the number the fast prune pass flagged (settled by the device's std::sort replay + exact cumulative chain).  The

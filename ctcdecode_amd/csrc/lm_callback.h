@@ -21,6 +21,10 @@
 // The built-in ARPA tables are one implementation of the same interface (HostScorer::cond_log10): tests run the decoder with a
 // callback that asks them and require bit-identical results.  A callback backed by the `kenlm` Python module (binary models
 // included) is ctcdecode_amd.KenlmScorer.
+//
+// The callback comes in two forms: one window per call (CondLog10Fn), or many windows per call (CondLog10BatchFn: the serving
+// loop hands it every new window of the queued pairs it has read in one pass -- at most kBatchWindows -- so that a callback
+// behind an interpreter pays its per-call overhead once per batch, not once per window).
 #pragma once
 #include <cmath>
 #include <limits>
@@ -36,10 +40,19 @@ namespace ctclm {
 // log10 p(words[n-1] | words[0 .. n-2]) as kenlm's BaseScore gives it (float32).  Returns 0 = ok, 1 = the window holds an
 // out-of-vocabulary word (the reference returns OOV_SCORE), < 0 = error (the decode fails).
 typedef int (*CondLog10Fn)(void *user, const char *const *words, int n, float *log10_prob);
+// ... the batched form: `words` = n_windows * order pointers, window-major; per window log10_probs[i] and status[i] = 0 (ok) or
+// 1 (out of vocabulary).  Returns 0, or < 0 = error (the decode fails).
+typedef int (*CondLog10BatchFn)(void *user, const char *const *words, int n_windows, int order, float *log10_probs, int32_t *status);
+// Windows per call of a batched callback, at most.  The serving loop reads the queued pairs that have arrived, up to this many,
+// and asks their new windows in one call; the workgroups that wait for the first answers of a batch wait for the whole batch.
+// A pass of 512 queued pairs holds a few hundred new windows on a cold cache: a callback behind an interpreter spreads its per-call
+// overhead over hundreds of windows, and the wait it adds is a fraction of a millisecond per pass.
+constexpr int kBatchWindows = 512;
 
 struct CallbackLm {
   HostScorer hs;  // labels, dictionary, and the cache tables (ng, st_bo, st_fail, uni_prob, uni_state)
   CondLog10Fn fn = nullptr;
+  CondLog10BatchFn bfn = nullptr;  // (exactly one of the two is set)
   void *user = nullptr;
   // Per state its word history: order - 1 word ids, flat (state 0 is never used); found through an open-addressed index of state ids
   // keyed by the history's hash.  (Rounds 4-5 kept a vector per state behind an unordered_map: two allocations and three dependent cache
@@ -54,7 +67,11 @@ struct CallbackLm {
   size_t used = 0;                                         // cache slots in use
   std::vector<uint32_t> dirty;                             // slots written since the device copy was last brought up to date
   bool rehashed = true;                                    // the whole table must travel
-  unsigned long long queries = 0;                          // callback calls so far
+  unsigned long long queries = 0;                          // windows the callback has answered so far
+  unsigned long long batches = 0;                          // calls of a batched callback so far
+  std::vector<const char *> bw_;                           // scratch of ask_many: the windows' words ...
+  std::vector<float> bp_;                                  // ... and the answers
+  std::vector<int32_t> bs_;
 
   size_t n_states() const { return n_st; }
   const uint32_t *history(uint32_t state) const { return hist_flat.data() + (size_t)state * hl; }
@@ -87,10 +104,10 @@ struct CallbackLm {
   }
 
   bool build(double alpha, double beta, int order, const std::vector<std::string> &vocabulary, const std::vector<std::string> &labels,
-             CondLog10Fn fn_, void *user_) {
-    if (!fn_) return hs.fail("no scorer callback");
+             CondLog10Fn fn_, void *user_, CondLog10BatchFn bfn_ = nullptr) {
+    if (!fn_ == !bfn_) return hs.fail("no scorer callback");
     if (order < 1 || order > kMaxOrder) return hs.fail("max_order must be in [1, 6] (KENLM_MAX_ORDER of the reference's build)");
-    fn = fn_; user = user_;
+    fn = fn_; bfn = bfn_; user = user_;
     hs.alpha = alpha; hs.beta = beta; hs.order = order; hs.labels = labels;
     hs.vocab.assign(1, "<unk>");
     auto add = [&](const std::string &w) {
@@ -186,9 +203,40 @@ struct CallbackLm {
     return true;
   }
   void ask(Ask &a) const { a.rc = fn(user, a.ptr, a.n, &a.p10); }
+  // n prepared windows at once: one call of a batched callback (n <= kBatchWindows), or one call per window of the other form
+  void ask_many(Ask *a, int n) {
+    if (!bfn) {
+      for (int i = 0; i < n; ++i) ask(a[i]);
+      return;
+    }
+    if (n <= 0) return;
+    const int N = (int)hl + 1;
+    bw_.resize((size_t)n * N);
+    bp_.assign((size_t)n, 0.f);
+    bs_.assign((size_t)n, 0);
+    for (int i = 0; i < n; ++i)
+      for (int j = 0; j < N; ++j) bw_[(size_t)i * N + j] = a[i].ptr[j];
+    const int rc = bfn(user, bw_.data(), n, N, bp_.data(), bs_.data());
+    ++batches;
+    for (int i = 0; i < n; ++i) {
+      a[i].p10 = bp_[i];
+      a[i].rc = rc < 0 ? -1 : bs_[i] == 0 ? 0 : bs_[i] == 1 ? 1 : -2;
+    }
+  }
+  // one window outside a decode (ctcd_scorer_cond_log10 / cond_log_prob), in whichever form the callback has
+  int ask_one(const char *const *words, int n, float *p10) const {
+    if (fn) return fn(user, words, n, p10);
+    float p = 0.f;
+    int32_t st = 0;
+    const int rc = bfn(user, words, 1, n, &p, &st);
+    if (rc < 0) return rc;
+    *p10 = p;
+    return st == 0 ? 0 : st == 1 ? 1 : -1;
+  }
   bool commit(const Ask &a, uint32_t *slot_out = nullptr) {
     ++queries;
     float p10 = a.p10;
+    if (a.rc == -2) return hs.fail("scorer hook: the batched callback gave a window a status other than 0 (ok) or 1 (out of vocabulary)");
     if (a.rc < 0) return hs.fail("scorer hook: the callback reported an error");
     if (a.rc == 0 && !(p10 == p10)) return hs.fail("scorer hook: the callback returned NaN");
     // (an out-of-vocabulary answer is cached as -inf: a callback that reports a probability of zero that way must say
@@ -233,6 +281,50 @@ struct CallbackLm {
       ask(a);
     }
     return commit(a, slot_out);
+  }
+  // resolve() for n queued pairs (stride words apart: ctclm::MissEntry) with a batched callback: every pair the cache does not hold
+  // yet is asked once, up to kBatchWindows windows per call.  slots (optional): per pair, where its slot sits afterwards -- valid
+  // once the call returns true, unless the table moved (it can grow while the answers are cached).
+  bool resolve_many(const uint32_t *pairs, size_t n, size_t stride, uint32_t *slots = nullptr) {
+    if (!bfn) {
+      for (size_t i = 0; i < n; ++i)
+        if (!resolve(pairs[i * stride], pairs[i * stride + 1], slots ? &slots[i] : nullptr)) return false;
+      return true;
+    }
+    std::vector<Ask> asks((size_t)kBatchWindows);
+    std::vector<size_t> asked_by;  // the pair whose window each ask is
+    std::vector<size_t> later;     // pairs whose window an ask of the current batch already holds: their slots are looked up after it
+    asked_by.reserve(kBatchWindows);
+    int na = 0;
+    auto flush = [&]() -> bool {
+      if (!na) return true;
+      const auto t0 = std::chrono::steady_clock::now();
+      ask_many(asks.data(), na);
+      cb_seconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+      for (int k = 0; k < na; ++k) {
+        uint32_t at = 0;
+        if (!commit(asks[k], &at)) return false;
+        if (slots) slots[asked_by[k]] = at;
+      }
+      for (size_t i : later)
+        if (slots) slots[i] = (uint32_t)find_slot(pairs[i * stride], pairs[i * stride + 1]);
+      na = 0; asked_by.clear(); later.clear();
+      return true;
+    };
+    for (size_t i = 0; i < n; ++i) {
+      const uint32_t state = pairs[i * stride], word = pairs[i * stride + 1];
+      if (state != 0 && state < n_st && word != 0 && word < hs.vocab.size()) {
+        const long long at = find_slot(state, word);
+        if (at >= 0) { if (slots) slots[i] = (uint32_t)at; continue; }
+        bool dup = false;  // (the same new pair twice in one batch: the callback is asked once per window)
+        for (int k = 0; k < na && !dup; ++k) dup = asks[k].state == state && asks[k].word == word;
+        if (dup) { later.push_back(i); continue; }
+      }
+      if (!prepare(state, word, asks[na])) return false;
+      asked_by.push_back(i);
+      if (++na == kBatchWindows && !flush()) return false;
+    }
+    return flush();
   }
 };
 

@@ -151,7 +151,8 @@ double ctcd_scorer_cond_log_prob(const ctcd_scorer *scorer, const char *const *w
  *   5-gram model, 195 k windows, 86-88 ms cold in one launch -- 264 ms and 699 launches in round 5).  ctcd_last_scorer_rounds tells
  *   how many launches the last call took.  The cache of such a scorer starts with room for 2 M windows (64 + 32 MB of HBM).
  * ctcd_scorer_cond_log10 evaluates any scorer in the callback's own form (so the built-in tables can sit behind one);
- * ctcd_scorer_callback_calls counts the callback invocations so far (= distinct windows cached). */
+ * ctcd_scorer_callback_calls counts the windows the callback has answered so far (= distinct windows cached; for the batched form
+ * below too). */
 typedef int (*ctcd_cond_log10_fn)(void *user, const char *const *words, int n, float *log10_prob);
 int ctcd_scorer_create_callback(ctcd_scorer **out, double alpha, double beta, int max_order, const char *const *vocabulary,
                                 int n_vocabulary, ctcd_cond_log10_fn fn, void *user, const char *const *labels, int V, int device_id);
@@ -176,6 +177,35 @@ int ctcd_last_scorer_rounds(ctcd_decoder *dec);
  * ctcd_set_scorer_wait(dec, 0): every miss ends the utterance's launch, as in rounds 4-5 (identical results; tests run both). */
 int ctcd_last_scorer_waits(ctcd_decoder *dec);
 int ctcd_set_scorer_wait(ctcd_decoder *dec, int on);
+
+/* The batched form of the callback: one call asks many windows.
+ *   fn(user, words, n_windows, order, log10_probs, status): words = n_windows * order pointers, window-major, each window oldest
+ *     word first and "<s>"-padded exactly like ctcd_cond_log10_fn's; per window store log10_probs[i] and status[i] = 0 (ok) or
+ *     1 (out of vocabulary; log10_probs[i] is ignored).  Return 0, or < 0 to fail the decode.  The contract is the per-window one:
+ *     a pure function of the words, each distinct window asked once per scorer, NaN or +-inf with status 0 fails the decode, and
+ *     it is called on the thread that called the decoder.
+ *   Windows the device cache or the serving loop already answers never reach it.  The serving loop (the waiting launch and the
+ *   launch-per-round path alike) reads the queued pairs in passes of at most 512 and asks the new windows of a pass in one call:
+ *   a larger pass costs fewer calls but holds back the answers the first waiting workgroups need.  A batched scorer takes no
+ *   helper threads (ctcd_scorer_set_callback_threads refuses threads > 1 with CTCD_EUNSUPPORTED).
+ * ctcd_scorer_cond_log10_batch has the batched signature and evaluates any scorer (the batched counterpart of
+ * ctcd_scorer_cond_log10: built-in tables behind the batched hook).  ctcd_scorer_callback_calls keeps counting WINDOWS;
+ * ctcd_scorer_callback_batches counts calls of a batched callback (0 for the per-window form). */
+typedef int (*ctcd_cond_log10_batch_fn)(void *user, const char *const *words, int n_windows, int order, float *log10_probs,
+                                        int32_t *status);
+int ctcd_scorer_create_callback_batch(ctcd_scorer **out, double alpha, double beta, int max_order, const char *const *vocabulary,
+                                      int n_vocabulary, ctcd_cond_log10_batch_fn fn, void *user, const char *const *labels, int V,
+                                      int device_id);
+int ctcd_scorer_cond_log10_batch(const ctcd_scorer *scorer, const char *const *words, int n_windows, int order, float *log10_probs,
+                                 int32_t *status);
+long long ctcd_scorer_callback_batches(const ctcd_scorer *scorer);
+/* Queued (history, word) pairs of the decoder's last call through a callback scorer: *queued = pairs the kernels queued and the
+ * host read, *distinct = windows the call asked the callback for (its new cache entries), *repeat_same_item = queued pairs that
+ * the item which first queued the pair in this call queued again.  A callback scorer's kernels drop repeated misses of one
+ * utterance while it is parked (a small per-workgroup filter in LDS, cleared whenever the utterance is taken up);
+ * ctcd_set_scorer_filter(dec, 0) turns that off (measurements, tests: identical results, more queued pairs). */
+int ctcd_last_scorer_pairs(ctcd_decoder *dec, long long *queued, long long *distinct, long long *repeat_same_item);
+int ctcd_set_scorer_filter(ctcd_decoder *dec, int on);
 
 int ctcd_beam_decode_lm(ctcd_decoder *dec, const float *probs, const int32_t *seq_lens, int B, int T, int V, int beam,
                         int num_processes, double cutoff_prob, int cutoff_top_n, int blank_id, int log_input, ctcd_scorer *scorer,
