@@ -233,6 +233,7 @@ class KenlmScorer(CallbackScorer):
 
 # include/ctcdecode_amd.h CTCD_DTYPE_*: device tensors of these dtypes go to the library as they are (its kernels widen them)
 DTYPE_F32, DTYPE_F16, DTYPE_BF16 = 0, 1, 2
+_LAUNCH_ORDERS = {"batch": 0, "length": 1}  # include/ctcdecode_amd.h CTCD_ORDER_BATCH / CTCD_ORDER_LENGTH
 _HALF_DTYPES = {torch.float16: DTYPE_F16, torch.bfloat16: DTYPE_BF16}
 
 
@@ -329,6 +330,27 @@ class CTCBeamDecoder(object):
 
     def set_threads(self, n):
         _native.check(_native.lib.ctcd_set_threads(self._handle, int(n)))
+
+    def set_launch_order(self, order="batch"):
+        """"length": the workgroups of a launch take their utterances longest first (ranked by ``seq_lens`` on the device), so that a
+        long utterance of a batch larger than the device's resident workgroups does not start last and run on alone; "batch"
+        (default): workgroup i decodes utterance i.  Results are bit-identical either way (include/ctcdecode_amd.h
+        ctcd_set_launch_order).  Applies to every one-shot call (not to OnlineCTCBeamDecoder)."""
+        if order not in _LAUNCH_ORDERS:
+            raise ValueError("launch order must be 'batch' or 'length', not %r" % (order,))
+        _native.check(_native.lib.ctcd_set_launch_order(self._handle, _LAUNCH_ORDERS[order]))
+
+    def last_launch_order(self):
+        """The permutation the last call's workgroups took their utterances in (numpy int32 [B]: rank -> utterance), or None if that
+        call ran in batch order.  Waits for that call's order pass."""
+        import numpy as np
+
+        B = getattr(self, "_last_batch", 0)
+        out = np.empty((max(B, 1),), np.int32)
+        rc = _native.lib.ctcd_debug_last_launch_order(self._handle, out.ctypes.data_as(_native._i32p), B)
+        if rc < 0:
+            _native.check(rc)
+        return out[:B] if rc == 1 else None
 
     def set_cu_sharing(self, mode=1):
         """1: always launch the two-workgroups-per-CU build of the kernel (beam <= 128, <= 32 labels) -- for a serving loop
@@ -445,11 +467,13 @@ class CTCBeamDecoder(object):
                     self._handle, probs.data_ptr(), seq_lens.data_ptr() if seq_lens is not None else None, B, T, V, K,
                     self._num_processes, float(self._cutoff_prob), int(self.cutoff_top_n), int(self._blank_id), self._log_probs,
                     self._scorer.handle, output.data_ptr(), timesteps.data_ptr(), scores.data_ptr(), out_len.data_ptr(), None, stream))
+                self._last_batch = B  # (last_launch_order: the batch of the last call that was queued)
             else:
                 _native.check(_native.lib.ctcd_beam_decode(
                     self._handle, probs.data_ptr(), seq_lens.data_ptr() if seq_lens is not None else None, B, T, V, K,
                     self._num_processes, float(self._cutoff_prob), int(self.cutoff_top_n), int(self._blank_id), self._log_probs,
                     output.data_ptr(), timesteps.data_ptr(), scores.data_ptr(), out_len.data_ptr(), None, stream))
+                self._last_batch = B  # (last_launch_order: the batch of the last call that was queued)
             if check:
                 _native.check(_native.lib.ctcd_check_status(self._handle, B))
         return output, scores, timesteps, out_len
@@ -490,6 +514,7 @@ class CTCBeamDecoder(object):
                 self._num_processes, float(self._cutoff_prob), int(self.cutoff_top_n), int(self._blank_id), self._log_probs,
                 self._scorer.handle if self._scorer is not None else None, output.data_ptr(), timesteps.data_ptr(), scores.data_ptr(),
                 out_len.data_ptr(), None, stream))
+            self._last_batch = B  # (last_launch_order: the batch of the last call that was queued)
         return output, scores, timesteps, out_len
 
     def log_softmax(self, logits, seq_lens=None):
@@ -540,6 +565,7 @@ class CTCBeamDecoder(object):
                 float(self._cutoff_prob), int(self.cutoff_top_n), int(self._blank_id), self._log_probs,
                 self._scorer.handle if self._scorer is not None else None, hdr.data_ptr(), ent.data_ptr(), self._c_labels.data_ptr(),
                 cnt.data_ptr(), cap, scores.data_ptr(), out_len.data_ptr(), None, stream))
+            self._last_batch = B  # (last_launch_order: the batch of the last call that was queued)
             _native.check(_native.lib.ctcd_check_status(self._handle, B))
             n = int(cnt.item())
         # (an owned copy: the per-decoder buffer is overwritten by this decoder's next call, possibly while an asynchronous
@@ -576,6 +602,7 @@ class CTCBeamDecoder(object):
                 float(self._cutoff_prob), int(self.cutoff_top_n), int(self._blank_id), self._log_probs,
                 self._scorer.handle if self._scorer is not None else None, hdr.data_ptr(), ent.data_ptr(), self._c_labels.data_ptr(),
                 cnt.data_ptr(), cap, scores.data_ptr(), out_len.data_ptr(), None, stream.cuda_stream))
+            self._last_batch = B  # (last_launch_order: the batch of the last call that was queued)
             status = torch.empty((max(B, 1),), dtype=torch.int32, pin_memory=True)
             cnt_host = torch.empty((1,), dtype=torch.int32, pin_memory=True)
             _native.check(_native.lib.ctcd_fetch_status_async(self._handle, B, status.data_ptr(), stream.cuda_stream))

@@ -1128,6 +1128,58 @@ __global__ void debug_math_kernel(int mode, uint32_t start, uint32_t stride, con
   }
 }
 
+// ---- launch order (ctcd_set_launch_order): the permutation the decode kernel's workgroups take their items from by ticket
+// (decode_kernel.h KernelArgs::order = [ticket | permutation]), longest utterance first, ties in batch order -- a pure function of
+// the clamped lengths.  Either kernel also zeroes the ticket counter (order[0]) of the launch behind it.
+__device__ __forceinline__ int order_len(const int32_t *lens, int i, int T) {
+  const int l = lens ? lens[i] : T;
+  return l < 0 ? 0 : (l > T ? T : l);  // (as the decode kernel clamps them: binding.cpp:64-65)
+}
+
+// B <= kOrderSortMax: one workgroup sorts the keys (T - len) << 32 | b -- unique, so the sort is stable by construction -- with a
+// bitonic network in LDS; n = B rounded up to a power of two (the padding keys sort last).
+constexpr int kOrderThreads = 1024, kOrderSortMax = 16384;
+__global__ void __launch_bounds__(kOrderThreads) launch_order_sort_kernel(const int32_t *lens, int B, int T, int n, int *order) {
+  extern __shared__ unsigned long long okey[];
+  for (int i = threadIdx.x; i < n; i += blockDim.x)
+    okey[i] = i < B ? ((unsigned long long)(unsigned)(T - order_len(lens, i, T)) << 32) | (unsigned)i : ~0ull;
+  if (threadIdx.x == 0) order[0] = 0;
+  __syncthreads();
+  for (int k = 2; k <= n; k <<= 1) {
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      for (int i = threadIdx.x; i < (n >> 1); i += blockDim.x) {
+        const int lo = ((i & ~(j - 1)) << 1) | (i & (j - 1)), hi = lo | j;  // (pair i of the stage: bit log2(j) of lo is 0)
+        const unsigned long long x = okey[lo], y = okey[hi];
+        if ((x > y) == ((lo & k) == 0)) { okey[lo] = y; okey[hi] = x; }
+      }
+      __syncthreads();
+    }
+  }
+  for (int i = threadIdx.x; i < B; i += blockDim.x) order[1 + i] = (int)(unsigned)okey[i];
+}
+
+// Larger batches: every item counts the items that go in front of it and writes itself to its rank.  O(B^2) compares spread over
+// ceil(B / 256) workgroups: 0.52 ms at B = 20000, growing with the square (about 50 ms at 200 000 items, a second near a million --
+// where the decode itself takes far longer still).
+constexpr int kOrderRankThreads = 256, kOrderRankTile = 1024;
+__global__ void __launch_bounds__(kOrderRankThreads) launch_order_rank_kernel(const int32_t *lens, int B, int T, int *order) {
+  __shared__ int tile[kOrderRankTile];
+  const int i = blockIdx.x * kOrderRankThreads + threadIdx.x;
+  const int li = i < B ? order_len(lens, i, T) : 0;
+  int rank = 0;
+  for (int j0 = 0; j0 < B; j0 += kOrderRankTile) {
+    __syncthreads();
+    for (int t = threadIdx.x; t < kOrderRankTile; t += kOrderRankThreads) tile[t] = j0 + t < B ? order_len(lens, j0 + t, T) : -1;
+    __syncthreads();
+    for (int t = 0; t < kOrderRankTile; ++t) {
+      const int lj = tile[t];  // (-1 past the end: never in front)
+      rank += lj > li || (lj == li && j0 + t < i);
+    }
+  }
+  if (i < B) order[1 + rank] = i;
+  if (i == 0) order[0] = 0;
+}
+
 // binary64 log / exp / log_sum_exp of exact_math_f64.h on float images (modes 3..6 of ctcd_debug_math_check)
 __global__ void debug_math64_kernel(int mode, uint32_t start, uint32_t stride, const float *xs, const float *ys, uint64_t *out, size_t n) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1273,6 +1325,10 @@ struct ctcd_decoder {
   bool no_fused_logits = false;  // tests: raw logits always through the one-wave log_softmax pass and the separate prune
   int in_dtype = CTCD_DTYPE_F32;       // ctcd_set_input_dtype: the element type of probs / logits on every entry point
   int last_in_dtype = CTCD_DTYPE_F32;  // the element type the last call's pre-passes read (ctcd_last_input_dtype)
+  int launch_order = CTCD_ORDER_BATCH; // ctcd_set_launch_order
+  Buf order;                           // length order: [ticket | permutation] of a call's first launch, then of a resumed launch (scorer hook)
+  int last_order_items = 0;            // items of the last one-shot call's permutation in `order` (0: that call ran in batch order)
+  hipEvent_t ev_order = nullptr;       // recorded behind that call's order pass (ctcd_debug_last_launch_order waits for it)
   Buf prof, dbg, tl;
   int tl_f0 = 0, tl_nf = 0;
   int status_items = 0;          // items of the launch whose status words (and shape statistic) are in d->status
@@ -1448,6 +1504,7 @@ struct StreamCall {          // extra arguments of a streaming decode (lens: the
   int *frames_done = nullptr;       // device, [B]
   const int32_t *row_lens = nullptr;  // device, [B]: frame_off + lens = the rows the pre-passes (log conversion, pruning) cover
   const char *live = nullptr;         // the scorer's page-locked block as the device sees it (ctcd_scorer::d_live): the launch waits for its answers
+  bool one_shot = false;              // the launches of a one-shot decode through a callback scorer: they follow ctcd_set_launch_order
 };
 
 std::atomic<unsigned long long> g_stream_call_id{0};
@@ -1531,11 +1588,12 @@ void ctcd_destroy(ctcd_decoder *d) {
   }
   if (d->copy_stream) (void)hipStreamDestroy(d->copy_stream);
   if (d->ev_in) (void)hipEventDestroy(d->ev_in);
+  if (d->ev_order) (void)hipEventDestroy(d->ev_order);
   if (d->ev0) { (void)hipEventDestroy(d->ev0); (void)hipEventDestroy(d->ev1); (void)hipEventDestroy(d->ev2); (void)hipEventDestroy(d->ev3); }
   d->pool.release(); d->status.release(); d->prof.release(); d->tables.release(); d->logp.release(); d->lsm.release(); d->pr_ml.release(); d->flags.release();
   d->stage_in.release(); d->stage_out.release(); d->pr_cnt.release(); d->pr_ch.release(); d->pr_lp.release(); d->far.release(); d->st_args.release(); d->prune_in.release(); d->prune_out.release(); d->st_lens.release();
   d->dbg.release(); d->tl.release();
-  d->cb_blocks.release(); d->cb_ctl.release();
+  d->cb_blocks.release(); d->cb_ctl.release(); d->order.release();
   if (d->h_cb) (void)hipHostFree(d->h_cb);
   d->c_hdr.release(); d->c_ent.release(); d->c_rag.release(); d->c_cnt.release(); d->c_sc.release(); d->c_ln.release();
   if (d->h_stage) (void)hipHostFree(d->h_stage);
@@ -1555,6 +1613,25 @@ int ctcd_set_cu_sharing(ctcd_decoder *d, int mode) {
   if (!d || mode < -1 || mode > 1) return fail(CTCD_EINVAL, "cu sharing mode must be -1 (automatic), 0 or 1");
   d->cu_sharing = mode;
   return CTCD_OK;
+}
+
+int ctcd_set_launch_order(ctcd_decoder *d, int mode) {
+  if (!d || (mode != CTCD_ORDER_BATCH && mode != CTCD_ORDER_LENGTH)) return fail(CTCD_EINVAL, "launch order must be CTCD_ORDER_BATCH or CTCD_ORDER_LENGTH");
+  d->launch_order = mode;
+  return CTCD_OK;
+}
+
+int ctcd_debug_last_launch_order(ctcd_decoder *d, int32_t *out, int B) {
+  if (!d) return fail(CTCD_EINVAL, "decoder == NULL");
+  std::lock_guard<std::mutex> lock(d->mu);
+  if (d->last_order_items == 0) return 0;
+  if (!out || B != d->last_order_items)
+    return fail(CTCD_EINVAL, "the last call's launch order has " + std::to_string(d->last_order_items) + " items");
+  CTC_ON_DEVICE(d->device);
+  // (the event behind the order pass: the caller's stream may be gone by now)
+  HIP_TRY(hipEventSynchronize(d->ev_order));
+  HIP_TRY(hipMemcpy(out, (char *)d->order.p + 4, (size_t)B * 4, hipMemcpyDeviceToHost));
+  return 1;
 }
 
 int ctcd_set_subtree_search(ctcd_decoder *d, int mode) {
@@ -1688,7 +1765,10 @@ static int decode_common(ctcd_decoder *d, const float *probs, const int32_t *seq
   std::lock_guard<std::mutex> lock(d->mu);
   hipStream_t stream = (hipStream_t)stream_;
   CTC_ON_DEVICE(d->device);
-  if (B == 0) return CTCD_OK;
+  if (B == 0) {
+    if (!sc) d->last_order_items = 0;  // (ctcd_debug_last_launch_order: an empty call has no order)
+    return CTCD_OK;
+  }
   const Dims dims = make_dims(beam, V, cutoff_top_n, cutoff_prob, scorer != nullptr);
   // more than 65535 candidate slots (cutoff_top_n >= V with thousands of labels): the layout with 32-bit slot indices and
   // everything per slot in HBM scratch (workspace level 3) -- the reference has no such limit (decoder_utils.cpp:33-35)
@@ -2084,11 +2164,39 @@ static int decode_common(ctcd_decoder *d, const float *probs, const int32_t *seq
   // (CTCD_LDS_FLOOR: experiments with the occupancy the LDS request allows)
   if (d->lds_floor >= 0) lds = std::max(lds, std::min((size_t)d->lds_floor, (size_t)d->max_lds - 2048));
   HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  if (d->timing) HIP_TRY(hipEventRecord(d->ev0, stream));
+  // launch order (ctcd_set_launch_order): the one-shot entry points, and every launch of a one-shot decode through a callback scorer
+  // (a resumed launch by the frames each utterance has left; the debug copy shows the first launch's order); streaming calls keep
+  // batch order.  The order pass runs on the same stream, from the lengths already on the device: nothing waits for the host.
+  // (the wide-beam run-time layouts -- BIG kernels at LAYOUT 0 -- take no order: decode_kernel.h kTicket)
+  const bool by_length = d->launch_order == CTCD_ORDER_LENGTH && (!sc || sc->one_shot) && !(big && !wide3);
+  const bool first_launch = !sc || !sc->no_clear;
+  const bool records = (!sc || sc->one_shot) && first_launch;  // (the launch ctcd_debug_last_launch_order reports)
+  a.order = nullptr;
+  if (by_length) {
+    // [ticket | B items] of the first launch at 0, of a resumed launch (scorer hook) behind it
+    const size_t region = ((size_t)B + 64) * 4;
+    if ((rc = d->order.ensure(2 * region))) return rc;
+    a.order = (int *)((char *)d->order.p + (first_launch ? 0 : region));
+    if (records && !d->ev_order) HIP_TRY(hipEventCreateWithFlags(&d->ev_order, hipEventDisableTiming));
+  }
+  if (d->timing) HIP_TRY(hipEventRecord(d->ev0, stream));  // (with length order the timed span includes the order pass)
+  if (by_length) {
+    int n = 1;
+    while (n < B) n <<= 1;
+    if (B <= kOrderSortMax && (size_t)n * 8 <= (size_t)d->max_lds) {
+      HIP_TRY(hipFuncSetAttribute((const void *)launch_order_sort_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, n * 8));
+      launch_order_sort_kernel<<<1, kOrderThreads, (size_t)n * 8, stream>>>(seq_lens, B, T, n, a.order);
+    } else {
+      launch_order_rank_kernel<<<(B + kOrderRankThreads - 1) / kOrderRankThreads, kOrderRankThreads, 0, stream>>>(seq_lens, B, T, a.order);
+    }
+    HIP_TRY(hipGetLastError());
+    if (records) HIP_TRY(hipEventRecord(d->ev_order, stream));
+  }
   void *kargs[] = {&a};
   HIP_TRY(hipLaunchKernel(fn, dim3(B), dim3(threads), kargs, lds, stream));
   HIP_TRY(hipGetLastError());
   if (d->timing) HIP_TRY(hipEventRecord(d->ev1, stream));
+  if (records) d->last_order_items = by_length ? B : 0;  // (set once the launch is queued: a call that failed leaves the last record)
   return CTCD_OK;
 }
 
@@ -2370,7 +2478,8 @@ long long ctcd_scorer_callback_batches(const ctcd_scorer *s) { return s && s->cb
 // own time; a warm cache needs one launch.
 static int cb_rounds(ctcd_decoder *d, ctcd_stream **states, const unsigned char *is_eos, const int32_t *lens, const float *probs, int B, int T, int V,
                      int beam, double cutoff_prob, int cutoff_top_n, int blank_id, int log_input, ctcd_scorer *scorer, int32_t *out_tok,
-                     int32_t *out_ts, float *out_sc, int32_t *out_len, int32_t *n_results, int out_T, void *stream_, const CompactOut *co = nullptr) {
+                     int32_t *out_ts, float *out_sc, int32_t *out_len, int32_t *n_results, int out_T, void *stream_, const CompactOut *co = nullptr,
+                     bool one_shot = false) {
   // (the callback runs under this lock: a callback that decodes with the same scorer deadlocks -- include/ctcdecode_amd.h)
   std::lock_guard<std::mutex> cache_lock(scorer->cb_mu);
   hipStream_t stream = (hipStream_t)stream_;
@@ -2441,6 +2550,7 @@ static int cb_rounds(ctcd_decoder *d, ctcd_stream **states, const unsigned char 
     sc.frame_off = d_off;
     sc.frames_done = d_done;
     sc.row_lens = d_rows;
+    sc.one_shot = one_shot;
     volatile unsigned *h_len = (volatile unsigned *)scorer->h_live;
     volatile int32_t *h_done = (volatile int32_t *)(scorer->h_live + kLiveOffDone);
     volatile uint32_t *h_miss = (volatile uint32_t *)(scorer->h_live + kLiveOffMiss);  // (four words per pair: ctclm::MissEntry)
@@ -2679,7 +2789,7 @@ static int decode_lm_callback(ctcd_decoder *d, const float *probs, const int32_t
   HIP_TRY(hipMemset2DAsync(blocks + stream_thi_offset(capf, beam), blk, 0, stream_nodes(capf, beam) * sizeof(int), (size_t)B, stream));
   const std::vector<unsigned char> eos(B, 1);
   return cb_rounds(d, states.data(), eos.data(), len.data(), probs, B, T, V, beam, cutoff_prob, cutoff_top_n, blank_id, log_input, scorer, out_tok,
-                   out_ts, out_sc, out_len, n_results, T, stream_, co);
+                   out_ts, out_sc, out_len, n_results, T, stream_, co, true);
 }
 
 int ctcd_beam_decode_lm(ctcd_decoder *d, const float *probs, const int32_t *seq_lens, int B, int T, int V, int beam,

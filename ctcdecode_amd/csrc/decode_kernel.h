@@ -112,6 +112,7 @@ struct DevX {
   // The only mutable state, the per-wave record counters, lives in LDS (tlcnt): mutable members would push this whole
   // object into scratch memory.  A counter at or beyond tl_cap means "not recording".
   long long *tl; int *tlcnt; int tl_cap, tl_f0, tl_nf;
+  int itm;  // the batch item this workgroup decodes (blockIdx.x, or the one its ticket drew: KernelArgs::order)
   __device__ __forceinline__ void tl_rec() {
     if ((threadIdx.x & 63) == 0) {
       const int i = atomicAdd(&tlcnt[threadIdx.x >> 6], 1);
@@ -501,7 +502,7 @@ struct DevX {
     if ((threadIdx.x & 63) == 0 && v) atomicMax((unsigned *)p, v);
   }
   __device__ __forceinline__ unsigned global_add(unsigned *p, unsigned v) { return atomicAdd(p, v); }
-  __device__ __forceinline__ int item() const { return (int)blockIdx.x; }  // batch item of this workgroup
+  __device__ __forceinline__ int item() const { return itm; }  // batch item of this workgroup
   __device__ __forceinline__ void wave_min_to(int *p, uint32_t v) {
     v = ~wave_max_u32(~v);
     if ((threadIdx.x & 63) == 0) atomicMin((unsigned *)p, v);
@@ -896,6 +897,11 @@ struct KernelArgs {
   const ctclm::NgSlot *cb_log_slot;  // [cap] its contents
   int32_t *cb_done;                  // [B] 1 + status once the workgroup has left
   const unsigned *cb_ans;            // [B] queued pairs of the item the host has dealt with (with their slots in the log by then)
+  // launch order (ctcd_set_launch_order): [ticket counter at zero | a permutation of the B items, longest first], written by
+  // launch_order_sort_kernel / launch_order_rank_kernel in front of this launch.  Workgroups take their item in the order they start:
+  // the first to draw a ticket decodes order[1].  Null: workgroup i decodes item i.  (Read through the kernel-argument segment when
+  // the workgroup starts, so that no register holds it.)
+  int *order;
 };
 
 // LAYOUT: 0 = the workspace is laid out for the call's own beam width / vocabulary (array bases are run-time values);
@@ -932,7 +938,22 @@ __global__ void __launch_bounds__(1024, OCC2 ? 8 : 1) ctc_beam_decode_kernel(Ker
   extern __shared__ __attribute__((aligned(16))) char smem[];
   __shared__ uint64_t tbl[64];
   __shared__ int red[32];
-  const int b = (int)blockIdx.x;
+  // The item: blockIdx.x, or under length order the one its ticket draws (HIP promises no dispatch order, so the order is claimed when
+  // the workgroup starts -- one device-scope atomic).  Either way it reaches the waves through red[] (free until the barrier in front
+  // of the decode): the same code on both routes, and the kernels keep the register allocation they had with blockIdx.x alone.
+  // The wide-beam run-time layouts (BIG at LAYOUT 0) do not: there a claimed item costs 1-3 % of every launch, so they
+  // keep batch order (decode_common never passes them an order).
+  constexpr bool kTicket = !(BIG != 0 && LAYOUT == 0);
+  if (kTicket && threadIdx.x == 0) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    int *o = *(int *const *)((const char *)__builtin_amdgcn_kernarg_segment_ptr() + offsetof(KernelArgs, order));
+#else
+    int *o = a.order;
+#endif
+    red[0] = o ? o[1 + __hip_atomic_fetch_add((unsigned *)o, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)] : (int)blockIdx.x;
+  }
+  if (kTicket) __syncthreads();
+  const int b = kTicket ? __builtin_amdgcn_readfirstlane(red[0]) : (int)blockIdx.x;
   if (threadIdx.x < 64) tbl[threadIdx.x] = a.tables[threadIdx.x];
   Work w;
   // (every layout keeps the exact replay's scratch in per-utterance HBM scratch; the wide-beam layouts more: beam_core.h carve)
@@ -957,7 +978,7 @@ __global__ void __launch_bounds__(1024, OCC2 ? 8 : 1) ctc_beam_decode_kernel(Ker
   // (every instantiation for which this holds is listed, with its twin, in ctcdecode_amd.hip streamed_input_twin: the launch code swaps them)
   constexpr bool kNoStreamedInput = (PROF == 0 || PROF == 3) && LAYOUT == 1 && NT == 1024 && (LM == 0 || LM == 2) && !PRUNED && BIG == 0 && (!OCC2 || LM == 0);
   DevX<XP, BIG != 0, NT> x{red, 0, prof, 0, (PROF == 1 && a.dbg && b == 0) ? a.dbg : nullptr, 1 + 4 * a.K,
-                    (PROF == 2 && b == 0 && a.tl) ? tlbuf : nullptr, tlcnt, kTlCap, a.tl_f0, a.tl_nf};
+                    (PROF == 2 && b == 0 && a.tl) ? tlbuf : nullptr, tlcnt, kTlCap, a.tl_f0, a.tl_nf, b};
   int len = a.seq_lens ? __builtin_amdgcn_readfirstlane(a.seq_lens[b]) : a.T;
   len = len < 0 ? 0 : (len > a.T ? a.T : len);  // binding.cpp:64-65
   __syncthreads();
