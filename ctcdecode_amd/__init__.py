@@ -273,6 +273,17 @@ def _last_scorer_pairs(handle):
     return int(q.value), int(d.value), int(r.value)
 
 
+def _last_kernel(handle):
+    if not handle:  # (a ctypes.c_void_p holding NULL is false; the C call answers -1 both for "no launch yet" and for a NULL decoder)
+        raise ValueError("ctcdecode_amd: the decoder has no native handle")
+    out = (ctypes.c_int32 * 7)()
+    rc = _native.lib.ctcd_debug_last_kernel(handle, out)
+    if rc == -1:
+        return None
+    _native.check(rc)
+    return tuple(int(v) for v in out)
+
+
 def _adopt_scorer(scorer, model_path, num_labels, device_index):
     if model_path:
         raise ValueError("pass either model_path or scorer, not both")
@@ -370,6 +381,11 @@ class CTCBeamDecoder(object):
         1 fixed (beam <= 128, <= 32 labels), 2 the pruned default's (beam <= 112, cutoff_top_n <= 40), 3 wide beams at a compile-time
         size, 4-6 wide beams with HBM scratch; -1 none yet."""
         return int(_native.lib.ctcd_debug_last_layout(self._handle))
+
+    def last_kernel(self):
+        """Test hook: the template arguments (PROF, BIG, LAYOUT, PRUNED, NT, LM, OCC2) of the kernel instantiation the last launch used
+        (include/ctcdecode_amd.h ctcd_debug_last_kernel), or None before any launch."""
+        return _last_kernel(self._handle)
 
     def set_host_path(self, input_streaming=None, mirror_cap_labels=None):
         """Test hook for decode(): turn the streamed input off / on; shrink the host mirror of the compact results."""
@@ -799,6 +815,10 @@ class OnlineCTCBeamDecoder(object):
     def last_layout(self):
         """As CTCBeamDecoder.last_layout (the last chunk's launch)."""
         return int(_native.lib.ctcd_debug_last_layout(self._handle))
+
+    def last_kernel(self):
+        """As CTCBeamDecoder.last_kernel (the last chunk's launch)."""
+        return _last_kernel(self._handle)
 
     def set_scorer_wait(self, on=True):
         """As CTCBeamDecoder.set_scorer_wait."""

@@ -1339,6 +1339,7 @@ struct ctcd_decoder {
   bool subtree_on = false;       // the automatic choice for the next launch
   int last_subtree_search = 0;   // what the last launch used
   int last_layout = -1;          // the workspace layout the last launch used (ctcd_debug_last_layout; -1: none yet)
+  const void *last_fn = nullptr;  // the kernel the last launch used (ctcd_debug_last_kernel; null: none yet)
   int last_cb_rounds = 0;        // scorer hook: launches the last decode through a callback scorer took (ctcd_last_scorer_rounds)
   hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr, ev3 = nullptr;  // decode kernel | vocabulary-prune pass
   bool prune_timed = false;
@@ -1641,6 +1642,23 @@ int ctcd_set_subtree_search(ctcd_decoder *d, int mode) {
 }
 int ctcd_last_subtree_search(const ctcd_decoder *d) { return d ? d->last_subtree_search : -1; }
 int ctcd_debug_last_layout(const ctcd_decoder *d) { return d ? d->last_layout : -1; }
+
+// The template arguments of every instantiation the build compiled, keyed by its address: one entry per CTC_KERNEL_LIST item.
+int ctcd_debug_last_kernel(const ctcd_decoder *d, int32_t params[7]) {
+  struct Entry { const void *fn; int32_t p[7]; };
+#define CTC_X_ENTRY(PROF_, BIG_, LAYOUT_, PRUNED_, NT_, LM_, OCC2_, G_) \
+  {(const void *)ctc_beam_decode_kernel<PROF_, BIG_, LAYOUT_, PRUNED_, NT_, LM_, OCC2_>, {PROF_, BIG_, LAYOUT_, PRUNED_, NT_, (int)(LM_), OCC2_}},
+  static const Entry tab[] = {CTC_KERNEL_LIST(CTC_X_ENTRY)};
+#undef CTC_X_ENTRY
+  if (!d || !params) return fail(CTCD_EINVAL, "decoder == NULL or params == NULL");
+  if (!d->last_fn) return CTCD_EINVAL;  // (no launch yet: ctcd_last_error is left as it was)
+  for (const Entry &e : tab)
+    if (e.fn == d->last_fn) {
+      std::memcpy(params, e.p, sizeof(e.p));
+      return CTCD_OK;
+    }
+  return fail(CTCD_EINTERNAL, "the last launch used a kernel that is not in CTC_KERNEL_LIST");
+}
 
 int ctcd_set_input_dtype(ctcd_decoder *d, int dtype) {
   if (!d || (dtype != CTCD_DTYPE_F32 && dtype != CTCD_DTYPE_F16 && dtype != CTCD_DTYPE_BF16))
@@ -2160,7 +2178,7 @@ static int decode_common(ctcd_decoder *d, const float *probs, const int32_t *seq
   }
   // the workspace layout of the kernel chosen above (include/ctcdecode_amd.h ctcd_debug_last_layout), in the order the selection
   // lets one override another: the HBM-scratch levels over everything but LAYOUT 3, LAYOUT 2 over LAYOUT 1 (they exclude each other)
-  d->last_layout = wide3 ? 3 : big ? 3 + far_level : fixed2 ? 2 : fixed ? 1 : 0;
+  const int layout = wide3 ? 3 : big ? 3 + far_level : fixed2 ? 2 : fixed ? 1 : 0;
   // (CTCD_LDS_FLOOR: experiments with the occupancy the LDS request allows)
   if (d->lds_floor >= 0) lds = std::max(lds, std::min((size_t)d->lds_floor, (size_t)d->max_lds - 2048));
   HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -2195,6 +2213,8 @@ static int decode_common(ctcd_decoder *d, const float *probs, const int32_t *seq
   void *kargs[] = {&a};
   HIP_TRY(hipLaunchKernel(fn, dim3(B), dim3(threads), kargs, lds, stream));
   HIP_TRY(hipGetLastError());
+  d->last_layout = layout;  // (recorded once the launch is queued: a launch that failed leaves the last record)
+  d->last_fn = fn;
   if (d->timing) HIP_TRY(hipEventRecord(d->ev1, stream));
   if (records) d->last_order_items = by_length ? B : 0;  // (set once the launch is queued: a call that failed leaves the last record)
   return CTCD_OK;

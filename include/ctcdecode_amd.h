@@ -368,6 +368,12 @@ int ctcd_last_subtree_search(const ctcd_decoder *dec);
  * compile-time size (beam <= 500, <= 29 labels, no pruning); 4 / 5 / 6 = the run-time layout with HBM scratch at level 1 / 2 / 3
  * (wide beams; level 3: more than 65535 candidate slots).  -1: no launch yet. */
 int ctcd_debug_last_layout(const ctcd_decoder *dec);
+/* The kernel instantiation the last decode launch used (tests prove with it that every instantiation is reached): writes its
+ * template arguments {PROF, BIG, LAYOUT, PRUNED, NT, LM, OCC2} (decode_kernel.h CTC_KERNEL_LIST; LM as 0 / 1 / 2 / 3, the others
+ * as 0 / 1 or their value) to params[7] and returns CTCD_OK.  A launch that failed is not recorded (nor by ctcd_debug_last_layout).
+ * -1 (CTCD_EINVAL): no launch yet, or a NULL argument (that case alone sets ctcd_last_error); CTCD_EINTERNAL: the launched kernel is
+ * not in the build's list (a bug). */
+int ctcd_debug_last_kernel(const ctcd_decoder *dec, int32_t params[7]);
 int ctcd_workgroup_lds_bytes(int beam, int V, int cutoff_top_n, double cutoff_prob); /* LDS one utterance needs (default build) */
 const char *ctcd_last_error(void);
 const char *ctcd_version(void);

@@ -25,7 +25,7 @@ def test_library_exports_every_declared_symbol():
     names = _declared()
     assert "ctcd_beam_decode" in names and "ctcd_beam_decode_host" in names and len(names) >= 9
     # the hook the GPU tests prove with which workspace layout (which kernel) a decode ran
-    assert "ctcd_debug_last_layout" in names
+    assert "ctcd_debug_last_layout" in names and "ctcd_debug_last_kernel" in names
     from ctcdecode_amd import _native
 
     assert set(names) <= set(_native.SYMBOLS), sorted(set(names) - set(_native.SYMBOLS))
@@ -35,6 +35,19 @@ def test_library_exports_every_declared_symbol():
     assert b"gfx950" in lib.ctcd_version()
     lib.ctcd_workgroup_lds_bytes.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double]
     assert 0 < lib.ctcd_workgroup_lds_bytes(100, 29, 40, 1.0) <= 160 * 1024  # BASELINE.json configs[1] fits one CU's LDS
+
+
+def test_kernel_matrix_covers_every_instantiation():
+    """tests/test_gpu_kernel_matrix.py has one case per instantiation the product build compiles (decode_kernel.h CTC_KERNEL_LIST,
+    its #else branch): an instantiation added without a case, or a case whose kernel no longer exists, fails here."""
+    import kernel_matrix_util as km
+
+    listed = km.parse_kernel_list(open(os.path.join(ROOT, "ctcdecode_amd", "csrc", "decode_kernel.h")).read())
+    assert len(listed) == 60 and len(set(listed)) == len(listed), len(listed)
+    cases = [c["kernel"] for c in km.CASES]
+    assert len(set(cases)) == len(cases), "two matrix cases expect the same kernel"
+    assert set(cases) == set(listed), (sorted(set(listed) - set(cases)), sorted(set(cases) - set(listed)))
+    assert len({km.case_id(c) for c in km.CASES}) == len(cases)
 
 
 def test_python_signature_mirrors_reference():

@@ -99,3 +99,24 @@ def test_prob_and_log_input_agree_on_labels():
     a = ou.decode(lp, beam=8, log_input=True)
     b = ou.decode(np.exp(lp), beam=8, log_input=False)
     assert np.array_equal(a["tokens"][:, 0], b["tokens"][:, 0])
+
+
+def test_kernel_matrix_overflow_frames_are_not_inf_frames():
+    """The degenerate utterance of every scorer-free case of tests/test_gpu_kernel_matrix.py exercises the overflow: with its two
+    -3e38 frames written as -inf instead, the oracle's result for that utterance changes."""
+    import kernel_matrix_util as km
+
+    for c in km.CASES:
+        if c["lm"]:
+            continue
+        d = km.degenerate_item(c)
+        args = dict(beam=c["K"], cutoff_prob=c["cutoff_prob"], cutoff_top_n=c["top_n"], blank_id=c["blank"], which="restated")
+        lp, sl = km.inputs(c)
+        r = ou.decode(lp, sl, **args)
+        lp_inf, _ = km.inputs(c, overflow_as_inf=True)
+        assert not np.array_equal(lp, lp_inf)
+        q = ou.decode(lp_inf, sl, **args)
+        same = all(np.array_equal(r[k][d], q[k][d]) for k in ("tokens", "timesteps", "lens")) and np.array_equal(
+            r["scores"][d].view(np.uint32), q["scores"][d].view(np.uint32))
+        assert not same, km.case_id(c)
+
