@@ -16,7 +16,14 @@ batch i+1 (ctcdecode_amd.distributed.ResultGatherer), all gathers complete befor
             contiguous blocks of ceil(2048 / N) (ctcdecode_amd.distributed.shard_bounds), one block per rank;
         4 = configs[4]: B=1024, beam 100, T=1500, with the LM scorer on tests/data/test.arpa (alpha 0.5, beta 1.0), strong scaling.
 
-Rank 0 prints ONE JSON line (see DESIGN.md "Measurement" for the definition of every field).
+Rank 0 prints ONE JSON line (see DESIGN.md "Measurement" for the definition of every field).  A plain run sets up, warms up,
+times the steps, writes its outputs if asked to and prints the headline line (metric, value, unit, ms_per_step, ...); nothing
+else is launched or timed.
+
+    python bench.py ... --full   also measures everything else, outside the timed region: the kernel duration by HIP events
+        (kernel_ms, roofline, latency), roofline.traffic by two rocprofv3 --pmc child runs, the extras of config 1 (e2e,
+        compact_results, pipelined, two_in_flight, seeds, streaming, other_configs), configs 2 / 4's partition_probe and the
+        CPU baseline of the reference.  --no-pmc, --no-extras and --no-cpu-baseline leave parts of it out.
 
     python bench.py ... --dump-outputs DIR   also writes what the last timed step returned (beam_results, beam_scores,
         timesteps, out_lens) as DIR/<name>.npy in float32 -- the inputs are seeded, so two builds can be compared output
@@ -71,13 +78,15 @@ def parse():
     ap.add_argument("--backend", default="", help="torch.distributed backend (default nccl = RCCL; gloo when ranks share a device)")
     ap.add_argument("--min-shard", type=int, default=0, help="configs 2 / 4 (strong scaling): at least this many utterances per rank -- fill a GPU (256 = its CU count) "
                     "before adding ranks; the ranks left over get empty shards (ctcdecode_amd.distributed.shard_size)")
-    ap.add_argument("--pmc", action="store_true", default=True, help="(default since round 5) measure roofline.traffic in this run: two rocprofv3 --pmc child runs of "
+    ap.add_argument("--full", action="store_true", help="besides the headline, measure the kernel duration, roofline and latency figures, "
+                    "the counter passes, the extras and the CPU baseline (outside the timed region; off: the headline line alone)")
+    ap.add_argument("--pmc", action="store_true", default=True, help="(with --full, the default there) measure roofline.traffic in this run: two rocprofv3 --pmc child runs of "
                     "tools/pmc_child.py (FETCH_SIZE, WRITE_SIZE: counters only, one per pass, as MI355X_MICROARCH.md prescribes; ~8 s each, outside the "
                     "timed region); the constant in --traffic-json is the fallback when the profiler is missing or fails")
-    ap.add_argument("--no-pmc", dest="pmc", action="store_false", help="use the committed constant (--traffic-json) for roofline.traffic")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the e2e and other_configs measurements (profiling runs)")
-    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="target CPU time of the cpu_baseline sample")
+    ap.add_argument("--no-pmc", dest="pmc", action="store_false", help="with --full: use the committed constant (--traffic-json) for roofline.traffic")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the cpu_baseline measurement")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the e2e, other_configs and partition_probe measurements (profiling runs)")
+    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="with --full: target CPU time of the cpu_baseline sample")
     ap.add_argument("--traffic-json", default=os.path.join(ROOT, "profiles", "traffic_latest.json"),
                     help="per-launch HBM bytes of the decode kernel from a rocprofv3 --pmc pass (tools/rocprof_summary.py)")
     ap.add_argument("--dump-outputs", metavar="DIR", default="",
@@ -802,46 +811,50 @@ def main():
         tt = torch.tensor([elapsed], dtype=torch.float64, device=dev if backend == "nccl" else "cpu")
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
-    # kernel duration of the last timed launch (HIP events on the launch stream); averaged over a few extra launches
-    # OUTSIDE the timed region so the event reads do not perturb it
-    durs = []
-    for _ in range(max(3, min(a.steps, 10)) if a.config == 1 else 2):
-        res = dec.decode_device(lp, None, check=False)
-        torch.cuda.synchronize()
-        durs.append(dec.last_kernel_ms())
-    ctcdecode_amd._native.check(ctcdecode_amd._native.lib.ctcd_check_status(dec._handle, B))
-    kern_ms = float(np.mean(durs))
-    kern_all = [kern_ms]
-    if use_dist:  # every rank's kernel duration (rank order)
-        kt = torch.tensor([kern_ms], dtype=torch.float64, device=dev if backend == "nccl" else "cpu")
-        parts = [torch.zeros_like(kt) for _ in range(world)]
-        dist.all_gather(parts, kt)
-        kern_all = [float(p.item()) for p in parts]
+    if not a.full:
+        # (a plain run launches nothing more: the status words of the last timed launch, which ran with check=False, are
+        #  read here; the compact forms read their own)
+        if not compact:
+            ctcdecode_amd._native.check(ctcdecode_amd._native.lib.ctcd_check_status(dec._handle, B))
+    else:
+        # kernel duration of the last timed launch (HIP events on the launch stream); averaged over a few extra launches
+        # OUTSIDE the timed region so the event reads do not perturb it
+        durs = []
+        for _ in range(max(3, min(a.steps, 10)) if a.config == 1 else 2):
+            res = dec.decode_device(lp, None, check=False)
+            torch.cuda.synchronize()
+            durs.append(dec.last_kernel_ms())
+        ctcdecode_amd._native.check(ctcdecode_amd._native.lib.ctcd_check_status(dec._handle, B))
+        kern_ms = float(np.mean(durs))
+        kern_all = [kern_ms]
+        if use_dist:  # every rank's kernel duration (rank order)
+            kt = torch.tensor([kern_ms], dtype=torch.float64, device=dev if backend == "nccl" else "cpu")
+            parts = [torch.zeros_like(kt) for _ in range(world)]
+            dist.all_gather(parts, kt)
+            kern_all = [float(p.item()) for p in parts]
 
-    out_len = res[3]
-    # ALGORITHMIC bytes per utterance: read T*V*4 of input + write the valid token/timestep prefixes
-    # (8 bytes per emitted label per beam) + scores and lengths (8 bytes per beam) + 4 (seq_len)
-    alg_bytes = B * (T * V * 4 + 8 * K + 4) + 8 * int(out_len.sum().item())
-    achieved = alg_bytes / (kern_ms * 1e-3) / 1e9 if kern_ms > 0 else 0.0
-    traffic, traffic_src, tj = None, None, {}
-    if os.path.exists(a.traffic_json):
-        try:
-            tj = json.load(open(a.traffic_json))
-            traffic, traffic_src = tj.get("hbm_bytes_per_launch"), tj.get("source")
-        except Exception:
-            traffic = None
-    traffic_note = ("constant from profiles/%s (rocprofv3 --pmc FETCH_SIZE/WRITE_SIZE passes of this command), not measured in this run" % traffic_src) if traffic else None
-    if a.pmc and rank == 0 and a.config == 1 and not use_dist:
-        measured, note = measure_traffic(a)
-        if measured:
-            traffic, traffic_note = measured, note
-        elif traffic_note:
-            traffic_note += "; --pmc: " + note
+        out_len = res[3]
+        # ALGORITHMIC bytes per utterance: read T*V*4 of input + write the valid token/timestep prefixes
+        # (8 bytes per emitted label per beam) + scores and lengths (8 bytes per beam) + 4 (seq_len)
+        alg_bytes = B * (T * V * 4 + 8 * K + 4) + 8 * int(out_len.sum().item())
+        achieved = alg_bytes / (kern_ms * 1e-3) / 1e9 if kern_ms > 0 else 0.0
+        traffic, traffic_src, tj = None, None, {}
+        if os.path.exists(a.traffic_json):
+            try:
+                tj = json.load(open(a.traffic_json))
+                traffic, traffic_src = tj.get("hbm_bytes_per_launch"), tj.get("source")
+            except Exception:
+                traffic = None
+        traffic_note = ("constant from profiles/%s (rocprofv3 --pmc FETCH_SIZE/WRITE_SIZE passes of this command), not measured in this run" % traffic_src) if traffic else None
+        if a.pmc and rank == 0 and a.config == 1 and not use_dist:
+            measured, note = measure_traffic(a)
+            if measured:
+                traffic, traffic_note = measured, note
+            elif traffic_note:
+                traffic_note += "; --pmc: " + note
 
     if rank == 0:
-        floor = sum(FRAME_FLOOR.values())
-        frame_clocks = kern_ms * 1e-3 / T * SHADER_GHZ * 1e9
-        workload = {1: "BASELINE.json configs[1]: CTC prefix beam search, no LM, log-softmax of N(0,1) logits; HBM-resident tensors (input in HBM, the four result tensors left in HBM: `e2e` is the host-to-host call)",
+        workload = {1: "BASELINE.json configs[1]: CTC prefix beam search, no LM, log-softmax of N(0,1) logits; HBM-resident tensors (input in HBM, the four result tensors left in HBM: `e2e`, with --full, is the host-to-host call)",
                     2: "BASELINE.json configs[2]: B=2048 batch-sharded, beam 500, T=2000, no LM, compact RCCL gather",
                     4: "BASELINE.json configs[4]: B=1024 batch-sharded, beam 100, T=1500, LM scorer on tests/data/test.arpa (alpha 0.5, beta 1.0)"}[a.config]
         line = {
@@ -859,20 +872,25 @@ def main():
                        "global_batch": B_total, "ranks": world, "devices_visible": ndev,
                        "parallelism": "batch-sharded x%d, gather=%s/%s, backend=%s" % (world, a.gather, a.gather_format, backend) if use_dist else "single GPU",
                        "threads_per_workgroup": a.threads or "default"},
-            "kernel_ms": round(kern_ms, 4),
-            "kernel_ms_per_rank": [round(v, 4) for v in kern_all],
-            "us_per_frame": round(kern_ms * 1e3 / T, 4),
-            "roofline": {"bound": "hbm", "achieved": round(achieved, 3), "peak": 8000.0, "unit": "GB/s",
-                         "frac": round(achieved / 8000.0, 6), "traffic": traffic if a.config == 1 else None,
-                         "traffic_source": traffic_note,
-                         "traffic_ratio": round(traffic / alg_bytes, 2) if traffic and a.config == 1 else None,
-                         "memset_bytes_outside_kernel": 2 * B * K * T * 4 + 2 * B * K * 4,
-                         "kernel": "ctc_beam_decode_kernel", "algorithmic_bytes_per_launch": alg_bytes},
-            # the recurrence is latency-bound, not HBM-bound: distance from the critical-path floor of one frame
-            "latency": {"frame_clocks": round(frame_clocks), "floor_clocks": floor, "frame_over_floor": round(frame_clocks / floor, 2),
-                        "shader_ghz_assumed": SHADER_GHZ, "floor_terms": FRAME_FLOOR},
         }
-        if strong and not a.no_extras:
+        if a.full:
+            floor = sum(FRAME_FLOOR.values())
+            frame_clocks = kern_ms * 1e-3 / T * SHADER_GHZ * 1e9
+            line.update({
+                "kernel_ms": round(kern_ms, 4),
+                "kernel_ms_per_rank": [round(v, 4) for v in kern_all],
+                "us_per_frame": round(kern_ms * 1e3 / T, 4),
+                "roofline": {"bound": "hbm", "achieved": round(achieved, 3), "peak": 8000.0, "unit": "GB/s",
+                             "frac": round(achieved / 8000.0, 6), "traffic": traffic if a.config == 1 else None,
+                             "traffic_source": traffic_note,
+                             "traffic_ratio": round(traffic / alg_bytes, 2) if traffic and a.config == 1 else None,
+                             "memset_bytes_outside_kernel": 2 * B * K * T * 4 + 2 * B * K * 4,
+                             "kernel": "ctc_beam_decode_kernel", "algorithmic_bytes_per_launch": alg_bytes},
+                # the recurrence is latency-bound, not HBM-bound: distance from the critical-path floor of one frame
+                "latency": {"frame_clocks": round(frame_clocks), "floor_clocks": floor, "frame_over_floor": round(frame_clocks / floor, 2),
+                            "shader_ghz_assumed": SHADER_GHZ, "floor_terms": FRAME_FLOOR},
+            })
+        if a.full and strong and not a.no_extras:
             # The partition rule: an utterance occupies one CU, so a shard below the CU count idles CUs
             # without finishing sooner.  This GPU's kernel time for the shard of the named 8-GPU partition and for a shard
             # that fills it: equal times mean half the GPUs do the same job in the same time (--min-shard 256).
@@ -891,7 +909,7 @@ def main():
                 line["partition_probe"] = {"error": str(e)[:200]}
         if shared:
             line["config"]["oversubscribed"] = "%d ranks on %d device(s): a dry run of the N-rank path, not a scaling number" % (world, ndev)
-        if world == 1 and not a.no_extras and a.config == 1:
+        if a.full and world == 1 and not a.no_extras and a.config == 1:
             # (its own decoder, released afterwards: decode() keeps a second HIP stream for the streamed input, and HIP maps
             #  streams onto a few hardware queues -- 4 by default, GPU_MAX_HW_QUEUES -- so a stream left behind here can end up
             #  sharing a queue with one of the `pipelined` measurement's three: INTEGRATION.md 5)
@@ -946,7 +964,7 @@ def main():
                 line["other_configs"] = other_configs(torch, ctcdecode_amd, dev, tj)
             except Exception as e:
                 line["other_configs"] = {"error": str(e)[:300]}
-        if not a.no_cpu_baseline:  # (rank 0's host cores, on rank 0's own shard; outside the timed region)
+        if a.full and not a.no_cpu_baseline:  # (rank 0's host cores, on rank 0's own shard; outside the timed region)
             line["cpu_baseline"] = cpu_baseline(lp_cpu.numpy(), K, a.cpu_seconds, lm=(labels,) + cfg["lm"] if cfg["lm"] else None)
         if a.dump_outputs:
             line["dump_outputs"] = dump_outputs(np, last_outputs, a.dump_outputs)

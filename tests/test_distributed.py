@@ -273,17 +273,39 @@ def test_bench_launches_its_own_ranks():
 
 
 @pytest.mark.gpu
+def test_bench_plain_run_prints_the_headline_alone():
+    """`python bench.py` without --full: the headline fields, and none of what --full measures outside the timed region
+    (kernel duration, roofline, counter passes, extras, CPU baseline)."""
+    import json
+    import subprocess
+
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "32",
+                        "--frames", "200"], capture_output=True, text=True, timeout=600, env=env)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    d = json.loads(lines[0])
+    assert d["metric"].startswith("utterances/sec") and d["unit"] == "utterances/s"
+    assert d["higher_is_better"] is True and d["dtype"] == "f32" and d["steps"] == 3 and d["warmup"] == 1
+    assert d["value"] > 0 and d["ms_per_step"] > 0 and abs(d["value"] - 32 * 1e3 / d["ms_per_step"]) <= 1e-3 * d["value"]
+    full_only = {"kernel_ms", "kernel_ms_per_rank", "us_per_frame", "roofline", "latency", "partition_probe", "e2e", "compact_results",
+                 "pipelined", "two_in_flight", "seeds", "streaming", "other_configs", "cpu_baseline"}
+    assert not full_only & set(d), sorted(full_only & set(d))
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("config,batch,extra", [(2, 12, ["--beam", "500", "--frames", "120"]), (4, 10, ["--frames", "150"])])
 def test_bench_strong_scaling_configs_two_rank_dry_run(config, batch, extra):
     """BASELINE.json's 8-GPU configurations as bench modes (configs[2]: beam 500; configs[4]: with the LM scorer), strong
     scaling: the named TOTAL batch is cut into contiguous blocks (shard_bounds).  Dry run with two ranks on this box's one
-    device (gloo), shrunk in batch / frames; cpu_baseline is part of every line."""
+    device (gloo), shrunk in batch / frames; with --full, cpu_baseline and every rank's kernel time are part of the line."""
     import json
     import subprocess
 
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--config", str(config), "--steps", "2", "--warmup", "1",
-                        "--batch", str(batch), "--cpu-seconds", "2"] + extra, capture_output=True, text=True, timeout=900, env=env)
+                        "--batch", str(batch), "--cpu-seconds", "2", "--full"] + extra, capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout

@@ -18,7 +18,7 @@ if has suite; then
   ( time timeout ${SUITE_TIMEOUT:-900} python -m pytest tests -m gpu -x -q --durations=8 ) > "$OUT/pytest_gpu.log" 2>&1; echo "pytest rc=$?" | tee -a "$OUT/host.txt"; tail -14 "$OUT/pytest_gpu.log"
 fi
 if has bench; then
-  ( time timeout 600 python bench.py --steps 20 --warmup 3 ) > "$OUT/bench.json" 2> "$OUT/bench.err"; echo "bench rc=$?"; cut -c1-600 "$OUT/bench.json"; tail -3 "$OUT/bench.err"
+  ( time timeout 600 python bench.py --steps 20 --warmup 3 --full ) > "$OUT/bench.json" 2> "$OUT/bench.err"; echo "bench rc=$?"; cut -c1-600 "$OUT/bench.json"; tail -3 "$OUT/bench.err"
 fi
 cd /tmp
 if has stats; then

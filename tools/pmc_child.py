@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """The workload bench.py's counter passes profile (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE around this script): the headline
-batch decoded a few times, nothing else -- the passes must be cheap enough to run inside every bench.py run.
+batch decoded a few times, nothing else -- the passes must be cheap enough to run inside every bench.py --full run.
     python tools/pmc_child.py B T V beam threads [seed]        (seed: bench.py passes its rank-0 seed, 1234)"""
 import os
 import sys
