@@ -284,6 +284,31 @@ def _last_kernel(handle):
     return tuple(int(v) for v in out)
 
 
+# include/ctcdecode_amd.h CTCD_PP_*: the pre-pass kernels, and the stages ctcd_debug_last_prepass reports them in
+PREPASS_KERNELS = {1: "prob_to_log", 2: "widen", 3: "lsm_wave", 4: "lsm_wg", 5: "prune_rows", 6: "prune_wg", 7: "prune_logits", 8: "resolve"}
+PREPASS_STAGES = ("elementwise", "log_softmax", "prune", "resolve")
+DTYPE_NAMES = {DTYPE_F32: "f32", DTYPE_F16: "f16", DTYPE_BF16: "bf16"}
+
+
+def _last_prepass(handle):
+    if not handle:
+        raise ValueError("ctcdecode_amd: the decoder has no native handle")
+    out = (ctypes.c_int32 * 16)()
+    _native.check(_native.lib.ctcd_debug_last_prepass(handle, out))
+    return {st: (PREPASS_KERNELS[out[4 * i]], int(out[4 * i + 1]), int(out[4 * i + 2]), DTYPE_NAMES[out[4 * i + 3]]) if out[4 * i] else None
+            for i, st in enumerate(PREPASS_STAGES)}
+
+
+def prepass_table():
+    """Every pre-pass kernel instantiation of the build (include/ctcdecode_amd.h ctcd_debug_prepass_table): a list of
+    (kernel, a, b, dtype, largest V the dispatch sends to it or 0), named as ``last_prepass()`` names them."""
+    n = int(_native.lib.ctcd_debug_prepass_table(None, 0))
+    out = (ctypes.c_int32 * (5 * n))()
+    _native.lib.ctcd_debug_prepass_table(out, n)
+    return [(PREPASS_KERNELS[out[5 * i]], int(out[5 * i + 1]), int(out[5 * i + 2]), DTYPE_NAMES[out[5 * i + 3]], int(out[5 * i + 4]))
+            for i in range(n)]
+
+
 def _adopt_scorer(scorer, model_path, num_labels, device_index):
     if model_path:
         raise ValueError("pass either model_path or scorer, not both")
@@ -386,6 +411,13 @@ class CTCBeamDecoder(object):
         """Test hook: the template arguments (PROF, BIG, LAYOUT, PRUNED, NT, LM, OCC2) of the kernel instantiation the last launch used
         (include/ctcdecode_amd.h ctcd_debug_last_kernel), or None before any launch."""
         return _last_kernel(self._handle)
+
+    def last_prepass(self):
+        """Test hook: the pre-pass kernels the last call launched (include/ctcdecode_amd.h ctcd_debug_last_prepass), as a dict over the
+        stages "elementwise", "log_softmax", "prune", "resolve" of None (nothing launched) or (kernel, a, b, dtype): kernel one of
+        "prob_to_log", "widen", "lsm_wave", "lsm_wg" (a = F4), "prune_rows" (a = R), "prune_wg" (a = F4, b = REG), "prune_logits" (a = F4),
+        "resolve" (b = 1: its arrays in global memory); dtype "f32" / "f16" / "bf16"."""
+        return _last_prepass(self._handle)
 
     def set_host_path(self, input_streaming=None, mirror_cap_labels=None):
         """Test hook for decode(): turn the streamed input off / on; shrink the host mirror of the compact results."""
@@ -819,6 +851,10 @@ class OnlineCTCBeamDecoder(object):
     def last_kernel(self):
         """As CTCBeamDecoder.last_kernel (the last chunk's launch)."""
         return _last_kernel(self._handle)
+
+    def last_prepass(self):
+        """As CTCBeamDecoder.last_prepass (the last chunk's pre-passes)."""
+        return _last_prepass(self._handle)
 
     def set_scorer_wait(self, on=True):
         """As CTCBeamDecoder.set_scorer_wait."""

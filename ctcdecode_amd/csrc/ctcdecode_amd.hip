@@ -1340,6 +1340,9 @@ struct ctcd_decoder {
   int last_subtree_search = 0;   // what the last launch used
   int last_layout = -1;          // the workspace layout the last launch used (ctcd_debug_last_layout; -1: none yet)
   const void *last_fn = nullptr;  // the kernel the last launch used (ctcd_debug_last_kernel; null: none yet)
+  // the pre-pass kernels the last call queued (ctcd_debug_last_prepass): elementwise | log_softmax | prune | prune_resolve (null: none)
+  const void *pre_fn[4] = {nullptr, nullptr, nullptr, nullptr};
+  bool pre_resolve_global = false;  // ... and the route of that prune_resolve_kernel: its arrays in global memory (else LDS)
   int last_cb_rounds = 0;        // scorer hook: launches the last decode through a callback scorer took (ctcd_last_scorer_rounds)
   hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr, ev3 = nullptr;  // decode kernel | vocabulary-prune pass
   bool prune_timed = false;
@@ -1521,6 +1524,11 @@ size_t stream_thi_offset(long long cap_frames, int beam) {
   return stream_pool_offset(beam) + stream_nodes(cap_frames, beam) * (sizeof(PoolNode) + sizeof(int));
 }
 
+// The cutoff_prob the pre-passes and the workspace are built for.  The reference runs its cumulative cut only when
+// log(cutoff_prob) < 0.0 (decoder_utils.cpp:16,21): not for a negative or NaN cutoff_prob, whose logarithm is NaN, nor for 1 or more.
+// Every such value means "no cumulative cut", which the kernels and make_dims read as cutoff_prob == 1.0.
+double used_cutoff_prob(double cutoff_prob) { return std::log(cutoff_prob) < 0.0 ? cutoff_prob : 1.0; }
+
 Dims make_dims(int beam, int V, int cutoff_top_n, double cutoff_prob, bool lm = false) {
   const bool pruned = cutoff_prob < 1.0 || cutoff_top_n < V;
   Dims d;
@@ -1554,7 +1562,7 @@ const char *ctcd_version(void) { return "ctcdecode_amd 0.1 (gfx950)"; }
 int ctcd_workgroup_lds_bytes(int beam, int V, int cutoff_top_n, double cutoff_prob) {
   if (beam <= 0 || V <= 0 || cutoff_top_n <= 0) return CTCD_EINVAL;
   Work w;
-  const size_t n = carve<0>(w, nullptr, nullptr, make_dims(beam, V, cutoff_top_n, cutoff_prob), nullptr);
+  const size_t n = carve<0>(w, nullptr, nullptr, make_dims(beam, V, cutoff_top_n, used_cutoff_prob(cutoff_prob)), nullptr);
   return n > 0x7fffffffu ? 0x7fffffff : (int)n;
 }
 
@@ -1703,13 +1711,50 @@ extern "C++" {  // (host helpers of the pre-pass launches, one template instanti
 // the element size of an input dtype, and the alignment the workgroup pre-pass kernels need of a row base (four elements per load)
 static size_t in_elem_bytes(int dt) { return dt == CTCD_DTYPE_F32 ? 4 : 2; }
 
-// the log-softmax kernels of one input dtype
-template <int DT> static const void *lsm_wg_fn(int V) {
-  return V <= 1024 ? (const void *)log_softmax_rows_wg_kernel<1, DT> : V <= 2048 ? (const void *)log_softmax_rows_wg_kernel<2, DT>
-       : V <= 4096 ? (const void *)log_softmax_rows_wg_kernel<4, DT> : V <= 10240 ? (const void *)log_softmax_rows_wg_kernel<10, DT>
-       : (const void *)log_softmax_rows_wg_kernel<16, DT>;
+// Every pre-pass instantiation the build compiles, one row each: the kernel (CTCD_PP_*, include/ctcdecode_amd.h), its size parameter
+// (F4 of the workgroup kernels, R of prune_rows_kernel, else 0), REG of prune_rows_wg_kernel (else 0), the input dtype, and the largest
+// V the dispatch sends to it (0: no bound).  The dispatch picks from this table (pp_pick: the first row that takes V) and
+// ctcd_debug_last_prepass reports from it, so the two cannot disagree.
+struct PrepassEntry { const void *fn; int32_t kernel, a, b, dt, vmax; };
+#define CTC_PP(K, A, B, DT, VMAX, ...) {(const void *)__VA_ARGS__, K, A, B, DT, VMAX}
+#define CTC_PP_DT(DT)                                                                                                                    \
+  CTC_PP(CTCD_PP_PROB_TO_LOG, 0, 0, DT, 0, prob_to_log_kernel<DT>), CTC_PP(CTCD_PP_LSM_WAVE, 0, 0, DT, 0, log_softmax_rows_kernel<DT>),  \
+  CTC_PP(CTCD_PP_LSM_WG, 1, 0, DT, 1024, log_softmax_rows_wg_kernel<1, DT>), CTC_PP(CTCD_PP_LSM_WG, 2, 0, DT, 2048, log_softmax_rows_wg_kernel<2, DT>), \
+  CTC_PP(CTCD_PP_LSM_WG, 4, 0, DT, 4096, log_softmax_rows_wg_kernel<4, DT>), CTC_PP(CTCD_PP_LSM_WG, 10, 0, DT, 10240, log_softmax_rows_wg_kernel<10, DT>), \
+  CTC_PP(CTCD_PP_LSM_WG, 16, 0, DT, 0, log_softmax_rows_wg_kernel<16, DT>),                                                              \
+  CTC_PP(CTCD_PP_PRUNE_ROWS, 1, 0, DT, 64, prune_rows_kernel<1, DT>), CTC_PP(CTCD_PP_PRUNE_ROWS, 4, 0, DT, 256, prune_rows_kernel<4, DT>),   \
+  CTC_PP(CTCD_PP_PRUNE_ROWS, 16, 0, DT, 1024, prune_rows_kernel<16, DT>), CTC_PP(CTCD_PP_PRUNE_ROWS, 64, 0, DT, 4096, prune_rows_kernel<64, DT>), \
+  CTC_PP(CTCD_PP_PRUNE_ROWS, 160, 0, DT, 10240, prune_rows_kernel<160, DT>), CTC_PP(CTCD_PP_PRUNE_ROWS, 0, 0, DT, 0, prune_rows_kernel<0, DT>), \
+  CTC_PP(CTCD_PP_PRUNE_WG, 1, 0, DT, 1024, prune_rows_wg_kernel<1, false, DT>), CTC_PP(CTCD_PP_PRUNE_WG, 2, 0, DT, 2048, prune_rows_wg_kernel<2, false, DT>), \
+  CTC_PP(CTCD_PP_PRUNE_WG, 4, 0, DT, 4096, prune_rows_wg_kernel<4, false, DT>), CTC_PP(CTCD_PP_PRUNE_WG, 10, 0, DT, 10240, prune_rows_wg_kernel<10, false, DT>), \
+  CTC_PP(CTCD_PP_PRUNE_WG, 16, 0, DT, 0, prune_rows_wg_kernel<16, false, DT>),                                                           \
+  /* (the row held in registers between the two looks at it: V <= 10240; beyond, the registers run out) */                              \
+  CTC_PP(CTCD_PP_PRUNE_WG, 1, 1, DT, 1024, prune_rows_wg_kernel<1, true, DT>), CTC_PP(CTCD_PP_PRUNE_WG, 2, 1, DT, 2048, prune_rows_wg_kernel<2, true, DT>), \
+  CTC_PP(CTCD_PP_PRUNE_WG, 4, 1, DT, 4096, prune_rows_wg_kernel<4, true, DT>), CTC_PP(CTCD_PP_PRUNE_WG, 10, 1, DT, 10240, prune_rows_wg_kernel<10, true, DT>), \
+  CTC_PP(CTCD_PP_PRUNE_LOGITS, 1, 0, DT, 1024, prune_logits_wg_kernel<1, DT>), CTC_PP(CTCD_PP_PRUNE_LOGITS, 2, 0, DT, 2048, prune_logits_wg_kernel<2, DT>), \
+  CTC_PP(CTCD_PP_PRUNE_LOGITS, 4, 0, DT, 4096, prune_logits_wg_kernel<4, DT>), CTC_PP(CTCD_PP_PRUNE_LOGITS, 10, 0, DT, 10240, prune_logits_wg_kernel<10, DT>), \
+  CTC_PP(CTCD_PP_PRUNE_LOGITS, 16, 0, DT, 0, prune_logits_wg_kernel<16, DT>), CTC_PP(CTCD_PP_RESOLVE, 0, 0, DT, 0, prune_resolve_kernel<DT>)
+static const PrepassEntry kPrepass[] = {
+  CTC_PP_DT(kInF32), CTC_PP_DT(kInF16), CTC_PP_DT(kInBF16),
+  CTC_PP(CTCD_PP_WIDEN, 0, 0, kInF16, 0, widen_rows_kernel<kInF16>), CTC_PP(CTCD_PP_WIDEN, 0, 0, kInBF16, 0, widen_rows_kernel<kInBF16>),
+};
+#undef CTC_PP_DT
+#undef CTC_PP
+// the first row of kernel `k` with REG `b` for dtype `dt` that takes V; null: none
+static const PrepassEntry *pp_pick(int k, int b, int dt, int V) {
+  for (const PrepassEntry &e : kPrepass)
+    if (e.kernel == k && e.b == b && e.dt == dt && (e.vmax == 0 || V <= e.vmax)) return &e;
+  return nullptr;
 }
-template <int DT> static const void *lsm_wave_fn() { return (const void *)log_softmax_rows_kernel<DT>; }
+static const PrepassEntry *pp_find(const void *fn) {
+  for (const PrepassEntry &e : kPrepass)
+    if (e.fn == fn) return &e;
+  return nullptr;
+}
+
+// the log-softmax kernels of one input dtype
+template <int DT> static const void *lsm_wg_fn(int V) { return pp_pick(CTCD_PP_LSM_WG, 0, DT, V)->fn; }
+template <int DT> static const void *lsm_wave_fn() { return pp_pick(CTCD_PP_LSM_WAVE, 0, DT, 0)->fn; }
 template <int DT>
 static int launch_log_softmax_t(ctcd_decoder *d, const float *in, float *out, long long rows, const int32_t *lens, int T, int V, hipStream_t stream) {
   const uint64_t *tb = (const uint64_t *)d->tables.p;
@@ -1717,8 +1762,10 @@ static int launch_log_softmax_t(ctcd_decoder *d, const float *in, float *out, lo
   if (V % 4 == 0 && V > 256 && V <= 16384 && (((uintptr_t)in & (4 * in_elem_bytes(DT) - 1)) | ((uintptr_t)out & 15)) == 0 && !d->no_fused_logits) {
     const dim3 grid((unsigned)std::min<long long>(rows, 256 * 32));
     HIP_TRY(hipLaunchKernel(lsm_wg_fn<DT>(V), grid, dim3(256), args, 0, stream));
+    d->pre_fn[1] = lsm_wg_fn<DT>(V);
   } else {
     HIP_TRY(hipLaunchKernel(lsm_wave_fn<DT>(), dim3((unsigned)std::min<long long>((rows + 3) / 4, 256 * 64)), dim3(256), args, 0, stream));
+    d->pre_fn[1] = lsm_wave_fn<DT>();
   }
   return CTCD_OK;
 }
@@ -1733,38 +1780,55 @@ static int launch_log_softmax(ctcd_decoder *d, const float *in, float *out, long
 }
 
 // The elementwise pre-passes into the decoder's workspace: prob -> log (to_log), or half rows widened as they are.
-static int launch_elementwise(const float *in, float *out, size_t n, const int32_t *lens, int T, int V, hipStream_t stream, int dt, bool to_log) {
+static int launch_elementwise(ctcd_decoder *d, const float *in, float *out, size_t n, const int32_t *lens, int T, int V, hipStream_t stream, int dt,
+                              bool to_log) {
   const int blocks = (int)std::min<size_t>((n + 255) / 256, 4096);
-  const void *fn = to_log ? (dt == CTCD_DTYPE_F16 ? (const void *)prob_to_log_kernel<kInF16> : dt == CTCD_DTYPE_BF16 ? (const void *)prob_to_log_kernel<kInBF16>
-                                                                                                                    : (const void *)prob_to_log_kernel<kInF32>)
-                          : dt == CTCD_DTYPE_F16 ? (const void *)widen_rows_kernel<kInF16> : (const void *)widen_rows_kernel<kInBF16>;
+  const PrepassEntry *e = pp_pick(to_log ? CTCD_PP_PROB_TO_LOG : CTCD_PP_WIDEN, 0, dt, V);
+  if (!e) return fail(CTCD_EINTERNAL, "no elementwise pre-pass for this input dtype");
+  const void *fn = e->fn;
   void *args[] = {(void *)&in, (void *)&out, (void *)&n, (void *)&lens, (void *)&T, (void *)&V};
   HIP_TRY(hipLaunchKernel(fn, dim3(blocks), dim3(256), args, 0, stream));
   HIP_TRY(hipGetLastError());
+  d->pre_fn[0] = fn;
   return CTCD_OK;
 }
 
 // The vocabulary-prune kernels for one input dtype (decode_common picks among them by shape)
 struct PruneFns { const void *rows, *wg, *wg_reg, *logits, *resolve; };
-template <int DT>
-static PruneFns prune_fns(int V) {
+static PruneFns prune_fns(int dt, int V) {
   PruneFns f;
-  f.rows = V <= 64 ? (const void *)prune_rows_kernel<1, DT> : V <= 256 ? (const void *)prune_rows_kernel<4, DT>
-           : V <= 1024 ? (const void *)prune_rows_kernel<16, DT> : V <= 4096 ? (const void *)prune_rows_kernel<64, DT>
-           : V <= 10240 ? (const void *)prune_rows_kernel<160, DT> : (const void *)prune_rows_kernel<0, DT>;
-  f.wg = V <= 1024 ? (const void *)prune_rows_wg_kernel<1, false, DT> : V <= 2048 ? (const void *)prune_rows_wg_kernel<2, false, DT>
-         : V <= 4096 ? (const void *)prune_rows_wg_kernel<4, false, DT> : V <= 10240 ? (const void *)prune_rows_wg_kernel<10, false, DT>
-         : (const void *)prune_rows_wg_kernel<16, false, DT>;
-  // (the row held in registers between the two looks at it: V <= 10240; beyond, the registers run out)
-  f.wg_reg = V <= 1024 ? (const void *)prune_rows_wg_kernel<1, true, DT> : V <= 2048 ? (const void *)prune_rows_wg_kernel<2, true, DT>
-             : V <= 4096 ? (const void *)prune_rows_wg_kernel<4, true, DT> : V <= 10240 ? (const void *)prune_rows_wg_kernel<10, true, DT> : f.wg;
-  f.logits = V <= 1024 ? (const void *)prune_logits_wg_kernel<1, DT> : V <= 2048 ? (const void *)prune_logits_wg_kernel<2, DT>
-             : V <= 4096 ? (const void *)prune_logits_wg_kernel<4, DT> : V <= 10240 ? (const void *)prune_logits_wg_kernel<10, DT>
-             : (const void *)prune_logits_wg_kernel<16, DT>;
-  f.resolve = (const void *)prune_resolve_kernel<DT>;
+  f.rows = pp_pick(CTCD_PP_PRUNE_ROWS, 0, dt, V)->fn;
+  f.wg = pp_pick(CTCD_PP_PRUNE_WG, 0, dt, V)->fn;
+  const PrepassEntry *reg = pp_pick(CTCD_PP_PRUNE_WG, 1, dt, V);  // (none beyond 10240 labels: the two-sweep form)
+  f.wg_reg = reg ? reg->fn : f.wg;
+  f.logits = pp_pick(CTCD_PP_PRUNE_LOGITS, 0, dt, V)->fn;
+  f.resolve = pp_pick(CTCD_PP_RESOLVE, 0, dt, V)->fn;
   return f;
 }
 }  // extern "C++"
+
+// What the last call's pre-passes launched, read back from the launched pointers through kPrepass: four stages of {kernel, a, b, dt}.
+int ctcd_debug_last_prepass(const ctcd_decoder *d, int32_t out[CTCD_PREPASS_FIELDS]) {
+  if (!d || !out) return fail(CTCD_EINVAL, "decoder == NULL or out == NULL");
+  for (int s = 0; s < 4; ++s) {
+    int32_t *o = out + 4 * s;
+    o[0] = o[1] = o[2] = o[3] = 0;
+    if (!d->pre_fn[s]) continue;
+    const PrepassEntry *e = pp_find(d->pre_fn[s]);
+    if (!e) return fail(CTCD_EINTERNAL, "the last call launched a pre-pass kernel that is not in the table");
+    o[0] = e->kernel; o[1] = e->a; o[2] = s == 3 ? (d->pre_resolve_global ? 1 : 0) : e->b; o[3] = e->dt;
+  }
+  return CTCD_OK;
+}
+int ctcd_debug_prepass_table(int32_t *out, int cap) {
+  const int n = (int)(sizeof(kPrepass) / sizeof(kPrepass[0]));
+  for (int i = 0; out && i < n && i < cap; ++i) {
+    const PrepassEntry &e = kPrepass[i];
+    int32_t *o = out + 5 * i;
+    o[0] = e.kernel; o[1] = e.a; o[2] = e.b; o[3] = e.dt; o[4] = e.vmax;
+  }
+  return n;
+}
 
 static int decode_common(ctcd_decoder *d, const float *probs, const int32_t *seq_lens, int B, int T, int V, int beam,
                          double cutoff_prob, int cutoff_top_n, int blank_id, int log_input, int32_t *out_tok, int32_t *out_ts,
@@ -1787,6 +1851,7 @@ static int decode_common(ctcd_decoder *d, const float *probs, const int32_t *seq
     if (!sc) d->last_order_items = 0;  // (ctcd_debug_last_launch_order: an empty call has no order)
     return CTCD_OK;
   }
+  cutoff_prob = used_cutoff_prob(cutoff_prob);  // (from here on, < 1.0 <=> the reference's cumulative cut)
   const Dims dims = make_dims(beam, V, cutoff_top_n, cutoff_prob, scorer != nullptr);
   // more than 65535 candidate slots (cutoff_top_n >= V with thousands of labels): the layout with 32-bit slot indices and
   // everything per slot in HBM scratch (workspace level 3) -- the reference has no such limit (decoder_utils.cpp:33-35)
@@ -1898,6 +1963,8 @@ static int decode_common(ctcd_decoder *d, const float *probs, const int32_t *seq
     st_eos = (unsigned char *)db + off_eos;
     seq_lens = (const int32_t *)(db + off_len);
   }
+  // ctcd_debug_last_prepass: what this call's pre-passes launch, recorded as each is queued
+  std::fill(d->pre_fn, d->pre_fn + 4, nullptr);
   // the rows the pre-passes cover (resumed launches of the scorer hook start inside the rows: StreamCall::row_lens)
   const int32_t *pre_lens = (sc && sc->row_lens) ? sc->row_lens : seq_lens;
   // half rows (ctcd_set_input_dtype): the pre-pass kernels read them; `probs` keeps pointing at the caller's rows until a pass has
@@ -1909,7 +1976,7 @@ static int decode_common(ctcd_decoder *d, const float *probs, const int32_t *seq
     // float32 route (raw logits are normalised into the workspace below anyway)
     if ((rc = d->lsm.ensure((size_t)B * T * V * 4))) return rc;
     if (pre_lens) HIP_TRY(hipMemsetAsync(d->lsm.p, 0, (size_t)B * T * V * 4, stream));
-    if ((rc = launch_elementwise(probs, (float *)d->lsm.p, (size_t)B * T * V, pre_lens, T, V, stream, dt, false))) return rc;
+    if ((rc = launch_elementwise(d, probs, (float *)d->lsm.p, (size_t)B * T * V, pre_lens, T, V, stream, dt, false))) return rc;
     probs = (const float *)d->lsm.p;
     dt = CTCD_DTYPE_F32;
   }
@@ -1950,11 +2017,11 @@ static int decode_common(ctcd_decoder *d, const float *probs, const int32_t *seq
     const size_t psm = (size_t)wpb * (3 * (size_t)stride + 2 * kPruneCand) * 4;
     if (psm > (size_t)d->max_lds) return fail(CTCD_EUNSUPPORTED, "cutoff_top_n too large for the prune pass");
     const int blocks = (int)std::min<long long>((rows + wpb - 1) / wpb, 256 * 16);
-    const PruneFns fns = dt == CTCD_DTYPE_F16 ? prune_fns<kInF16>(V) : dt == CTCD_DTYPE_BF16 ? prune_fns<kInBF16>(V) : prune_fns<kInF32>(V);
+    const PruneFns fns = prune_fns(dt, V);
     const void *pfn = fns.rows;
     bool wg_kernel = false;
-    // the bandwidth-shaped variant (half rows: four elements per 8-byte load, the row base 8-byte aligned)
-    if (V % 4 == 0 && V > 256 && V <= 16384 && std::min(cutoff_top_n, V) <= 64 && (dt == CTCD_DTYPE_F32 || ((uintptr_t)probs & 7) == 0)) {
+    // the bandwidth-shaped variant (four elements per load: the row base 16-byte aligned for float32 rows, 8-byte for half rows)
+    if (V % 4 == 0 && V > 256 && V <= 16384 && std::min(cutoff_top_n, V) <= 64 && ((uintptr_t)probs & (4 * in_elem_bytes(dt) - 1)) == 0) {
       wg_kernel = true;
       pfn = fns.wg;
       static const bool reg_rows = getenv("CTCD_PRUNE_REG") ? atoi(getenv("CTCD_PRUNE_REG")) != 0 : true;
@@ -1994,6 +2061,7 @@ static int decode_common(ctcd_decoder *d, const float *probs, const int32_t *seq
     if (d->timing) HIP_TRY(hipEventRecord(d->ev2, stream));
     HIP_TRY(hipLaunchKernel(pfn, dim3(blocks_launch), dim3(wpb * 64), pargs, psm_launch, stream));
     HIP_TRY(hipGetLastError());
+    d->pre_fn[2] = pfn;
     if (d->timing) { HIP_TRY(hipEventRecord(d->ev3, stream)); d->prune_timed = true; }
     // (prune_resolve_kernel keeps positions and counters in 16 bits: the refusal of pruning with more than 32767 labels above is
     //  what guarantees they fit -- said here, next to the launch, so that the two cannot drift apart: ADVICE r4)
@@ -2004,6 +2072,8 @@ static int decode_common(ctcd_decoder *d, const float *probs, const int32_t *seq
     void *rargs[] = {&pa, (void *)&rfar, (void *)&rstride_arg};
     HIP_TRY(hipLaunchKernel(fns.resolve, dim3(rblocks), dim3(kResolveThreads), rargs, in_lds ? rbytes : 0, stream));
     HIP_TRY(hipGetLastError());
+    d->pre_fn[3] = fns.resolve;
+    d->pre_resolve_global = !in_lds;
     // (statistics only: the number of flagged frames travels to page-locked memory behind the kernels; whoever asks for it
     //  -- ctcd_last_prune_flagged_rows -- waits for the stream)
     if (!d->h_flagged) HIP_TRY(hipHostMalloc((void **)&d->h_flagged, 8, hipHostMallocDefault));
@@ -2014,7 +2084,7 @@ static int decode_common(ctcd_decoder *d, const float *probs, const int32_t *seq
     const size_t n = (size_t)B * T * V;
     if ((rc = d->logp.ensure(n * 4))) return rc;
     if (pre_lens) HIP_TRY(hipMemsetAsync(d->logp.p, 0, n * 4, stream));  // frames past an utterance's end stay defined
-    if ((rc = launch_elementwise(probs, (float *)d->logp.p, n, pre_lens, T, V, stream, dt, !log_input))) return rc;
+    if ((rc = launch_elementwise(d, probs, (float *)d->logp.p, n, pre_lens, T, V, stream, dt, !log_input))) return rc;
     logp = (const float *)d->logp.p;
   }
 
@@ -3135,7 +3205,7 @@ static int decode_to_host_locked(ctcd_decoder *d, const float *probs, const int3
   // input has crossed PCIe; the rows follow frame block by frame block on a second stream (the input is [B, T, V]: a
   // block is a strided copy), each block followed by an update of the "frames arrived" counter the kernel's row fetch
   // waits on (beam_core.h decode_utterance).  Hides the 0.5 ms the 30 MB of a configs[1] batch take.
-  const bool pruned_in = cutoff_prob < 1.0 || cutoff_top_n < V;
+  const bool pruned_in = used_cutoff_prob(cutoff_prob) < 1.0 || cutoff_top_n < V;
   // (V <= the workgroup size the launch will use -- decode_common: the caller's, or at least 512 -- so that the kernel
   //  prefetches its rows: ADVICE r3; rows that are not prefetched wait as well since round 4, this keeps the fast form)
   const bool stream_in = !probs_on_device && log_input == 1 && !pruned_in && T >= 128 && T <= 65536 && V <= (d->threads ? d->threads : 512) &&
@@ -3342,6 +3412,7 @@ int ctcd_log_softmax(ctcd_decoder *d, const float *logits, const int32_t *seq_le
     if (x0 < y1 && y0 < x1) return fail(CTCD_EINVAL, "half-precision logits: `out` must not overlap them (in-place is float32 only)");
   }
   d->last_in_dtype = d->in_dtype;
+  std::fill(d->pre_fn, d->pre_fn + 4, nullptr);
   return launch_log_softmax(d, logits, out, (long long)B * T, seq_lens, T, V, stream, d->in_dtype);
 }
 

@@ -374,6 +374,26 @@ int ctcd_debug_last_layout(const ctcd_decoder *dec);
  * -1 (CTCD_EINVAL): no launch yet, or a NULL argument (that case alone sets ctcd_last_error); CTCD_EINTERNAL: the launched kernel is
  * not in the build's list (a bug). */
 int ctcd_debug_last_kernel(const ctcd_decoder *dec, int32_t params[7]);
+/* The pre-pass kernels the last call of `dec` launched (tests prove with it that every pre-pass instantiation is reached): four stages
+ * -- elementwise (prob -> log / half rows widened), log_softmax, vocabulary prune, prune_resolve_kernel -- of four words each, {kernel,
+ * a, b, dtype}: kernel one of CTCD_PP_* (CTCD_PP_NONE: the stage launched nothing, and the other three words are 0); a = F4 of the
+ * workgroup kernels, R of prune_rows_kernel, else 0; b = REG of prune_rows_wg_kernel, for prune_resolve_kernel its route (0: arrays in
+ * LDS, 1: in global memory, ctcd_debug_set_prune_resolve), else 0; dtype = the CTCD_DTYPE_* the kernel reads.  A stage is recorded once
+ * its launch is queued; every decode call (and ctcd_log_softmax) that reaches its pre-passes starts with four empty stages.
+ * ctcd_debug_prepass_table: every pre-pass instantiation of the build, five words each {kernel, a, b, dtype, largest V the dispatch sends
+ * to it or 0: no bound}, up to `cap` of them written to `out`; returns their number. */
+#define CTCD_PP_NONE 0
+#define CTCD_PP_PROB_TO_LOG 1   /* prob_to_log_kernel<DT> */
+#define CTCD_PP_WIDEN 2         /* widen_rows_kernel<DT> */
+#define CTCD_PP_LSM_WAVE 3      /* log_softmax_rows_kernel<DT> (one wave per row) */
+#define CTCD_PP_LSM_WG 4        /* log_softmax_rows_wg_kernel<F4, DT> */
+#define CTCD_PP_PRUNE_ROWS 5    /* prune_rows_kernel<R, DT> */
+#define CTCD_PP_PRUNE_WG 6      /* prune_rows_wg_kernel<F4, REG, DT> */
+#define CTCD_PP_PRUNE_LOGITS 7  /* prune_logits_wg_kernel<F4, DT> (raw logits -> candidates) */
+#define CTCD_PP_RESOLVE 8       /* prune_resolve_kernel<DT> */
+#define CTCD_PREPASS_FIELDS 16
+int ctcd_debug_last_prepass(const ctcd_decoder *dec, int32_t out[CTCD_PREPASS_FIELDS]);
+int ctcd_debug_prepass_table(int32_t *out, int cap);
 int ctcd_workgroup_lds_bytes(int beam, int V, int cutoff_top_n, double cutoff_prob); /* LDS one utterance needs (default build) */
 const char *ctcd_last_error(void);
 const char *ctcd_version(void);

@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "ctc_beam_search_decoder.h"
+#include "decoder_utils.h"
 
 // Labels travel as one buffer of NUL-terminated UTF-8 strings (V of them); nullptr = anonymous labels without a space.
 static std::vector<std::string> unpack_labels(const char *labels, int V) {
@@ -73,6 +74,25 @@ extern "C" int ctcref_decode_lm_f32(const float *probs, const int32_t *seq_lens,
                                     int32_t *out_lens, int32_t *n_results) {
   return run_batch(probs, seq_lens, B, T, V, beam, num_processes, cutoff_prob, cutoff_top_n, blank_id, log_input,
                    unpack_labels(labels, V), static_cast<Scorer *>(scorer), out_tokens, out_timesteps, out_scores, out_lens, n_results);
+}
+
+// The reference's own vocabulary prune (decoder_utils.cpp:10-45, get_pruned_log_probs), frame by frame: each float32 row widened to
+// vector<double> as run_batch does (binding.cpp:70-71); per row the number of candidates kept, their labels in the order the
+// reference returns them and their values (float), at row * stride.
+extern "C" int ctcref_pruned_log_probs(const float *rows, long long n_rows, int V, double cutoff_prob, int cutoff_top_n, int log_input,
+                                       int stride, int32_t *cnt, int32_t *labels, float *values) {
+  std::vector<double> step(V);
+  for (long long r = 0; r < n_rows; ++r) {
+    for (int v = 0; v < V; ++v) step[v] = rows[(size_t)r * V + v];
+    const std::vector<std::pair<size_t, float>> c = get_pruned_log_probs(step, cutoff_prob, (size_t)cutoff_top_n, log_input);
+    if ((int)c.size() > stride) return -1;
+    cnt[r] = (int32_t)c.size();
+    for (size_t i = 0; i < c.size(); ++i) {
+      labels[(size_t)r * stride + i] = (int32_t)c[i].first;
+      values[(size_t)r * stride + i] = c[i].second;
+    }
+  }
+  return 1;
 }
 
 static int run_batch(const float *probs, const int32_t *seq_lens, int B, int T, int V, int beam, int num_processes,

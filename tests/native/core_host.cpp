@@ -266,6 +266,13 @@ extern "C" int ctccore_event_counts(long long *out, int reset) {
   return ctcbeam::EV_COUNT;
 }
 
+// The host twin's vocabulary prune (prune_row above: log-probability rows, pruned configurations only), frame by frame.
+extern "C" void ctccore_prune_rows(const float *rows, long long n_rows, int V, double cutoff_prob, int cutoff_top_n, int stride,
+                                   int32_t *cnt, int32_t *labels, float *values) {
+  for (long long r = 0; r < n_rows; ++r)
+    prune_row(rows + (size_t)r * V, V, cutoff_prob, cutoff_top_n, &cnt[r], &labels[(size_t)r * stride], &values[(size_t)r * stride]);
+}
+
 extern "C" void ctccore_log_softmax_rows(const float *x, long long rows, int V, float *out) {
   for (long long r = 0; r < rows; ++r) {
     const float *xr = x + (size_t)r * V;

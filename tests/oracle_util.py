@@ -23,6 +23,16 @@ def have_reference():
     return os.path.exists(REFERENCE_SO)
 
 
+def have_reference_prune():
+    """oracle/_ref is built AND from a driver that has the per-frame prune (ctcref_pruned_log_probs).  Where the reference's sources are
+    absent, oracle/Makefile cannot rebuild the library, and a copy made from an older driver lacks that entry: the decode is still the
+    reference's, the per-frame prune then comes from the restatement (pinned to the reference by tests/test_oracle.py, live or through
+    its recorded digests)."""
+    if not have_reference():
+        return False
+    return hasattr(ctypes.CDLL(REFERENCE_SO), "ctcref_pruned_log_probs")
+
+
 def _ptr(a, t):
     return a.ctypes.data_as(t) if a is not None else None
 
@@ -125,6 +135,54 @@ def decode(probs, seq_lens=None, beam=100, cutoff_prob=1.0, cutoff_top_n=40, bla
     if want_stats:
         out["stats"] = stats
     return out
+
+
+def pruned_rows(x, cutoff_prob, top_n, log_input=True, which="restated"):
+    """The vocabulary prune of decoder_utils.cpp:10-45 (get_pruned_log_probs) applied to every row of ``x`` (float32 [..., V], widened
+    to double as binding.cpp:70-71 does) -> (counts [R], labels [R, stride], values [R, stride] float32), R = the number of rows,
+    stride = min(top_n, V); entries at or beyond a row's count are 0.
+
+    which: ``reference`` = the reference's own function (oracle/_ref), ``restated`` = oracle/ctc_oracle.cpp's prune_vocab, ``host`` =
+    the host twin of the product's core (tests/native/core_host.cpp prune_row: log-probability rows of a pruned configuration only)."""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    V = x.shape[-1]
+    R = x.size // V if V else 0
+    stride = min(int(top_n), V)
+    cnt = np.zeros((R,), np.int32)
+    lab = np.zeros((R, stride), np.int32)
+    val = np.zeros((R, stride), np.float32)
+    args = (_ptr(x, _f32p), ctypes.c_longlong(R), V, ctypes.c_double(cutoff_prob), int(top_n))
+    outs = (stride, _ptr(cnt, _i32p), _ptr(lab, _i32p), _ptr(val, _f32p))
+    if which == "host":
+        assert log_input and (0.0 <= cutoff_prob < 1.0 or top_n < V), "the host twin prunes log-probability rows of pruned configurations"
+        ctypes.CDLL(build_core_host()).ctccore_prune_rows(*args, *outs)
+        return cnt, lab, val
+    if which == "restated":
+        fn = ctypes.CDLL(RESTATED_SO).ctcoracle_pruned_log_probs
+    elif which == "reference":
+        if not have_reference_prune():
+            raise RuntimeError("oracle/_ref/libctcref.so has no ctcref_pruned_log_probs (built from an older oracle/ref_driver.cpp)")
+        fn = ctypes.CDLL(REFERENCE_SO).ctcref_pruned_log_probs
+    else:
+        raise ValueError(which)
+    rc = fn(*args, int(bool(log_input)), *outs)
+    if rc != 1:
+        raise RuntimeError("checker returned %d" % rc)
+    return cnt, lab, val
+
+
+def assert_same_pruned(got, want, what="", rows=None):
+    """Bit-exact comparison of two per-frame prune outputs (counts, labels, values) over ``rows`` (default: all); entries at or beyond
+    a frame's count are not compared."""
+    gc, gl, gv = got
+    wc, wl, wv = want
+    rows = range(len(wc)) if rows is None else rows
+    for r in rows:
+        n = int(wc[r])
+        assert int(gc[r]) == n, "%s frame %d: %d candidates kept, want %d" % (what, r, int(gc[r]), n)
+        assert np.array_equal(gl[r, :n], wl[r, :n]), "%s frame %d: labels differ at %s" % (what, r, np.nonzero(gl[r, :n] != wl[r, :n])[0][:6])
+        d = gv[r, :n].view(np.uint32) != wv[r, :n].view(np.uint32)
+        assert not d.any(), "%s frame %d: values differ at %s: %s vs %s" % (what, r, np.nonzero(d)[0][:4], gv[r, :n][d][:4], wv[r, :n][d][:4])
 
 
 def assert_same(a, b, what=""):

@@ -26,6 +26,7 @@ def test_library_exports_every_declared_symbol():
     assert "ctcd_beam_decode" in names and "ctcd_beam_decode_host" in names and len(names) >= 9
     # the hook the GPU tests prove with which workspace layout (which kernel) a decode ran
     assert "ctcd_debug_last_layout" in names and "ctcd_debug_last_kernel" in names
+    assert "ctcd_debug_last_prepass" in names and "ctcd_debug_prepass_table" in names
     from ctcdecode_amd import _native
 
     assert set(names) <= set(_native.SYMBOLS), sorted(set(names) - set(_native.SYMBOLS))
@@ -48,6 +49,40 @@ def test_kernel_matrix_covers_every_instantiation():
     assert len(set(cases)) == len(cases), "two matrix cases expect the same kernel"
     assert set(cases) == set(listed), (sorted(set(listed) - set(cases)), sorted(set(cases) - set(listed)))
     assert len({km.case_id(c) for c in km.CASES}) == len(cases)
+
+
+def test_prepass_matrix_covers_every_instantiation():
+    """tests/test_gpu_prepass_matrix.py has one case per pre-pass instantiation the build compiles (the table the dispatch picks from,
+    ctcd_debug_prepass_table) and one for the global-memory route of prune_resolve_kernel per dtype: an instantiation added without a
+    case, or a case whose kernel no longer exists, fails here.  Each case's target is among the kernels the dispatch prescribes for it."""
+    import __graft_entry__ as g
+
+    g.build()
+    import ctcdecode_amd
+    import prepass_matrix_util as pm
+
+    table = ctcdecode_amd.prepass_table()
+    listed = [t[:4] for t in table]
+    assert len(listed) == 86 and len(set(listed)) == len(listed), len(listed)
+    counts = {}
+    for k, a, b, dt in listed:
+        counts[k] = counts.get(k, 0) + 1
+    assert counts == dict(prob_to_log=3, widen=2, lsm_wave=3, lsm_wg=15, prune_rows=18, prune_wg=27, prune_logits=15, resolve=3), counts
+    targets = [c["target"] for c in pm.CASES]
+    assert len(targets) == 89 and len(set(targets)) == len(targets), "two matrix cases have the same target"
+    want = set(listed) | {("resolve", 0, 1, dt) for dt in pm.DTYPES}
+    assert set(targets) == want, (sorted(want - set(targets)), sorted(set(targets) - want))
+    assert len({pm.case_id(c) for c in pm.CASES}) == len(targets)
+    for c in pm.CASES:
+        assert c["target"] in pm.expected_prepass(c).values(), pm.case_id(c)
+    # the size bounds of the table are the ones the case table restates (expected_prepass)
+    for k, a, b, dt, vmax in table:
+        if k in ("lsm_wg", "prune_wg", "prune_logits"):
+            assert vmax == {1: 1024, 2: 2048, 4: 4096, 10: 10240, 16: 0}[a], (k, a, vmax)
+        elif k == "prune_rows":
+            assert vmax == {1: 64, 4: 256, 16: 1024, 64: 4096, 160: 10240, 0: 0}[a], (k, a, vmax)
+        else:
+            assert vmax == 0, (k, vmax)
 
 
 def test_python_signature_mirrors_reference():

@@ -286,3 +286,18 @@ def test_log_softmax_host_twin_is_a_log_softmax():
         ok = np.isfinite(want)
         assert np.allclose(y[ok], want[ok], rtol=0, atol=2e-6 * (1 + np.log(V)))
         assert np.all(np.isneginf(y[~ok]))
+
+
+def test_core_negative_cutoff_prob_makes_no_cumulative_cut():
+    """A negative or NaN cutoff_prob: log(cutoff_prob) is NaN, so the reference makes no cumulative cut (decoder_utils.cpp:16,21) and
+    keeps cutoff_top_n candidates per frame -- the decode equals the one with cutoff_prob 1.0, and the oracle's."""
+    lp = ou.synth_logprobs(2, 60, 50, 31)
+    kw = dict(beam=10, cutoff_top_n=12)
+    plain = ou.decode_core_host(lp, cutoff_prob=1.0, **kw)
+    for cp in (-0.5, float("nan")):
+        got = ou.decode_core_host(lp, cutoff_prob=cp, **kw)
+        ou.assert_same(got, ou.decode(lp, cutoff_prob=cp, which="reference" if ou.have_reference() else "restated", **kw), "cp %r" % cp)
+        ou.assert_same(got, plain, "cp %r vs 1.0" % cp)
+    # (and a real cut below ln 2 does change it: the comparison above is not vacuous)
+    cut = ou.decode_core_host(lp, cutoff_prob=0.3, **kw)
+    assert not all(np.array_equal(cut[k], plain[k]) for k in ("tokens", "lens", "scores"))

@@ -5,6 +5,8 @@
 (c) the committed fixtures produced by the real reference build (tests/golden, tests/golden/make_golden.py),
 (d) live differential runs against oracle/_ref where it is built, else against its stored results (tests/golden/live).
 """
+import os
+
 import numpy as np
 import pytest
 
@@ -120,3 +122,128 @@ def test_kernel_matrix_overflow_frames_are_not_inf_frames():
             r["scores"][d].view(np.uint32), q["scores"][d].view(np.uint32))
         assert not same, km.case_id(c)
 
+
+
+# ---- the vocabulary prune alone, frame by frame (decoder_utils.cpp:10-45 get_pruned_log_probs): the restatement's prune_vocab and
+# the host twin's prune_row against the reference's own function, bit for bit -- the yardstick of tests/test_gpu_prepass_matrix.py
+PRUNE_CPS = (1.0, 0.99, 0.6, 0.3, 0.0, -0.0, -0.5, 1.5, float("nan"), 5e-324)
+PRUNE_DIGESTS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "live", "pruned_rows.json")
+
+
+def _prune_rows_for(V, log_input, seed):
+    """Rows of every kind the prune must get right: random, ties inside and across the cut (a 0.5 grid), peaky (the cumulative cut
+    stops early), every third label -inf / 0, a frame of -inf / all 0, probabilities near FLT_MIN, rows that do not sum to 1."""
+    rng = np.random.default_rng(seed)
+    rows = []
+    for kind in range(9):
+        z = rng.standard_normal(V) * 2.0
+        if kind == 2:
+            z[rng.integers(0, V)] += 9.0
+        lp = z - z.max() - np.log(np.exp(z - z.max()).sum())
+        if kind == 1:
+            lp = np.round(lp * 2) / 2
+        elif kind == 3:
+            lp = np.round(lp)  # (coarser: long runs of equal values)
+        elif kind == 4:
+            lp[::3] = -np.inf
+        elif kind == 5:
+            lp[:] = -np.inf
+        elif kind == 6:
+            lp = np.log(rng.random(V) * 3.0)  # (sums to about 1.5 V)
+        elif kind == 7:
+            lp = np.log(rng.random(V) * 1e-3)  # (sums to well below 1: the cut runs to cutoff_top_n)
+        elif kind == 8:
+            lp = np.log(rng.random(V) * 4 * np.finfo(np.float32).tiny)  # (probabilities near FLT_MIN, subnormal included)
+            lp[rng.integers(0, V)] = np.log(0.5)
+        rows.append(lp)
+    x = np.array(rows)
+    x = (np.exp(x) if not log_input else x).astype(np.float32)
+    return x
+
+
+def _near_cut_rows(base_cp, log_input, V=70, seed=3):
+    """Rows whose first partial sum log(1 + p0) lands on cutoff_prob: three rows sharing p0 = expm1(base_cp) (as float32), tails of
+    different sizes; -> (rows, [the double the reference's log_sum_exp(0, log p0) gives, and its two neighbours])."""
+    rng = np.random.default_rng(seed)
+    p0 = np.float32(np.expm1(base_cp))
+    rows = np.stack([rng.random(V) * s for s in (1e-9, 1e-4, 1e-2)]).astype(np.float32)
+    rows[:, 5] = p0
+    rows = (np.log(rows) if log_input else rows).astype(np.float32)
+    x0 = np.float64(rows[0, 5]) if log_input else np.log(np.float64(rows[0, 5]))  # (the reference's log p0, from the float32 it reads)
+    c = np.log(np.exp(0.0) + np.exp(x0))  # (decoder_utils.h:47-54 with xmax = 0)
+    cps = [float(np.nextafter(c, -np.inf)), float(c), float(np.nextafter(c, np.inf))]
+    return rows, cps
+
+
+def _prune_cases():
+    out = []
+    for li in (1, 0):
+        for V in (29, 70):
+            x = _prune_rows_for(V, li, 40 + V + li)
+            for cp in PRUNE_CPS:
+                for top_n in (1, 40, 64, 65, V, V + 7):
+                    out.append(("V%d_li%d_cp%r_n%d" % (V, li, cp, top_n), x, cp, top_n, li))
+        for base in (0.6, 0.3):
+            x, cps = _near_cut_rows(base, li)
+            for k, cp in enumerate(cps):
+                for top_n in (1, 3, 40):
+                    out.append(("near%r_%d_li%d_n%d" % (base, k, li, top_n), x, cp, top_n, li))
+    return out
+
+
+def _digest(*arrays):
+    import hashlib
+
+    h = hashlib.sha256()
+    for a in arrays:
+        a = np.ascontiguousarray(a)
+        h.update(repr((a.shape, a.dtype.str)).encode())
+        h.update(a.tobytes())
+    return h.hexdigest()
+
+
+def _prune_digests():
+    """case name -> [input digest, output digest] of the reference's get_pruned_log_probs (tests/golden/make_golden_pruned.py)."""
+    import json
+
+    with open(PRUNE_DIGESTS) as f:
+        return json.load(f)
+
+
+def test_pruned_rows_restatement_and_host_twin_equal_the_reference():
+    """Count, labels in std::sort order, float values: oracle/ctc_oracle.cpp's prune_vocab and the host core's prune_row equal the
+    reference's get_pruned_log_probs bit for bit -- over cutoff_prob 1, 0.99, 0.6, 0.3, +-0, negative, above 1, NaN and subnormal,
+    cutoff_top_n 1 / 40 / 64 / 65 / >= V, log and probability rows, and rows whose first partial sum sits on cutoff_prob.  The
+    reference is oracle/_ref where it is built with the per-frame entry, else its recorded digests (tests/golden/live/pruned_rows.json)."""
+    stored = _prune_digests()
+    cases = _prune_cases()
+    assert set(stored) == {c[0] for c in cases}
+    n_host = 0
+    for name, x, cp, top_n, li in cases:
+        got = ou.pruned_rows(x, cp, top_n, li, which="restated")
+        assert stored[name][0] == _digest(x, np.float64(cp), np.int32(top_n), np.int32(li)), name + ": the recorded digest is of other inputs"
+        if ou.have_reference_prune():
+            want = ou.pruned_rows(x, cp, top_n, li, which="reference")
+            ou.assert_same_pruned(got, want, name)
+            assert stored[name][1] == _digest(*want), name + ": the live reference disagrees with its recorded digest"
+        assert _digest(*got) == stored[name][1], name
+        if li and (0.0 <= cp < 1.0 or top_n < x.shape[-1]):  # (the host twin prunes the log-probability rows of pruned configurations)
+            ou.assert_same_pruned(ou.pruned_rows(x, cp, top_n, li, which="host"), got, name + " host twin")
+            n_host += 1
+    assert n_host > 100
+
+
+def test_pruned_rows_edge_semantics():
+    """What the comparison above pins, spelled out: a negative or NaN cutoff_prob makes no cumulative cut (log of it is NaN); 0 and
+    -0 keep one candidate (log 0 = -inf < 0, and every partial sum is >= 0); cutoff_top_n >= V with no cut keeps all V in label order."""
+    x = _prune_rows_for(70, 1, 5)
+    for cp in (-0.5, float("nan"), 1.5):
+        cnt, lab, _ = ou.pruned_rows(x, cp, 40, True)
+        assert np.all(cnt == 40)
+        cnt, lab, _ = ou.pruned_rows(x, cp, 70, True)
+        assert np.all(cnt == 70) and np.array_equal(lab, np.tile(np.arange(70), (len(x), 1)))
+    for cp in (0.0, -0.0):
+        cnt, _, _ = ou.pruned_rows(x, cp, 40, True)
+        assert np.all(cnt == 1)
+    cnt, _, _ = ou.pruned_rows(x, 5e-324, 40, True)  # (a subnormal cut: a frame of -inf never reaches it, cum stays log 1 = 0)
+    assert cnt[5] == 40 and np.all(np.delete(cnt, 5) == 1)
