@@ -188,6 +188,17 @@ constexpr int kSmallK = 128, kSmallV = 32;  // the class of shapes of the fixed 
 // ctcdecode/__init__.py:26-38) on any vocabulary too large for class 1, i.e. BASELINE configs[3] (V = 10 000).  Same role geometry
 // as class 1 (at most 128 entries: two waves per role); 112 x 42 slots leave room for the 20 KB rank table.
 constexpr int kMidK = 112, kMidVc = 40, kMidV = 10240;
+// The first wide-beam class with a compile-time layout (round 6; the kernel's LAYOUT 3 at BIG == 1): beam <= kWideK over <= kWideV labels,
+// no pruning, no scorer -- BASELINE configs[2]'s decoder (beam 500 over the 29 labels of English characters; the largest beam whose
+// slot keys still fit one workgroup's LDS).  The algorithm is the run-time layout's (SMALLV = 0); only the array addresses are fixed.
+constexpr int kWideK = 500, kWideV = 29;
+// The shapes of these classes (a call that fits one may run the kernel of its compile-time layout) and the Dims those layouts are cut for.
+CTC_HD constexpr Dims fixed_layout_dims(bool lm = false) { return Dims{kSmallK, kSmallV, kSmallV, 1, lm ? 1 : 0}; }
+CTC_HD bool fits_fixed_layout(const Dims &d) { return d.K <= kSmallK && d.V <= kSmallV && d.Vc_max <= kSmallV; }
+CTC_HD constexpr Dims mid_layout_dims() { return Dims{kMidK, kMidV, kMidVc, 1, 0}; }
+CTC_HD bool fits_mid_layout(const Dims &d) { return d.K <= kMidK && d.V <= kMidV && d.Vc_max <= kMidVc && d.use_rank_table && !d.lm; }
+CTC_HD constexpr Dims wide_layout_dims() { return Dims{kWideK, kWideV, kWideV, 0, 0}; }
+CTC_HD bool fits_wide_layout(const Dims &d) { return d.K <= kWideK && d.V <= kWideV && d.Vc_max <= kWideV && !d.use_rank_table && !d.lm; }
 constexpr int kHotCap = 256;    // speculative select (Decoder::kSpec): capacity of the frame's hot list (keys at or above the predicted threshold)
 // (round 5: 24 -> 12.  The tail of a range on ONE lane costs an LDS round trip per access -- 8-18 k clocks for 24 elements --
 //  against ~4 k for one more partition round by the whole workgroup; tie frames decide how long a launch lasts

@@ -39,6 +39,20 @@ using namespace ctcdk;
 #define CTC_X_EXTERN(PROF_, BIG_, LAYOUT_, PRUNED_, NT_, LM_, OCC2_, G_) extern template __global__ void ctcdk::ctc_beam_decode_kernel<PROF_, BIG_, LAYOUT_, PRUNED_, NT_, LM_, OCC2_>(ctcdk::KernelArgs);
 } namespace ctcdk { CTC_KERNEL_LIST(CTC_X_EXTERN) } namespace {
 #undef CTC_X_EXTERN
+// ... and their addresses by template arguments: what decode_common launches for a planned key (launch_plan.h)
+struct KernelEntry {
+  KernelKey key;
+  const void *fn;
+};
+#define CTC_X_ENTRY(PROF_, BIG_, LAYOUT_, PRUNED_, NT_, LM_, OCC2_, G_) \
+  {{PROF_, BIG_, LAYOUT_, PRUNED_, NT_, (int)(LM_), OCC2_}, (const void *)ctc_beam_decode_kernel<PROF_, BIG_, LAYOUT_, PRUNED_, NT_, LM_, OCC2_>},
+const KernelEntry kKernels[] = {CTC_KERNEL_LIST(CTC_X_ENTRY)};
+#undef CTC_X_ENTRY
+const KernelEntry *kernel_entry(const KernelKey &k) {
+  for (const KernelEntry &e : kKernels)
+    if (e.key == k) return &e;
+  return nullptr;
+}
 
 
 // The data of the bit-exact binary64 log / exp (exact_math_f64.h): the vocabulary pruning and the probability -> log
@@ -1337,9 +1351,7 @@ struct ctcd_decoder {
   // last checked launch reported (chains: on), 0 / 1 = forced
   int subtree_mode = -1;
   bool subtree_on = false;       // the automatic choice for the next launch
-  int last_subtree_search = 0;   // what the last launch used
-  int last_layout = -1;          // the workspace layout the last launch used (ctcd_debug_last_layout; -1: none yet)
-  const void *last_fn = nullptr;  // the kernel the last launch used (ctcd_debug_last_kernel; null: none yet)
+  const KernelEntry *last_kernel = nullptr;  // the kernel the last launch used (null: none yet)
   // the pre-pass kernels the last call queued (ctcd_debug_last_prepass): elementwise | log_softmax | prune | prune_resolve (null: none)
   const void *pre_fn[4] = {nullptr, nullptr, nullptr, nullptr};
   bool pre_resolve_global = false;  // ... and the route of that prune_resolve_kernel: its arrays in global memory (else LDS)
@@ -1524,22 +1536,6 @@ size_t stream_thi_offset(long long cap_frames, int beam) {
   return stream_pool_offset(beam) + stream_nodes(cap_frames, beam) * (sizeof(PoolNode) + sizeof(int));
 }
 
-// The cutoff_prob the pre-passes and the workspace are built for.  The reference runs its cumulative cut only when
-// log(cutoff_prob) < 0.0 (decoder_utils.cpp:16,21): not for a negative or NaN cutoff_prob, whose logarithm is NaN, nor for 1 or more.
-// Every such value means "no cumulative cut", which the kernels and make_dims read as cutoff_prob == 1.0.
-double used_cutoff_prob(double cutoff_prob) { return std::log(cutoff_prob) < 0.0 ? cutoff_prob : 1.0; }
-
-Dims make_dims(int beam, int V, int cutoff_top_n, double cutoff_prob, bool lm = false) {
-  const bool pruned = cutoff_prob < 1.0 || cutoff_top_n < V;
-  Dims d;
-  d.K = beam;
-  d.V = V;
-  d.Vc_max = pruned ? (cutoff_top_n < V ? cutoff_top_n : V) : V;
-  d.use_rank_table = pruned ? 1 : 0;
-  d.lm = lm ? 1 : 0;
-  return d;
-}
-
 int check_args(int B, int T, int V, int beam, int cutoff_top_n, int blank_id, const void *probs, const void *tok,
                const void *ts, const void *sc, const void *ln) {
   if (B < 0 || T < 0 || V <= 0 || beam <= 0 || cutoff_top_n <= 0) return fail(CTCD_EINVAL, "B, T >= 0 and V, beam_width, cutoff_top_n > 0 required");
@@ -1648,24 +1644,18 @@ int ctcd_set_subtree_search(ctcd_decoder *d, int mode) {
   d->subtree_mode = mode;
   return CTCD_OK;
 }
-int ctcd_last_subtree_search(const ctcd_decoder *d) { return d ? d->last_subtree_search : -1; }
-int ctcd_debug_last_layout(const ctcd_decoder *d) { return d ? d->last_layout : -1; }
-
-// The template arguments of every instantiation the build compiled, keyed by its address: one entry per CTC_KERNEL_LIST item.
+// (all three read the key of the last launch: recorded once it is queued)
+int ctcd_last_subtree_search(const ctcd_decoder *d) {
+  return d ? (d->last_kernel && (d->last_kernel->key.prof == 3 || d->last_kernel->key.prof == 5)) : -1;
+}
+int ctcd_debug_last_layout(const ctcd_decoder *d) { return d && d->last_kernel ? layout_of(d->last_kernel->key) : -1; }
 int ctcd_debug_last_kernel(const ctcd_decoder *d, int32_t params[7]) {
-  struct Entry { const void *fn; int32_t p[7]; };
-#define CTC_X_ENTRY(PROF_, BIG_, LAYOUT_, PRUNED_, NT_, LM_, OCC2_, G_) \
-  {(const void *)ctc_beam_decode_kernel<PROF_, BIG_, LAYOUT_, PRUNED_, NT_, LM_, OCC2_>, {PROF_, BIG_, LAYOUT_, PRUNED_, NT_, (int)(LM_), OCC2_}},
-  static const Entry tab[] = {CTC_KERNEL_LIST(CTC_X_ENTRY)};
-#undef CTC_X_ENTRY
   if (!d || !params) return fail(CTCD_EINVAL, "decoder == NULL or params == NULL");
-  if (!d->last_fn) return CTCD_EINVAL;  // (no launch yet: ctcd_last_error is left as it was)
-  for (const Entry &e : tab)
-    if (e.fn == d->last_fn) {
-      std::memcpy(params, e.p, sizeof(e.p));
-      return CTCD_OK;
-    }
-  return fail(CTCD_EINTERNAL, "the last launch used a kernel that is not in CTC_KERNEL_LIST");
+  if (!d->last_kernel) return CTCD_EINVAL;  // (no launch yet: ctcd_last_error is left as it was)
+  const KernelKey &k = d->last_kernel->key;
+  const int32_t p[7] = {k.prof, k.big, k.layout, k.pruned, k.nt, k.lm, k.occ2};
+  std::memcpy(params, p, sizeof(p));
+  return CTCD_OK;
 }
 
 int ctcd_set_input_dtype(ctcd_decoder *d, int dtype) {
@@ -1680,30 +1670,6 @@ int ctcd_set_threads(ctcd_decoder *d, int t) {
   if (!d || t < 0 || t > 1024 || (t && (t < 64 || (t & (t - 1))))) return fail(CTCD_EINVAL, "threads must be 0 (automatic) or a power of two in [64, 1024]");
   d->threads = t;
   return CTCD_OK;
-}
-
-// The builds whose kernels ignore KernelArgs::frames_ready (decode_kernel.h kNoStreamedInput) and the twins that poll it.  EVERY
-// instantiation for which kNoStreamedInput holds must be listed here.
-static const void *streamed_input_twin(const void *fn) {
-  struct Pair { const void *plain, *twin; };
-  static const Pair tab[] = {
-#if defined(CTC_QUICK_BUILD) && CTC_QUICK_BUILD == 2
-    {(const void *)ctc_beam_decode_kernel<0, 0, 1, false, 1024, 2>, (const void *)ctc_beam_decode_kernel<4, 0, 1, false, 1024, 2>},
-#elif defined(CTC_QUICK_BUILD) && (CTC_QUICK_BUILD == 3 || CTC_QUICK_BUILD == 4)
-    {nullptr, nullptr},
-#elif defined(CTC_QUICK_BUILD)
-    {(const void *)ctc_beam_decode_kernel<0, 0, 1, false, 1024>, (const void *)ctc_beam_decode_kernel<4, 0, 1, false, 1024>},
-    {(const void *)ctc_beam_decode_kernel<0, 0, 1, false, 1024, false, true>, (const void *)ctc_beam_decode_kernel<4, 0, 1, false, 1024, false, true>},
-#else
-    {(const void *)ctc_beam_decode_kernel<0, 0, 1, false, 1024>, (const void *)ctc_beam_decode_kernel<4, 0, 1, false, 1024>},
-    {(const void *)ctc_beam_decode_kernel<3, 0, 1, false, 1024>, (const void *)ctc_beam_decode_kernel<5, 0, 1, false, 1024>},
-    {(const void *)ctc_beam_decode_kernel<0, 0, 1, false, 1024, false, true>, (const void *)ctc_beam_decode_kernel<4, 0, 1, false, 1024, false, true>},
-    {(const void *)ctc_beam_decode_kernel<0, 0, 1, false, 1024, 2>, (const void *)ctc_beam_decode_kernel<4, 0, 1, false, 1024, 2>},
-#endif
-  };
-  for (const Pair &p : tab)
-    if (p.plain && p.plain == fn) return p.twin;
-  return nullptr;
 }
 
 // log_softmax of every frame (ctcd_log_softmax's definition): long rows by a workgroup each, short ones by a wave each
@@ -1853,55 +1819,17 @@ static int decode_common(ctcd_decoder *d, const float *probs, const int32_t *seq
   }
   cutoff_prob = used_cutoff_prob(cutoff_prob);  // (from here on, < 1.0 <=> the reference's cumulative cut)
   const Dims dims = make_dims(beam, V, cutoff_top_n, cutoff_prob, scorer != nullptr);
-  // more than 65535 candidate slots (cutoff_top_n >= V with thousands of labels): the layout with 32-bit slot indices and
-  // everything per slot in HBM scratch (workspace level 3) -- the reference has no such limit (decoder_utils.cpp:33-35)
-  const bool huge = dims.S_max() > 65535;
-  if ((long long)beam * (dims.Vc_max + 2) > (1LL << 24) - 1)
-    return fail(CTCD_EUNSUPPORTED, "beam_width * (candidates + 2) exceeds 16777215 candidate slots");
-  if (huge && d->profile) return fail(CTCD_EUNSUPPORTED, "the instrumented kernel builds do not include the layout for more than 65535 candidate slots");
-  if (dims.use_rank_table && V > 32767) return fail(CTCD_EUNSUPPORTED, "vocabulary pruning with more than 32767 labels");
-  Work wtmp;
-  size_t far_bytes = 0;
-  // workgroup size (measured): 1024 threads for the usual shapes; below ~1300 candidate slots 512 is marginally better
-  // (fewer idle waves), fewer than that is always slower (the new-children phase wants its own waves)
-  int threads = d->threads;
-  if (threads == 0) threads = (dims.S_max() <= 1300 && !scorer) ? 512 : 1024;
-  // (the LM tier has the fixed-layout kernel at 1024 threads only)
-  const bool fixed = fits_fixed_layout(dims) && !d->no_fixed_layout && (!scorer || threads == 1024);
-  // the second compile-time layout: the pruned default (beam <= 112, cutoff_top_n <= 40) on a vocabulary of up to 10 240 labels
-  const bool fixed2 = !fixed && fits_mid_layout(dims) && !d->no_fixed_layout && !scorer && threads == 1024 && !d->profile;
-  const Dims ldims = fixed ? fixed_layout_dims(scorer != nullptr) : fixed2 ? mid_layout_dims() : dims;
-  // two workgroups per CU (OCC2 build of the fixed-layout kernel): batches that outnumber the CUs, or on request
-  const bool hooked = scorer && scorer->cbl;  // a callback scorer: its own kernel instantiations (beam_core.h CB)
-  const bool occ2 = fixed && threads == 1024 && !d->profile && !hooked && (d->cu_sharing == 1 || (d->cu_sharing < 0 && B > d->cu_count));
-  size_t lds = occ2 ? carve<0, true>(wtmp, nullptr, nullptr, ldims, &far_bytes) : carve<0>(wtmp, nullptr, nullptr, ldims, &far_bytes);
-  bool big = false;
-  int far_level = 1;
-  if (huge) {
-    big = true;
-    far_level = 3;
-    lds = carve<3>(wtmp, nullptr, nullptr, dims, &far_bytes);
-  } else if (lds + 2048 > (size_t)d->max_lds) {  // wide beam: rare-path arrays go to HBM scratch
-    big = true;
-    lds = carve<1>(wtmp, nullptr, nullptr, dims, &far_bytes);
-    if (lds + 2048 > (size_t)d->max_lds) {  // wider still: the slot keys and the rarely read per-entry arrays follow them
-      far_level = 2;
-      lds = carve<2>(wtmp, nullptr, nullptr, dims, &far_bytes);
-    }
-  }
-  // the first wide-beam layout at its compile-time size (decode_kernel.h LAYOUT 3: beam <= 500 over <= 29 labels, no pruning, no scorer)
-  bool wide3 = false;
-#if !defined(CTC_QUICK_BUILD)
-  if (big && far_level == 1 && fits_wide_layout(dims) && !d->no_fixed_layout && !scorer && threads == 1024 && !d->profile) {
-    size_t fb3 = 0;
-    const size_t lds3 = carve<1>(wtmp, nullptr, nullptr, wide_layout_dims(), &fb3);
-    if (lds3 + 2048 <= (size_t)d->max_lds) { wide3 = true; lds = lds3; far_bytes = fb3; }
-  }
-#endif
-  far_bytes = (far_bytes + 255) / 256 * 256;
-  if (lds + 2048 > (size_t)d->max_lds)
-    return fail(CTCD_EUNSUPPORTED, "beam_width * (candidates + 2) needs " + std::to_string(lds) + " B of LDS, more than one workgroup has");
-  if (scorer && d->profile && !d->tl_armed) return fail(CTCD_EUNSUPPORTED, "the phase-timer kernel builds do not include the LM tier (the barrier timeline does)");
+  // the kernel, its workgroup size and its LDS, before anything is queued: a call this build refuses leaves no trace
+  const ScorerKind sk = !scorer ? kNoScorer : scorer->cbl ? kCallbackScorer
+                        : (!scorer->host.char_based && !scorer->host.dict_wide && !d->general_lm_kernel) ? kWordScorer : kGeneralScorer;
+  const LaunchSwitches sw{d->no_fixed_layout, d->profile, d->tl_armed, d->cu_sharing, d->subtree_mode, d->subtree_on};
+  const LaunchPlan plan = plan_launch(dims, B, d->threads, d->max_lds, d->cu_count, sw, sk, frames_ready != nullptr,
+                                      [](const KernelKey &k) { return kernel_entry(k) != nullptr; });
+  if (plan.rc) return fail(plan.rc, plan.msg);
+  const KernelEntry *kernel = kernel_entry(plan.key);  // (plan_launch plans only what the build's list holds)
+  const int threads = plan.threads;
+  size_t lds = plan.lds;
+  const size_t far_bytes = plan.far_bytes;
   if ((rc = d->far.ensure((size_t)B * far_bytes))) return rc;
 
   // outputs: everything outside the valid region is defined as 0
@@ -2145,118 +2073,14 @@ static int decode_common(ctcd_decoder *d, const float *probs, const int32_t *seq
     a.prof = (long long *)d->prof.p;
   }
   a.far = (char *)d->far.p; a.far_stride = (long long)far_bytes;
-  const bool pruned_mode = a.pr_cnt != nullptr;
-  const void *fn;
-#if defined(CTC_QUICK_BUILD) && CTC_QUICK_BUILD == 4
-  if (big || scorer || d->profile || occ2 || !(pruned_mode || (!fixed && !fixed2)))
-    return fail(CTCD_EUNSUPPORTED, "CTC_QUICK_BUILD=4: only the pruned-mode kernels of the compile-time layouts and the run-time layout were compiled");
-  fn = fixed2 ? (const void *)ctc_beam_decode_kernel<0, 0, 2, true, 1024> : fixed && threads == 1024 ? (const void *)ctc_beam_decode_kernel<0, 0, 1, true, 1024>
-       : pruned_mode ? (const void *)ctc_beam_decode_kernel<0, 0, 0, true> : (const void *)ctc_beam_decode_kernel<0, 0, 0, false>;
-  if (fixed && threads != 1024) return fail(CTCD_EUNSUPPORTED, "CTC_QUICK_BUILD=4: 1024 threads");
-#elif defined(CTC_QUICK_BUILD) && CTC_QUICK_BUILD == 2
-  if (big || !fixed || pruned_mode || !scorer || occ2 || threads != 1024 || (d->profile && !d->tl_armed))
-    return fail(CTCD_EUNSUPPORTED, "CTC_QUICK_BUILD=2: only the fixed-layout, no-prune, 1024-thread kernel of the LM tier was compiled");
-  fn = d->profile ? (const void *)ctc_beam_decode_kernel<2, 0, 1, false, 1024, true> : (const void *)ctc_beam_decode_kernel<0, 0, 1, false, 1024, true>;
-  if (!scorer->host.char_based && !scorer->host.dict_wide && !d->general_lm_kernel)
-    fn = d->profile ? (const void *)ctc_beam_decode_kernel<2, 0, 1, false, 1024, 2> : (const void *)ctc_beam_decode_kernel<0, 0, 1, false, 1024, 2>;
-#elif defined(CTC_QUICK_BUILD) && CTC_QUICK_BUILD == 3
-  // Workgroup-size sweep (tools/build_variants.sh nt512:CTC_QUICK_BUILD=3,CTC_QUICK_NT=512; raw_multi.py --threads 512)
-  if (big || !fixed || pruned_mode || scorer || occ2 || threads != CTC_QUICK_NT || d->profile)
-    return fail(CTCD_EUNSUPPORTED, "CTC_QUICK_BUILD=3: only the fixed-layout, no-prune, no-LM kernel with CTC_QUICK_NT threads was compiled (ctcd_set_threads)");
-  fn = (const void *)ctc_beam_decode_kernel<0, 0, 1, false, CTC_QUICK_NT>;
-#elif defined(CTC_QUICK_BUILD)
-  // Experiment builds (tools/build_variants.sh, seconds instead of minutes): only the north-star class kernel and its
-  // barrier-timeline twin exist; everything else is refused.
-  if (big || !fixed || pruned_mode || scorer || threads != 1024 || (d->profile && !d->tl_armed))
-    return fail(CTCD_EUNSUPPORTED, "CTC_QUICK_BUILD: only the fixed-layout, no-prune, no-LM, 1024-thread kernel was compiled");
-  fn = d->profile ? (const void *)ctc_beam_decode_kernel<2, 0, 1, false, 1024> : (const void *)ctc_beam_decode_kernel<0, 0, 1, false, 1024>;
-  if (occ2) fn = (const void *)ctc_beam_decode_kernel<0, 0, 1, false, 1024, false, true>;
-#else
-#define CTC_PICK(PROF_)                                                                                                  \
-  (big ? (pruned_mode ? (const void *)ctc_beam_decode_kernel<PROF_, 1, 0, true> : (const void *)ctc_beam_decode_kernel<PROF_, 1, 0, false>)    \
-       : fixed ? (pruned_mode ? (const void *)ctc_beam_decode_kernel<PROF_, 0, 1, true> : (const void *)ctc_beam_decode_kernel<PROF_, 0, 1, false>) \
-               : (pruned_mode ? (const void *)ctc_beam_decode_kernel<PROF_, 0, 0, true> : (const void *)ctc_beam_decode_kernel<PROF_, 0, 0, false>))
-  fn = d->profile ? CTC_PICK(1) : CTC_PICK(0);
-  if (big && far_level == 3) fn = pruned_mode ? (const void *)ctc_beam_decode_kernel<0, 3, 0, true> : (const void *)ctc_beam_decode_kernel<0, 3, 0, false>;
-  if (big && far_level == 2) {  // the widest beams: their own instantiation (every workspace array keeps a static address space)
-    if (d->profile) return fail(CTCD_EUNSUPPORTED, "the instrumented kernel builds do not include the widest-beam layout");
-    fn = pruned_mode ? (const void *)ctc_beam_decode_kernel<0, 2, 0, true> : (const void *)ctc_beam_decode_kernel<0, 2, 0, false>;
-  }
-  if (!d->profile && big && far_level == 1 && threads == 1024)  // wide beams at the usual workgroup size: folded into the code as well
-    fn = pruned_mode ? (const void *)ctc_beam_decode_kernel<0, 1, 0, true, 1024> : (const void *)ctc_beam_decode_kernel<0, 1, 0, false, 1024>;
-  if (!d->profile && fixed && !big && threads == 1024)  // the usual case: workgroup size folded into the code
-    fn = pruned_mode ? (const void *)ctc_beam_decode_kernel<0, 0, 1, true, 1024> : (const void *)ctc_beam_decode_kernel<0, 0, 1, false, 1024>;
-  d->last_subtree_search = 0;
-  if (!d->profile && fixed && !big && threads == 1024 && !scorer && !occ2 && (d->subtree_mode == 1 || (d->subtree_mode < 0 && d->subtree_on))) {
-    // chain-shaped beams (blank-dominated rows: what acoustic models emit): the build whose phase A1 searches four subtrees per wave
-    fn = pruned_mode ? (const void *)ctc_beam_decode_kernel<3, 0, 1, true, 1024> : (const void *)ctc_beam_decode_kernel<3, 0, 1, false, 1024>;
-    d->last_subtree_search = 1;
-  }
-  if (occ2) fn = pruned_mode ? (const void *)ctc_beam_decode_kernel<0, 0, 1, true, 1024, false, true> : (const void *)ctc_beam_decode_kernel<0, 0, 1, false, 1024, false, true>;
-  if (fixed2 && !big) fn = (const void *)ctc_beam_decode_kernel<0, 0, 2, true, 1024>;
-  if (wide3) fn = (const void *)ctc_beam_decode_kernel<0, 1, 3, false, 1024>;
-  if (d->profile && d->tl_armed) {  // the timeline build exists for the north-star class of shapes and for the first wide-beam layout
-    if (threads != 1024) return fail(CTCD_EUNSUPPORTED, "barrier timeline: 1024 threads per workgroup (the product configuration)");
-    if (big && far_level == 1 && !pruned_mode) {
-      fn = (const void *)ctc_beam_decode_kernel<2, 1, 0, false, 1024>;  // (a quarter of the stamps: its LDS is nearly full)
-    } else {
-      if (big || !fixed || pruned_mode) return fail(CTCD_EUNSUPPORTED, "barrier timeline: beam <= 128 and <= 32 labels, or the first wide-beam layout; no pruning");
-      fn = (const void *)ctc_beam_decode_kernel<2, 0, 1, false, 1024>;
-    }
-  }
-#undef CTC_PICK
-  if (scorer) {
-    fn = pruned_mode ? (const void *)ctc_beam_decode_kernel<0, 0, 0, true, 0, true> : (const void *)ctc_beam_decode_kernel<0, 0, 0, false, 0, true>;
-    if (fixed)  // the usual class of shapes: compile-time workspace layout and workgroup size, as without a scorer
-      fn = pruned_mode ? (const void *)ctc_beam_decode_kernel<0, 0, 1, true, 1024, true> : (const void *)ctc_beam_decode_kernel<0, 0, 1, false, 1024, true>;
-    if (occ2) fn = pruned_mode ? (const void *)ctc_beam_decode_kernel<0, 0, 1, true, 1024, true, true> : (const void *)ctc_beam_decode_kernel<0, 0, 1, false, 1024, true, true>;
-    // word models over at most 64 labels (the usual scorer): the instantiations without the character-model and
-    // wide-dictionary branches (-3.6 % per frame; CTCD_GENERAL_LM_KERNEL=1 keeps the general ones: tests run both)
-    if (fixed && !big && !scorer->host.char_based && !scorer->host.dict_wide && !d->general_lm_kernel) {
-      fn = pruned_mode ? (const void *)ctc_beam_decode_kernel<0, 0, 1, true, 1024, 2> : (const void *)ctc_beam_decode_kernel<0, 0, 1, false, 1024, 2>;
-      if (occ2) fn = pruned_mode ? (const void *)ctc_beam_decode_kernel<0, 0, 1, true, 1024, 2, true> : (const void *)ctc_beam_decode_kernel<0, 0, 1, false, 1024, 2, true>;
-    }
-    // wide beams: the scorer's per-entry state moves to the HBM scratch with the other rare-path arrays (a capability, not a fast path)
-    if (big && far_level == 3) fn = pruned_mode ? (const void *)ctc_beam_decode_kernel<0, 3, 0, true, 0, true> : (const void *)ctc_beam_decode_kernel<0, 3, 0, false, 0, true>;
-    else if (big) fn = far_level == 2 ? (pruned_mode ? (const void *)ctc_beam_decode_kernel<0, 2, 0, true, 0, true> : (const void *)ctc_beam_decode_kernel<0, 2, 0, false, 0, true>)
-                                 : (pruned_mode ? (const void *)ctc_beam_decode_kernel<0, 1, 0, true, 0, true> : (const void *)ctc_beam_decode_kernel<0, 1, 0, false, 0, true>);
-    if (hooked) {
-      if (d->profile) return fail(CTCD_EUNSUPPORTED, "the instrumented kernel builds do not include the scorer hook");
-      fn = fixed ? (pruned_mode ? (const void *)ctc_beam_decode_kernel<0, 0, 1, true, 1024, 3> : (const void *)ctc_beam_decode_kernel<0, 0, 1, false, 1024, 3>)
-                 : (pruned_mode ? (const void *)ctc_beam_decode_kernel<0, 0, 0, true, 0, 3> : (const void *)ctc_beam_decode_kernel<0, 0, 0, false, 0, 3>);
-      // wide beams (round 6: the reference's scorer pointer works for any beam, binding.cpp:122-140): the hook's builds of the three wide-beam layouts
-      if (big && far_level == 3) fn = pruned_mode ? (const void *)ctc_beam_decode_kernel<0, 3, 0, true, 0, 3> : (const void *)ctc_beam_decode_kernel<0, 3, 0, false, 0, 3>;
-      else if (big) fn = far_level == 2 ? (pruned_mode ? (const void *)ctc_beam_decode_kernel<0, 2, 0, true, 0, 3> : (const void *)ctc_beam_decode_kernel<0, 2, 0, false, 0, 3>)
-                                   : (pruned_mode ? (const void *)ctc_beam_decode_kernel<0, 1, 0, true, 0, 3> : (const void *)ctc_beam_decode_kernel<0, 1, 0, false, 0, 3>);
-    }
-    if (d->profile && d->tl_armed) {  // (shape conditions checked above)
-      if (!fixed) return fail(CTCD_EUNSUPPORTED, "barrier timeline: beam <= 128, <= 32 labels");
-      fn = (const void *)ctc_beam_decode_kernel<2, 0, 1, false, 1024, true>;
-      if (!scorer->host.char_based && !scorer->host.dict_wide && !d->general_lm_kernel) fn = (const void *)ctc_beam_decode_kernel<2, 0, 1, false, 1024, 2>;
-    }
-  }
-#endif
-  // streamed input (a.frames_ready: the host-tensor entry point feeds the rows while the kernel runs): the north-star class's default
-  // builds do not poll for rows (decode_kernel.h kNoStreamedInput) -- their twins do.  The mapping lives HERE, behind every branch of the
-  // selection above (it used to be repeated per branch; a branch without it would decode rows that have not crossed PCIe).
-  if (a.frames_ready) {
-    const void *twin = streamed_input_twin(fn);
-    if (twin) fn = twin;
-#if defined(CTC_QUICK_BUILD) && (CTC_QUICK_BUILD == 3 || CTC_QUICK_BUILD == 4)
-    else return fail(CTCD_EUNSUPPORTED, "this experiment build has no kernels that take streamed input");
-#endif
-  }
-  // the workspace layout of the kernel chosen above (include/ctcdecode_amd.h ctcd_debug_last_layout), in the order the selection
-  // lets one override another: the HBM-scratch levels over everything but LAYOUT 3, LAYOUT 2 over LAYOUT 1 (they exclude each other)
-  const int layout = wide3 ? 3 : big ? 3 + far_level : fixed2 ? 2 : fixed ? 1 : 0;
   // (CTCD_LDS_FLOOR: experiments with the occupancy the LDS request allows)
   if (d->lds_floor >= 0) lds = std::max(lds, std::min((size_t)d->lds_floor, (size_t)d->max_lds - 2048));
-  HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  HIP_TRY(hipFuncSetAttribute(kernel->fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   // launch order (ctcd_set_launch_order): the one-shot entry points, and every launch of a one-shot decode through a callback scorer
   // (a resumed launch by the frames each utterance has left; the debug copy shows the first launch's order); streaming calls keep
   // batch order.  The order pass runs on the same stream, from the lengths already on the device: nothing waits for the host.
   // (the wide-beam run-time layouts -- BIG kernels at LAYOUT 0 -- take no order: decode_kernel.h kTicket)
-  const bool by_length = d->launch_order == CTCD_ORDER_LENGTH && (!sc || sc->one_shot) && !(big && !wide3);
+  const bool by_length = d->launch_order == CTCD_ORDER_LENGTH && (!sc || sc->one_shot) && takes_launch_order(plan.key);
   const bool first_launch = !sc || !sc->no_clear;
   const bool records = (!sc || sc->one_shot) && first_launch;  // (the launch ctcd_debug_last_launch_order reports)
   a.order = nullptr;
@@ -2281,10 +2105,9 @@ static int decode_common(ctcd_decoder *d, const float *probs, const int32_t *seq
     if (records) HIP_TRY(hipEventRecord(d->ev_order, stream));
   }
   void *kargs[] = {&a};
-  HIP_TRY(hipLaunchKernel(fn, dim3(B), dim3(threads), kargs, lds, stream));
+  HIP_TRY(hipLaunchKernel(kernel->fn, dim3(B), dim3(threads), kargs, lds, stream));
   HIP_TRY(hipGetLastError());
-  d->last_layout = layout;  // (recorded once the launch is queued: a launch that failed leaves the last record)
-  d->last_fn = fn;
+  d->last_kernel = kernel;  // (recorded once the launch is queued: a launch that failed leaves the last record)
   if (d->timing) HIP_TRY(hipEventRecord(d->ev1, stream));
   if (records) d->last_order_items = by_length ? B : 0;  // (set once the launch is queued: a call that failed leaves the last record)
   return CTCD_OK;

@@ -1,7 +1,7 @@
 // decode_kernel.h -- the workgroup execution policy (barriers, wave-level scans and compactions in DPP) and the decode
 // kernel template of the CTC prefix beam search (one workgroup per utterance, beam_core.h inside).  Shared by
-// ctcdecode_amd.hip (host side: picks an instantiation, launches it) and decode_kernels.hip (the instantiations, compiled
-// as several translation units in parallel: ctcdecode_amd/_build.py).
+// ctcdecode_amd.hip (host side: launches the instantiation launch_plan.h picks) and decode_kernels.hip (the instantiations,
+// compiled as several translation units in parallel: ctcdecode_amd/_build.py).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -9,6 +9,7 @@
 #include <cstdint>
 
 #include "beam_core.h"
+#include "launch_plan.h"
 
 namespace ctcdk {
 
@@ -905,26 +906,9 @@ struct KernelArgs {
 };
 
 // LAYOUT: 0 = the workspace is laid out for the call's own beam width / vocabulary (array bases are run-time values);
-// 1 = fixed layout for beam <= kFixedK, vocabulary <= kFixedV: every LDS array sits at a compile-time address, which
-// frees the scalar registers the bases would occupy and folds them into the instructions' offset fields.
-constexpr int kFixedK = ctcbeam::kSmallK, kFixedV = ctcbeam::kSmallV;
-__host__ __device__ constexpr Dims fixed_layout_dims(bool lm = false) { return Dims{kFixedK, kFixedV, kFixedV, 1, lm ? 1 : 0}; }
-__host__ __device__ inline bool fits_fixed_layout(const Dims &d) { return d.K <= kFixedK && d.V <= kFixedV && d.Vc_max <= kFixedV; }
-// LAYOUT 2 (round 6): the second class with a compile-time layout -- beam <= kMidK, <= kMidVc candidates per frame of a pruned
-// vocabulary of <= kMidV labels (beam_core.h kMidK: the reference's default decoder on a large vocabulary, BASELINE configs[3]).
-__host__ __device__ constexpr Dims mid_layout_dims() { return Dims{ctcbeam::kMidK, ctcbeam::kMidV, ctcbeam::kMidVc, 1, 0}; }
-__host__ __device__ inline bool fits_mid_layout(const Dims &d) {
-  return d.K <= ctcbeam::kMidK && d.V <= ctcbeam::kMidV && d.Vc_max <= ctcbeam::kMidVc && d.use_rank_table && !d.lm;
-}
-
-// LAYOUT 3 (round 6): the first wide-beam layout (BIG == 1) at a compile-time size -- beam <= kWideK over <= kWideV labels, no pruning, no
-// scorer: BASELINE configs[2]'s decoder (beam 500 over the 29 labels of English characters; the largest beam whose slot keys still fit one
-// workgroup's LDS).  The algorithm is the run-time layout's (beam_core.h SMALLV = 0); what changes is that every LDS array sits at an
-// address the instructions can hold, as in LAYOUT 1.
-constexpr int kWideK = 500, kWideV = 29;
-__host__ __device__ constexpr Dims wide_layout_dims() { return Dims{kWideK, kWideV, kWideV, 0, 0}; }
-__host__ __device__ inline bool fits_wide_layout(const Dims &d) { return d.K <= kWideK && d.V <= kWideV && d.Vc_max <= kWideV && !d.use_rank_table && !d.lm; }
-
+// 1 = fixed layout for beam <= kSmallK, vocabulary <= kSmallV: every LDS array sits at a compile-time address, which
+// frees the scalar registers the bases would occupy and folds them into the instructions' offset fields;
+// 2 = the pruned default's compile-time layout (beam_core.h kMidK); 3 = the first wide-beam one, at BIG == 1 (beam_core.h kWideK).
 // PRUNED: the candidates of every frame come from the vocabulary-prune pass (a.pr_*), otherwise they are the rows of a.probs.
 // OCC2 (fixed layout only): the build for two workgroups per CU -- at most 64 VGPRs (8 waves per SIMD) and the exact
 // replay's scratch in HBM (67 KB of LDS instead of 132 KB).  A lone workgroup runs ~7 % slower than in the default build
@@ -943,7 +927,8 @@ __global__ void __launch_bounds__(1024, OCC2 ? 8 : 1) ctc_beam_decode_kernel(Ker
   // of the decode): the same code on both routes, and the kernels keep the register allocation they had with blockIdx.x alone.
   // The wide-beam run-time layouts (BIG at LAYOUT 0) do not: there a claimed item costs 1-3 % of every launch, so they
   // keep batch order (decode_common never passes them an order).
-  constexpr bool kTicket = !(BIG != 0 && LAYOUT == 0);
+  constexpr KernelKey kKey{PROF, BIG, LAYOUT, PRUNED, NT, LM, OCC2};
+  constexpr bool kTicket = takes_launch_order(kKey);
   if (kTicket && threadIdx.x == 0) {
 #if defined(__HIP_DEVICE_COMPILE__)
     int *o = *(int *const *)((const char *)__builtin_amdgcn_kernarg_segment_ptr() + offsetof(KernelArgs, order));
@@ -975,8 +960,8 @@ __global__ void __launch_bounds__(1024, OCC2 ? 8 : 1) ctc_beam_decode_kernel(Ker
   // 10.94 -> 10.70 ms; the kernels sit at the scalar-register limit), so that case gets a build without them and the
   // streamed case keeps the build it had.
   constexpr int XP = PROF == 4 ? 0 : PROF == 5 ? 3 : PROF;
-  // (every instantiation for which this holds is listed, with its twin, in ctcdecode_amd.hip streamed_input_twin: the launch code swaps them)
-  constexpr bool kNoStreamedInput = (PROF == 0 || PROF == 3) && LAYOUT == 1 && NT == 1024 && (LM == 0 || LM == 2) && !PRUNED && BIG == 0 && (!OCC2 || LM == 0);
+  // (launch_plan.h plan_launch swaps a build for which this holds for its twin when the rows are streamed)
+  constexpr bool kNoStreamedInput = ignores_streamed_input(kKey);
   DevX<XP, BIG != 0, NT> x{red, 0, prof, 0, (PROF == 1 && a.dbg && b == 0) ? a.dbg : nullptr, 1 + 4 * a.K,
                     (PROF == 2 && b == 0 && a.tl) ? tlbuf : nullptr, tlcnt, kTlCap, a.tl_f0, a.tl_nf, b};
   int len = a.seq_lens ? __builtin_amdgcn_readfirstlane(a.seq_lens[b]) : a.T;
@@ -1087,7 +1072,8 @@ __global__ void __launch_bounds__(1024, OCC2 ? 8 : 1) ctc_beam_decode_kernel(Ker
 
 // Every instantiation the library launches: X(PROF, BIG, LAYOUT, PRUNED, NT, LM, OCC2, translation-unit group).
 // (Groups 0-3 hold the headline families; new instantiations go elsewhere so that those translation units stay as they are.)
-// decode_kernels.hip instantiates the ones of its group (-DCTC_KERNEL_GROUP=g); ctcdecode_amd.hip declares them all extern.
+// decode_kernels.hip instantiates the ones of its group (-DCTC_KERNEL_GROUP=g); ctcdecode_amd.hip declares them all extern and keeps
+// their addresses by key, and launch_plan.h plan_launch picks among them.
 #define CTC_KERNEL_GROUPS 12
 #if defined(CTC_QUICK_BUILD) && CTC_QUICK_BUILD == 2  // experiment builds of the LM tier: its north-star class kernel and the timeline twin
 #define CTC_KERNEL_LIST(X) X(0, 0, 1, false, 1024, 2, false, 0) X(2, 0, 1, false, 1024, 2, false, 1) X(0, 0, 1, false, 1024, true, false, 1) X(2, 0, 1, false, 1024, true, false, 0) X(4, 0, 1, false, 1024, 2, false, 1)

@@ -359,7 +359,8 @@ int ctcd_set_cu_sharing(ctcd_decoder *dec, int mode);
  * produce: some twenty entries with descendants in the beam per frame -- decode 7 % faster with it, bushy beams (random rows:
  * one or two) 3 % slower.  mode -1 (default): chosen per launch from the shape statistic of the last launch whose status was
  * checked (ctcd_check_status; the *_host / to_host entries check); 0 / 1: never / always.  Results are identical in both
- * builds.  ctcd_last_subtree_search: which build the last launch used (0 / 1). */
+ * builds (mode 1 in a library built without the subtree build: CTCD_EUNSUPPORTED).  ctcd_last_subtree_search: which build the
+ * last launch used (0 / 1). */
 int ctcd_set_subtree_search(ctcd_decoder *dec, int mode);
 int ctcd_last_subtree_search(const ctcd_decoder *dec);
 /* The workspace layout of the kernel the last decode launch used (tests prove with it which kernel ran): 0 = the run-time layout;
@@ -370,9 +371,8 @@ int ctcd_last_subtree_search(const ctcd_decoder *dec);
 int ctcd_debug_last_layout(const ctcd_decoder *dec);
 /* The kernel instantiation the last decode launch used (tests prove with it that every instantiation is reached): writes its
  * template arguments {PROF, BIG, LAYOUT, PRUNED, NT, LM, OCC2} (decode_kernel.h CTC_KERNEL_LIST; LM as 0 / 1 / 2 / 3, the others
- * as 0 / 1 or their value) to params[7] and returns CTCD_OK.  A launch that failed is not recorded (nor by ctcd_debug_last_layout).
- * -1 (CTCD_EINVAL): no launch yet, or a NULL argument (that case alone sets ctcd_last_error); CTCD_EINTERNAL: the launched kernel is
- * not in the build's list (a bug). */
+ * as 0 / 1 or their value) to params[7] and returns CTCD_OK.  A launch that failed is not recorded (nor by ctcd_debug_last_layout
+ * and ctcd_last_subtree_search).  -1 (CTCD_EINVAL): no launch yet, or a NULL argument (that case alone sets ctcd_last_error). */
 int ctcd_debug_last_kernel(const ctcd_decoder *dec, int32_t params[7]);
 /* The pre-pass kernels the last call of `dec` launched (tests prove with it that every pre-pass instantiation is reached): four stages
  * -- elementwise (prob -> log / half rows widened), log_softmax, vocabulary prune, prune_resolve_kernel -- of four words each, {kernel,

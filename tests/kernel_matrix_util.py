@@ -1,7 +1,8 @@
 """One case per instantiation of ctc_beam_decode_kernel (ctcdecode_amd/csrc/decode_kernel.h CTC_KERNEL_LIST, product branch): the
 template arguments the case must launch, the decoder arguments and switches that select it, and an input recipe.  Shared by the CPU
-coverage check (test_abi.py: the table covers the list exactly) and the GPU tests (test_gpu_kernel_matrix.py: the hook reports the
-expected kernel, which decodes like the oracle).  No torch here: the CPU suite imports this module.
+checks (test_abi.py: the table covers the list exactly; test_launch_plan.py: the host's choice plans each case's kernel) and the GPU
+tests (test_gpu_kernel_matrix.py: the hook reports the expected kernel, which decodes like the oracle).  No torch here: the CPU suite
+imports this module.
 
 A kernel is the tuple (PROF, BIG, LAYOUT, PRUNED, NT, LM, OCC2), LM as 0 / 1 / 2 / 3 (no scorer / general scorer / word model over
 <= 64 labels / callback scorer).  Shapes were chosen with the workspace sizes of beam_core.h carve() against 160 KB of LDS:
@@ -123,6 +124,16 @@ def expected_layout(kernel):
     if big and layout == 0:
         return 3 + big
     return layout if layout in (1, 2) else 0
+
+
+def scorer_kind(c):
+    """The scorer of a case as launch_plan.h ScorerKind: 0 none, 1 one the general builds serve (a character model, a word model over
+    more than 64 labels, or any with CTCD_GENERAL_LM_KERNEL=1), 2 a word model over <= 64 labels, 3 a callback."""
+    if not c["lm"]:
+        return 0
+    if c["callback"]:
+        return 3
+    return 2 if c["lm"] == "word" and not c["general"] else 1
 
 
 def parse_kernel_list(header_text):

@@ -7,6 +7,7 @@
 #include "../../ctcdecode_amd/csrc/lm_build.h"
 #include "../../ctcdecode_amd/csrc/lm_callback.h"
 #include "../../ctcdecode_amd/csrc/compact_results.h"
+#include "../../ctcdecode_amd/csrc/launch_plan.h"
 
 #include <algorithm>
 #include <atomic>
@@ -733,4 +734,29 @@ extern "C" long long ctccore_check_helpers(unsigned long long seed, long long n_
         if (ch >= 0 && (mk_info(ch, 0, 0) >> 16) >= (mk_info(ch - 1, 0, 0) >> 16)) ++bad;
       }
   return bad;
+}
+
+// The decode kernel the library plans for a call (launch_plan.h plan_launch; tests/test_launch_plan.py) in a build whose
+// CTC_KERNEL_LIST holds the n_keys kernels of keys[7 * n_keys] (the tuples of tests/kernel_matrix_util.py parse_kernel_list).
+// scorer: launch_plan.h ScorerKind.  Writes {PROF, BIG, LAYOUT, PRUNED, NT, LM, OCC2, layout_of(key), threads, lds} to out[10] and
+// returns 0, or returns the refusal's code (and leaves out as it was).
+extern "C" int ctccore_plan_kernel(const int32_t *keys, int n_keys, int B, int V, int beam, int cutoff_top_n, double cutoff_prob, int threads,
+                                   int max_lds, int cu_count, int no_fixed_layout, int profile, int tl_armed, int cu_sharing,
+                                   int subtree_mode, int subtree_on, int scorer, int streamed, int32_t out[10]) {
+  using namespace ctcdk;
+  auto compiled = [keys, n_keys](const KernelKey &k) {
+    for (int i = 0; i < n_keys; ++i) {
+      const int32_t *c = keys + 7 * i;
+      if (KernelKey{c[0], c[1], c[2], c[3], c[4], c[5], c[6]} == k) return true;
+    }
+    return false;
+  };
+  const ctcbeam::Dims dims = make_dims(beam, V, cutoff_top_n, used_cutoff_prob(cutoff_prob), scorer != kNoScorer);
+  const LaunchSwitches sw{no_fixed_layout != 0, profile != 0, tl_armed != 0, cu_sharing, subtree_mode, subtree_on != 0};
+  const LaunchPlan p = plan_launch(dims, B, threads, max_lds, cu_count, sw, (ScorerKind)scorer, streamed != 0, compiled);
+  if (p.rc) return p.rc;
+  const KernelKey &k = p.key;
+  const int32_t o[10] = {k.prof, k.big, k.layout, k.pruned, k.nt, k.lm, k.occ2, layout_of(k), p.threads, (int32_t)p.lds};
+  std::memcpy(out, o, sizeof(o));
+  return 0;
 }
