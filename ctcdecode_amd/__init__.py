@@ -887,6 +887,7 @@ class OnlineCTCBeamDecoder(object):
         if seq_lens is not None:
             lens_cpu = seq_lens.detach().cpu().to(torch.int32).contiguous()
         K = self._beam_width
+        self._unchecked = 0  # (this call's launch takes over the status words)
         # (a serving loop calls this once per chunk with the same states: the per-call host work is kept small -- the array of
         #  state handles is rebuilt only when the list changes, nothing is allocated or read back unless a stream ends)
         # (the cache holds WEAK references: a strong list kept ended streams' HBM blocks alive until the next call with other
@@ -952,7 +953,10 @@ class OnlineCTCBeamDecoder(object):
                 float(self._cutoff_prob), int(self._cutoff_top_n), int(self._blank_id), self._log_probs,
                 output.data_ptr(), timesteps.data_ptr(), scores.data_ptr(), out_len.data_ptr(), nres.data_ptr(), out_T, stream))
             if check or any_eos:
+                self._unchecked = 0
                 _native.check(_native.lib.ctcd_check_status(self._handle, B))
+            else:
+                self._unchecked = B  # (peek() looks at these status words with its own)
         if any_eos:
             self._ptr_cache = None  # (ended streams are not decoded again: the next call brings other states)
         if not any_eos:  # nothing ended: no results (binding.cpp:186-205 sizes them to the most results of any item: none)
@@ -963,6 +967,50 @@ class OnlineCTCBeamDecoder(object):
         R = int(nres_c.max()) if B else 0          # binding.cpp:186-205: sized to the most results / the longest beam
         L = int(out_len_c.max()) if B and R else 0
         return _to_host((output[:, :R, :L].contiguous(), scores, timesteps[:, :R, :L].contiguous(), out_len))
+
+    def peek(self, states, n_best=1, since=None):
+        """Interim results of live streams (extension; the reference reports nothing before ``is_eos``): what the streams' one-shot
+        decode of the frames fed so far returns, without feeding a frame and without disturbing the streams.
+
+        Returns CPU tensors ``beam_results[B, n, L], beam_scores[B, n], timesteps[B, n, L], out_lens[B, n], stable_lens[B]``: n = the
+        most results of any stream (at most ``n_best``), ``out_lens`` the FULL lengths, ``beam_results`` / ``timesteps`` the labels
+        from depth ``since[b]`` on (``since``: a sequence of B ints or None = 0; L = the longest reported part).  ``stable_lens[b]``
+        labels of every row of stream b are final -- every later result of the stream begins with them, time steps included -- so a
+        client commits them and asks with ``since=stable_lens`` next time.  Works behind ``decode(..., check=False)`` chunks."""
+        B = len(states)
+        n_best = int(n_best)
+        if n_best < 1:
+            raise ValueError("n_best must be at least 1")
+        if since is not None and len(since) != B:
+            raise ValueError("since needs one entry per stream")
+        if self._scorer is not None and isinstance(self._scorer, CallbackScorer):
+            raise NotImplementedError("ctcdecode_amd: interim results of streams behind a callback scorer")
+        if B == 0:
+            return (torch.zeros((0, 0, 0), dtype=torch.int32), torch.zeros((0, 0), dtype=torch.float32), torch.zeros((0, 0, 0), dtype=torch.int32),
+                    torch.zeros((0, 0), dtype=torch.int32), torch.zeros((0,), dtype=torch.int32))
+        ptrs = (ctypes.c_void_p * B)(*[st._ptr(self) for st in states])
+        sin = [max(0, int(v)) for v in since] if since is not None else [0] * B
+        # the device buffers are bounded by what the host knows: no row is longer than the frames its stream has been fed
+        L_cap = max(0, max(int(_native.lib.ctcd_stream_frames(ptrs[b])) - sin[b] for b in range(B)))
+        since_c = (ctypes.c_int32 * B)(*sin)
+        with torch.cuda.device(self._device):
+            tok = torch.empty((B, n_best, L_cap), dtype=torch.int32, device=self._device)
+            ts = torch.empty((B, n_best, L_cap), dtype=torch.int32, device=self._device)
+            scores = torch.empty((B, n_best), dtype=torch.float32, device=self._device)
+            # [out_lens | n_results | stable_lens]: one small copy tells the host how much of the label tensors to bring over
+            meta = torch.empty((B * (n_best + 2),), dtype=torch.int32, device=self._device)
+            out_len, nres, stable = meta[:B * n_best].view(B, n_best), meta[B * n_best:B * n_best + B], meta[B * n_best + B:]
+            stream = torch.cuda.current_stream(self._device).cuda_stream
+            _native.check(_native.lib.ctcd_stream_peek(self._handle, ptrs, B, n_best, since_c, tok.data_ptr(), ts.data_ptr(), L_cap,
+                                                       scores.data_ptr(), out_len.data_ptr(), nres.data_ptr(), stable.data_ptr(), stream))
+            unchecked, self._unchecked = getattr(self, "_unchecked", 0), 0
+            _native.check(_native.lib.ctcd_check_status(self._handle, unchecked))
+            meta_c = meta.cpu()
+            out_len_c = meta_c[:B * n_best].view(B, n_best)
+            n = int(meta_c[B * n_best:B * n_best + B].max())
+            rep = out_len_c[:, :n] - torch.tensor(sin, dtype=torch.int32).view(B, 1)
+            L = max(0, int(rep.max())) if n else 0
+            return (tok[:, :n, :L].cpu(), scores[:, :n].cpu(), ts[:, :n, :L].cpu(), out_len_c[:, :n].contiguous(), meta_c[B * n_best + B:].contiguous())
 
     def character_based(self):
         return bool(_native.lib.ctcd_scorer_is_character_based(self._scorer.handle)) if self._scorer else None

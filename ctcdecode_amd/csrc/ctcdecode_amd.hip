@@ -29,6 +29,7 @@
 #include "lm_build.h"
 #include "lm_callback.h"
 #include "compact_results.h"
+#include "stream_peek.h"
 
 namespace {
 
@@ -1376,6 +1377,15 @@ struct ctcd_decoder {
   size_t h_stargs_cap = 0;
   hipEvent_t ev_stargs[2] = {nullptr, nullptr};
   unsigned long long stream_calls = 0;
+  // ctcd_stream_peek: its per-item arguments [block pointers | pool capacities | since] travel like a chunk call's (two page-locked
+  // slots, an event each); its status words are its own, so that a peek between unchecked chunks does not hide their outcome
+  Buf peek_args, peek_status;
+  char *h_pkargs[2] = {nullptr, nullptr};
+  size_t h_pkargs_cap = 0;
+  hipEvent_t ev_pkargs[2] = {nullptr, nullptr};
+  unsigned long long peek_calls = 0;
+  int peek_items = 0;                 // items of a queued peek whose status words nobody has looked at yet (0: none)
+  hipStream_t peek_stream = nullptr;  // ... and the stream it was queued on
   std::mutex mu;
   std::mutex mu_host;  // the host-tensor entry points: compact buffers, page-locked staging and the worker threads are per decoder
 };
@@ -1591,6 +1601,11 @@ void ctcd_destroy(ctcd_decoder *d) {
     if (d->h_stargs[i]) (void)hipHostFree(d->h_stargs[i]);
     if (d->ev_stargs[i]) (void)hipEventDestroy(d->ev_stargs[i]);
   }
+  for (int i = 0; i < 2; ++i) {
+    if (d->h_pkargs[i]) (void)hipHostFree(d->h_pkargs[i]);
+    if (d->ev_pkargs[i]) (void)hipEventDestroy(d->ev_pkargs[i]);
+  }
+  d->peek_args.release(); d->peek_status.release();
   if (d->copy_stream) (void)hipStreamDestroy(d->copy_stream);
   if (d->ev_in) (void)hipEventDestroy(d->ev_in);
   if (d->ev_order) (void)hipEventDestroy(d->ev_order);
@@ -2820,6 +2835,82 @@ int ctcd_stream_decode(ctcd_decoder *d, ctcd_stream **states, const unsigned cha
   return CTCD_OK;
 }
 
+// Interim results of live streams (stream_peek.h): one launch of ctc_stream_peek_kernel on the parked states, behind whatever chunks
+// are queued on `stream`.  Everything is refused before anything is queued.
+int ctcd_stream_peek(ctcd_decoder *d, ctcd_stream **states, int B, int n_best, const int32_t *since_host, int32_t *out_tok, int32_t *out_ts,
+                     int L_cap, float *out_sc, int32_t *out_len, int32_t *n_results, int32_t *stable_lens, void *stream_) {
+  if (!d || B < 0 || L_cap < 0 || (B > 0 && !states)) return fail(CTCD_EINVAL, "bad arguments");
+  if (B == 0) return CTCD_OK;
+  if (!out_sc || !out_len || !n_results || !stable_lens || (L_cap > 0 && (!out_tok || !out_ts))) return fail(CTCD_EINVAL, "null tensor");
+  if (n_best < 1) return fail(CTCD_EINVAL, "n_best must be at least 1");
+  std::lock_guard<std::mutex> lock(d->mu);
+  CTC_ON_DEVICE(d->device);
+  hipStream_t stream = (hipStream_t)stream_;
+  const unsigned long long call_id = ++g_stream_call_id;
+  for (int b = 0; b < B; ++b) {
+    ctcd_stream *st = states[b];
+    if (!st || st->device != d->device || st->beam != states[0]->beam || st->V != states[0]->V)
+      return fail(CTCD_EINVAL, "stream state does not match the decoder configuration");
+    if (st->scorer != states[0]->scorer) return fail(CTCD_EINVAL, "the streams of one batch must share their scorer");
+    if (st->seen_in_call == call_id) return fail(CTCD_EINVAL, "the same stream state appears twice in one batch");
+    st->seen_in_call = call_id;
+  }
+  const int beam = states[0]->beam;
+  ctcd_scorer *scorer = states[0]->scorer;
+  if (n_best > beam) return fail(CTCD_EINVAL, "n_best is larger than the beam width");
+  if (scorer && scorer->cbl)
+    return fail(CTCD_EUNSUPPORTED, "interim results of streams behind a callback scorer (the scorer's cache may not hold the \"<s>\" / \"</s>\" / last-word windows they need)");
+  if (scorer && scorer->device != d->device) return fail(CTCD_EINVAL, "the scorer's tables live on another device than the decoder");
+  const size_t lds = ctcpeek::peek_lds_bytes(beam, scorer != nullptr);
+  if (lds + 1024 > (size_t)d->max_lds) return fail(CTCD_EUNSUPPORTED, "interim results: the sort words of this beam width exceed one workgroup's LDS");
+  int rc;
+  const size_t off_cap = (size_t)B * 8, off_since = off_cap + (size_t)B * 4, need = (off_since + (size_t)B * 4 + 31) & ~(size_t)15;
+  if ((rc = d->peek_args.ensure(2 * need))) return rc;
+  if ((rc = d->peek_status.ensure((size_t)B * 4))) return rc;
+  if (d->h_pkargs_cap < need) {
+    for (int i = 0; i < 2; ++i) {
+      if (d->ev_pkargs[i]) HIP_TRY(hipEventSynchronize(d->ev_pkargs[i]));
+      if (d->h_pkargs[i]) (void)hipHostFree(d->h_pkargs[i]);
+      d->h_pkargs[i] = nullptr;
+      HIP_TRY(hipHostMalloc((void **)&d->h_pkargs[i], need, hipHostMallocDefault));
+      if (!d->ev_pkargs[i]) HIP_TRY(hipEventCreateWithFlags(&d->ev_pkargs[i], hipEventDisableTiming));
+    }
+    d->h_pkargs_cap = need;
+  }
+  const int slot = (int)(d->peek_calls++ & 1);
+  HIP_TRY(hipEventSynchronize(d->ev_pkargs[slot]));  // (the copy of two calls ago: long done)
+  char *hb = d->h_pkargs[slot];
+  for (int b = 0; b < B; ++b) {
+    ctcd_stream *st = states[b];
+    ((char **)hb)[b] = st->block;
+    ((int *)(hb + off_cap))[b] = (int)(st->cap_frames * beam + 1);
+    ((int *)(hb + off_since))[b] = since_host ? since_host[b] : 0;
+  }
+  char *db = (char *)d->peek_args.p + (size_t)slot * need;
+  HIP_TRY(hipMemcpyAsync(db, hb, off_since + (size_t)B * 4, hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipEventRecord(d->ev_pkargs[slot], stream));
+  // every status word starts as -1 ("no result"): a workgroup that never ran cannot read back as ok
+  HIP_TRY(hipMemsetAsync(d->peek_status.p, 0xff, (size_t)B * 4, stream));
+  ctclm::LmView lmv;
+  if (scorer) {
+    lmv = scorer->dview;
+    lmv.alpha = scorer->host.alpha;  // reset_params takes effect at the next call, as for a decode
+    lmv.beta = scorer->host.beta;
+  }
+  ctcpeek::PeekLaunch l;
+  l.blocks = (char *const *)db; l.pool_caps = (const int *)(db + off_cap); l.since = (const int *)(db + off_since);
+  l.pool_off = (long long)stream_pool_offset(beam);
+  l.B = B; l.K = beam;
+  l.lm = scorer ? &lmv : nullptr;
+  l.out = ctcpeek::PeekOut{out_tok, out_ts, out_sc, out_len, n_results, stable_lens, n_best, L_cap};
+  l.status = (int32_t *)d->peek_status.p;
+  const int e = ctcpeek::launch_stream_peek(l, stream_);
+  if (e != (int)hipSuccess) return fail(CTCD_EHIP, std::string("ctc_stream_peek_kernel: ") + hipGetErrorString((hipError_t)e));
+  d->peek_items = B;
+  d->peek_stream = stream;
+  return CTCD_OK;
+}
+
 // The streaming call with its results delivered to HOST memory, sized as the reference sizes them (binding.cpp:186-205: tokens /
 // timesteps [B, R, L] with R = the most results of any item that ended, L = the longest of their label sequences).  R and L are
 // known only when the kernel has run: the caller hands over an allocator, called once with (R, L), that returns the two buffers
@@ -3426,8 +3517,18 @@ int ctcd_fetch_status_async(ctcd_decoder *d, int B, int32_t *host_status, void *
 // Status words of the last ctcd_beam_decode on this decoder (device -> host); for callers of the async entry point.
 int ctcd_check_status(ctcd_decoder *d, int B) {
   if (!d || B < 0) return fail(CTCD_EINVAL, "bad arguments");
-  if (B == 0) return CTCD_OK;
   CTC_ON_DEVICE(d->device);
+  if (d->peek_items > 0) {  // a queued ctcd_stream_peek: its own status words first (B counts the items of the last decode launch; 0: the peek alone)
+    std::vector<int32_t> ps((size_t)d->peek_items);
+    d->peek_items = 0;
+    HIP_TRY(hipMemcpyAsync(ps.data(), d->peek_status.p, ps.size() * 4, hipMemcpyDeviceToHost, d->peek_stream));
+    HIP_TRY(hipStreamSynchronize(d->peek_stream));
+    for (size_t b = 0; b < ps.size(); ++b) {
+      if (ps[b] == ctcpeek::PEEK_ROW_OVERFLOW) return fail(CTCD_EINVAL, "ctcd_stream_peek: a result row of item " + std::to_string(b) + " does not fit L_cap");
+      if (ps[b] != ctcpeek::PEEK_OK) return fail(CTCD_EINTERNAL, "ctcd_stream_peek: status " + std::to_string(ps[b]) + " for item " + std::to_string(b));
+    }
+  }
+  if (B == 0) return CTCD_OK;
   if (!d->status.p || d->status.cap < (size_t)B * 4) return fail(CTCD_EINVAL, "no decode of that many items has been launched");
   const bool with_shape = d->status.cap >= (size_t)B * 8 && d->status_items == B;
   std::vector<int32_t> st((size_t)B * (with_shape ? 2 : 1));

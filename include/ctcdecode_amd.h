@@ -247,6 +247,25 @@ int ctcd_stream_decode_to_host(ctcd_decoder *dec, ctcd_stream **states, const un
                                int cutoff_top_n, int blank_id, int log_input, ctcd_result_alloc_fn alloc, void *alloc_user,
                                float *out_scores, int32_t *out_lens, int32_t *n_results, int out_T, int *out_R, int *out_L, void *stream);
 
+/* Interim results of live streams (extension; the reference reports nothing before is_eos): what DecoderState::decode()
+ * (ctc_beam_search_decoder.cpp:164-211, which does not change the state) would return now -- the result list of the one-shot decode
+ * of the frames fed so far.  No frame is fed and nothing a later chunk reads is written.  Per stream b, with n = min(n_best, results):
+ * n_results[b] = n; out_scores / out_lens [b, p] for p < n (the FULL length of row p); out_tokens / out_timesteps [b, p, q - since[b]]
+ * for since[b] <= q < length (since_host == NULL: 0; a row shorter than since[b] reports no labels); stable_lens[b] = the length of
+ * the longest common prefix of ALL current beam entries -- a prefix of every hypothesis the stream can still produce: it only grows,
+ * and its labels and time steps never change again, so a client commits those labels and asks with since = stable_len.  Every
+ * other position of the buffers is written as zero.  A stream without frames reports the root alone: one result of length 0.
+ * Queued on `stream` behind the chunks already queued there; asynchronous (the `since` values are copied before the call returns).
+ * A row that does not fit L_cap is not cut: nothing of that stream's rows is written and the next ctcd_check_status reports
+ * CTCD_EINVAL (it checks the peek's status words before those of the last decode launch, which stay as they are).
+ * CTCD_EINVAL: n_best < 1 or > beam, a state that is not this decoder's (device, beam), a state twice in the batch, streams with
+ * different scorers.  CTCD_EUNSUPPORTED: streams behind a callback scorer (the interim result needs "<s>" / "</s>" / last-word
+ * windows its cache may not hold).  The decoder and the states stay usable after every refused call. */
+int ctcd_stream_peek(ctcd_decoder *dec, ctcd_stream **states, int B, int n_best, const int32_t *since_host /* [B] or NULL */,
+                     int32_t *out_tokens, int32_t *out_timesteps /* DEVICE [B, n_best, L_cap] */, int L_cap,
+                     float *out_scores, int32_t *out_lens /* DEVICE [B, n_best] */,
+                     int32_t *n_results, int32_t *stable_lens /* DEVICE [B] */, void *stream);
+
 /* Host check of the per-item status words written by the last ctcd_beam_decode (synchronises the device). */
 int ctcd_check_status(ctcd_decoder *dec, int B);
 /* ... without blocking: enqueues the copy of the B status words (0 = ok) into `host_status` (page-locked memory) on
