@@ -809,7 +809,7 @@ class OnlineCTCBeamDecoder(object):
     every stream stay in HBM between calls; ``timesteps`` count frames from the beginning of the stream."""
 
     def __init__(self, labels, model_path=None, alpha=0, beta=0, cutoff_top_n=40, cutoff_prob=1.0, beam_width=100,
-                 num_processes=4, blank_id=0, log_probs_input=False, device=None, logits_input=False, scorer=None):
+                 num_processes=4, blank_id=0, log_probs_input=False, device=None, logits_input=False, scorer=None, compact_pool_above=None):
         self._cutoff_top_n = cutoff_top_n
         self._beam_width = beam_width
         self._scorer = None
@@ -829,6 +829,12 @@ class OnlineCTCBeamDecoder(object):
         h = ctypes.c_void_p()
         _native.check(_native.lib.ctcd_create(ctypes.byref(h), self._device.index))
         self._handle = h
+        # compact_pool_above (extension): a stream whose next chunk does not fit its node pool, and whose pool may hold at least this
+        # many nodes, is compacted (see ``compact``) before it is allowed to double; None: streams only ever double
+        if compact_pool_above is not None:
+            if int(compact_pool_above) < 1:
+                raise ValueError("compact_pool_above is a node count of at least 1 (None: off)")
+            _native.check(_native.lib.ctcd_set_stream_compaction(self._handle, int(compact_pool_above)))
         if scorer is not None:
             self._scorer = _adopt_scorer(scorer, model_path, self._num_labels, self._device.index)
         elif model_path:  # ctcdecode/__init__.py:183-187
@@ -1012,6 +1018,25 @@ class OnlineCTCBeamDecoder(object):
             L = max(0, int(rep.max())) if n else 0
             return (tok[:, :n, :L].cpu(), scores[:, :n].cpu(), ts[:, :n, :L].cpu(), out_len_c[:, :n].contiguous(), meta_c[B * n_best + B:].contiguous())
 
+    def compact(self, states):
+        """Give back the memory of live streams (extension; the reference frees trie nodes as it goes): every stream keeps exactly
+        the trie nodes its current beam can still reach and drops the rest of its node pool.  Nothing a later ``decode`` or ``peek``
+        returns changes, however often and wherever between chunks this is called.  Returns the nodes kept per stream (a list of B
+        ints).  A stream that now needs at most a quarter of its block moves to a smaller one (``DecoderState.nbytes`` falls).
+        Works behind ``decode(..., check=False)`` chunks; synchronous."""
+        B = len(states)
+        if B == 0:
+            return []
+        ptrs = (ctypes.c_void_p * B)(*[st._ptr(self) for st in states])
+        live = (ctypes.c_int32 * B)()
+        with torch.cuda.device(self._device):
+            stream = torch.cuda.current_stream(self._device).cuda_stream
+            self._check(_native.lib.ctcd_stream_compact(self._handle, ptrs, B, live, stream))
+            # (the call has waited for the chunks queued in front of it: their status words are looked at now, as peek() does)
+            unchecked, self._unchecked = getattr(self, "_unchecked", 0), 0
+            _native.check(_native.lib.ctcd_check_status(self._handle, unchecked))
+        return [int(v) for v in live]
+
     def character_based(self):
         return bool(_native.lib.ctcd_scorer_is_character_based(self._scorer.handle)) if self._scorer else None
 
@@ -1051,6 +1076,16 @@ class DecoderState(object):
         if decoder is not self._decoder:
             raise ValueError("DecoderState used with a different decoder than it was created for")
         return self.state.value
+
+    @property
+    def nbytes(self):
+        """Bytes of HBM the stream's block holds now (it doubles as the stream grows; ``OnlineCTCBeamDecoder.compact`` can shrink it)."""
+        return int(_native.lib.ctcd_stream_bytes(self.state))
+
+    @property
+    def pool_nodes(self):
+        """Upper bound of the trie nodes in the stream's pool: frames * beam + 1, or nodes kept + (frames since) * beam after a compaction."""
+        return int(_native.lib.ctcd_stream_pool_nodes(self.state))
 
     def __del__(self):
         h = getattr(self, "state", None)

@@ -30,6 +30,7 @@
 #include "lm_callback.h"
 #include "compact_results.h"
 #include "stream_peek.h"
+#include "stream_compact.h"
 
 namespace {
 
@@ -1386,6 +1387,12 @@ struct ctcd_decoder {
   unsigned long long peek_calls = 0;
   int peek_items = 0;                 // items of a queued peek whose status words nobody has looked at yet (0: none)
   hipStream_t peek_stream = nullptr;  // ... and the stream it was queued on
+  // ctcd_stream_compact: the new layouts are gathered here before they go back into the streams' blocks; its per-item arguments
+  // and what its kernels report live in one page-locked region both sides read and write in place (the call is synchronous)
+  Buf cp_scratch;
+  char *h_cp = nullptr;
+  size_t h_cp_cap = 0;
+  long long compact_min_nodes = 0;    // ctcd_set_stream_compaction: 0 = a stream that outgrows its pool doubles it, as ever
   std::mutex mu;
   std::mutex mu_host;  // the host-tensor entry points: compact buffers, page-locked staging and the worker threads are per decoder
 };
@@ -1399,7 +1406,11 @@ struct ctcd_stream {
   size_t bytes = 0;
   int V = 0, beam = 0;
   long long frames = 0;      // frames fed so far (host mirror of the header word)
-  long long cap_frames = 0;  // frames the node pool can take
+  long long cap_frames = 0;  // the node pool holds cap_frames * beam + 1 nodes
+  // ctcd_stream_compact (stream_compact.h): the nodes the last compaction left and the frame it ran at -- the pool count is at most
+  // base_nodes + (frames - base_frames) * beam; (1, 0) until the first one: frames * beam + 1
+  long long base_nodes = 1, base_frames = 0;
+  long long hint_frames = 0;  // the capacity the stream was created with: a compacted stream does not shrink below it
 };
 
 // The external scorer (ctcdecode/src/scorer.h:41-110, created by paddle_get_scorer, binding.cpp:143-150): built on the host
@@ -1606,6 +1617,8 @@ void ctcd_destroy(ctcd_decoder *d) {
     if (d->ev_pkargs[i]) (void)hipEventDestroy(d->ev_pkargs[i]);
   }
   d->peek_args.release(); d->peek_status.release();
+  d->cp_scratch.release();
+  if (d->h_cp) (void)hipHostFree(d->h_cp);
   if (d->copy_stream) (void)hipStreamDestroy(d->copy_stream);
   if (d->ev_in) (void)hipEventDestroy(d->ev_in);
   if (d->ev_order) (void)hipEventDestroy(d->ev_order);
@@ -2746,6 +2759,7 @@ int ctcd_stream_create(ctcd_decoder *d, ctcd_stream **out, int V, int beam, int 
   st->V = V;
   st->beam = beam;
   st->cap_frames = frames_hint > 0 ? frames_hint : 1024;
+  st->hint_frames = st->cap_frames;
   st->bytes = stream_block_bytes(st->cap_frames, beam);
   hipError_t e = hipMalloc((void **)&st->block, st->bytes);
   if (e != hipSuccess) { delete st; return fail(CTCD_EHIP, std::string("hipMalloc: ") + hipGetErrorString(e)); }
@@ -2765,12 +2779,130 @@ void ctcd_stream_destroy(ctcd_decoder *d, ctcd_stream *st) {
 
 long long ctcd_stream_frames(const ctcd_stream *st) { return st ? st->frames : -1; }
 
+// Compacts the node pools of B parked streams of one beam width (stream_compact.h), behind whatever is queued on `stream`:
+// count -> the host sizes the scratch and decides which streams move to a smaller block -> gather -> store.  The caller has checked
+// the states.  live_out (host, or null): nodes of every stream's live set.  Synchronous.
+static int compact_streams(ctcd_decoder *d, ctcd_stream **sts, int B, int32_t *live_out, hipStream_t stream) {
+  namespace cc = ctccompact;
+  std::lock_guard<std::mutex> lock(d->mu);
+  const int beam = sts[0]->beam;
+  if (cc::compact_lds_bytes(beam) + 1024 > (size_t)d->max_lds)
+    return fail(CTCD_EUNSUPPORTED, "stream compaction: the layout arrays of this beam width exceed one workgroup's LDS");
+  const size_t n = (size_t)B, o_dst = n * 8, o_scr = 2 * n * 8, o_cap = 3 * n * 8, o_dcap = o_cap + n * 4, o_live = o_dcap + n * 4,
+               o_stat = o_live + n * 4, need = o_stat + n * 4;
+  if (d->h_cp_cap < need) {
+    if (d->h_cp) (void)hipHostFree(d->h_cp);
+    d->h_cp = nullptr;
+    d->h_cp_cap = 0;
+    HIP_TRY(hipHostMalloc((void **)&d->h_cp, 2 * need, hipHostMallocMapped | hipHostMallocCoherent));
+    d->h_cp_cap = 2 * need;
+  }
+  char *hb = d->h_cp, *db = nullptr;
+  HIP_TRY(hipHostGetDevicePointer((void **)&db, hb, 0));
+  char **h_blk = (char **)hb, **h_dst = (char **)(hb + o_dst);
+  long long *h_scr = (long long *)(hb + o_scr);
+  int *h_cap = (int *)(hb + o_cap), *h_dcap = (int *)(hb + o_dcap);
+  volatile int *h_live = (volatile int *)(hb + o_live), *h_stat = (volatile int *)(hb + o_stat);
+  for (int b = 0; b < B; ++b) {
+    h_blk[b] = h_dst[b] = sts[b]->block;
+    h_cap[b] = h_dcap[b] = (int)cc::pool_capacity(sts[b]->cap_frames, beam);
+    h_scr[b] = 0;
+    h_live[b] = -1;  // ("no result": a workgroup that never ran cannot read back as a count)
+    h_stat[b] = cc::COMPACT_OK;
+  }
+  cc::CompactLaunch l;
+  l.ctl = cc::CompactCtl{(char *const *)db, (const int *)(db + o_cap), (int *)(db + o_live), (int *)(db + o_stat), (char *const *)(db + o_dst),
+                         (const int *)(db + o_dcap), (const long long *)(db + o_scr)};
+  l.scratch = nullptr;
+  l.pool_off = (long long)stream_pool_offset(beam);
+  l.B = B; l.K = beam;
+  int e = cc::launch_compact_count(l, (void *)stream);
+  if (e != (int)hipSuccess) return fail(CTCD_EHIP, std::string("ctc_stream_compact_count_kernel: ") + hipGetErrorString((hipError_t)e));
+  HIP_TRY(hipStreamSynchronize(stream));
+  long long total = 0;
+  for (int b = 0; b < B; ++b) {
+    const int M = h_live[b];
+    if (M < 0) return fail(CTCD_EINTERNAL, "ctcd_stream_compact: the parked state of item " + std::to_string(b) + " is not one a decode wrote");
+    h_scr[b] = total;
+    total += (long long)cc::compact_out_ints(M);
+  }
+  if (total > 0) {
+    int rc;
+    if ((size_t)total * 4 > d->cp_scratch.cap && (rc = d->cp_scratch.ensure((size_t)total * 4 + (size_t)total)))  // (a quarter of headroom)
+      return rc;
+    l.scratch = (int *)d->cp_scratch.p;
+    // a stream whose live set needs at most a quarter of its block moves to a smaller one: the only allocation of the call
+    std::vector<std::pair<char *, long long>> moved((size_t)B, {nullptr, 0});
+    auto drop_moved = [&] { for (auto &m : moved) if (m.first) (void)hipFree(m.first); };
+    for (int b = 0; b < B; ++b) {
+      const int M = h_live[b];
+      const long long nf = M > 0 ? cc::shrunk_cap_frames(sts[b]->cap_frames, sts[b]->hint_frames, M, beam) : 0;
+      if (!nf) continue;
+      char *nb = nullptr;
+      const hipError_t me = hipMalloc((void **)&nb, stream_block_bytes(nf, beam));
+      if (me != hipSuccess) { drop_moved(); return fail(CTCD_EHIP, std::string("hipMalloc: ") + hipGetErrorString(me)); }
+      moved[b] = {nb, nf};
+      h_dst[b] = nb;
+      h_dcap[b] = (int)cc::pool_capacity(nf, beam);
+    }
+    e = cc::launch_compact_move(l, (void *)stream);
+    if (e == (int)hipSuccess) e = (int)hipStreamSynchronize(stream);
+    if (e != (int)hipSuccess) { drop_moved(); return fail(CTCD_EHIP, std::string("ctc_stream_compact kernels: ") + hipGetErrorString((hipError_t)e)); }
+    for (int b = 0; b < B; ++b)
+      if (h_stat[b] != cc::COMPACT_OK) {
+        drop_moved();
+        return fail(CTCD_EINTERNAL, "ctcd_stream_compact: status " + std::to_string(h_stat[b]) + " for item " + std::to_string(b));
+      }
+    for (int b = 0; b < B; ++b) {
+      ctcd_stream *st = sts[b];
+      const int M = h_live[b];
+      if (M <= 0) continue;
+      if (moved[b].first) {
+        (void)hipFree(st->block);
+        st->block = moved[b].first;
+        st->cap_frames = moved[b].second;
+        st->bytes = stream_block_bytes(st->cap_frames, beam);
+      }
+      st->base_nodes = M;
+      st->base_frames = st->frames;
+    }
+  }
+  if (live_out)
+    for (int b = 0; b < B; ++b) live_out[b] = h_live[b] > 0 ? h_live[b] : 1;  // (a stream without frames: the root alone)
+  return CTCD_OK;
+}
+
+// grows a stream's block so that its pool takes `need` nodes (device-to-device copy of the parked state)
+static int stream_grow(ctcd_stream *st, long long need, hipStream_t stream) {
+  const int beam = st->beam;
+  const long long cap = ctccompact::grown_cap_frames(st->cap_frames, need, beam);
+  const size_t bytes = stream_block_bytes(cap, beam);
+  char *nb = nullptr;
+  HIP_TRY(hipMalloc((void **)&nb, bytes));
+  HIP_TRY(hipStreamSynchronize(stream));
+  const size_t used = (size_t)ctccompact::pool_bound(st->frames, st->base_nodes, st->base_frames, beam), off = stream_pool_offset(beam);
+  HIP_TRY(hipMemcpy(nb, st->block, off + used * sizeof(PoolNode), hipMemcpyDeviceToDevice));
+  HIP_TRY(hipMemcpy(nb + off + stream_nodes(cap, beam) * sizeof(PoolNode),
+                    st->block + off + stream_nodes(st->cap_frames, beam) * sizeof(PoolNode), used * sizeof(int), hipMemcpyDeviceToDevice));
+  HIP_TRY(hipMemset(nb + stream_thi_offset(cap, beam), 0, stream_nodes(cap, beam) * sizeof(int)));
+  HIP_TRY(hipMemcpy(nb + stream_thi_offset(cap, beam), st->block + stream_thi_offset(st->cap_frames, beam), used * sizeof(int), hipMemcpyDeviceToDevice));
+  (void)hipFree(st->block);
+  st->block = nb;
+  st->bytes = bytes;
+  st->cap_frames = cap;
+  return CTCD_OK;
+}
+
 // what every streaming call does first: the states are checked against the call, the chunk lengths clamped (binding.cpp:171),
-// node pools that the chunk would overflow grown
+// node pools that the chunk would overflow grown -- or, with ctcd_set_stream_compaction, compacted first and grown only if the
+// chunk still does not fit
 static int stream_prepare(ctcd_decoder *d, ctcd_stream **states, const unsigned char *is_eos, const int32_t *seq_lens_host, int B, int T, int V,
                           int beam, int out_T, hipStream_t stream, std::vector<int32_t> &lens, bool &any_eos) {
+  namespace cc = ctccompact;
   const unsigned long long call_id = ++g_stream_call_id;
   any_eos = false;
+  std::vector<ctcd_stream *> compact_first;
+  std::vector<int> compact_item;
   for (int b = 0; b < B; ++b) {
     ctcd_stream *st = states[b];
     if (!st || st->V != V || st->beam != beam) return fail(CTCD_EINVAL, "stream state does not match the decoder configuration");
@@ -2782,26 +2914,59 @@ static int stream_prepare(ctcd_decoder *d, ctcd_stream **states, const unsigned 
     len = len < 0 ? 0 : (len > T ? T : len);  // binding.cpp:171
     lens[b] = len;
     if (is_eos[b] && st->frames + len > out_T) return fail(CTCD_EINVAL, "out_T is smaller than the number of frames of a finishing stream");
-    if ((st->frames + len) * (long long)beam + 1 > 0x7fffffffLL) return fail(CTCD_EUNSUPPORTED, "stream too long for this beam width");
-    if (st->frames + len > st->cap_frames) {  // grow the node pool (device-to-device copy of the parked state)
-      long long cap = st->cap_frames * 2;
-      while (cap < st->frames + len) cap *= 2;
-      const size_t bytes = stream_block_bytes(cap, beam);
-      char *nb = nullptr;
-      HIP_TRY(hipMalloc((void **)&nb, bytes));
-      HIP_TRY(hipStreamSynchronize(stream));
-      const size_t used = stream_nodes(st->frames, beam), off = stream_pool_offset(beam);
-      HIP_TRY(hipMemcpy(nb, st->block, off + used * sizeof(PoolNode), hipMemcpyDeviceToDevice));
-      HIP_TRY(hipMemcpy(nb + off + stream_nodes(cap, beam) * sizeof(PoolNode),
-                        st->block + off + stream_nodes(st->cap_frames, beam) * sizeof(PoolNode), used * sizeof(int), hipMemcpyDeviceToDevice));
-      HIP_TRY(hipMemset(nb + stream_thi_offset(cap, beam), 0, stream_nodes(cap, beam) * sizeof(int)));
-      HIP_TRY(hipMemcpy(nb + stream_thi_offset(cap, beam), st->block + stream_thi_offset(st->cap_frames, beam), used * sizeof(int), hipMemcpyDeviceToDevice));
-      (void)hipFree(st->block);
-      st->block = nb;
-      st->bytes = bytes;
-      st->cap_frames = cap;
+    // nodes the pool may hold once the chunk is in (frames * beam + 1 for a stream that was never compacted)
+    const long long need = cc::pool_bound(st->frames + len, st->base_nodes, st->base_frames, beam);
+    const bool fits = need <= cc::pool_capacity(st->cap_frames, beam);
+    if (!fits && d->compact_min_nodes > 0 && st->frames > st->base_frames && st->device == d->device &&
+        cc::pool_bound(st->frames, st->base_nodes, st->base_frames, beam) >= d->compact_min_nodes) {
+      compact_first.push_back(st);
+      compact_item.push_back(b);
+      continue;
+    }
+    if (need > 0x7fffffffLL) return fail(CTCD_EUNSUPPORTED, "stream too long for this beam width");
+    if (!fits) {
+      const int rc = stream_grow(st, need, stream);
+      if (rc) return rc;
     }
   }
+  if (!compact_first.empty()) {
+    int rc = compact_streams(d, compact_first.data(), (int)compact_first.size(), nullptr, stream);
+    if (rc) return rc;
+    for (size_t i = 0; i < compact_first.size(); ++i) {
+      ctcd_stream *st = compact_first[i];
+      const long long need = cc::pool_bound(st->frames + lens[compact_item[i]], st->base_nodes, st->base_frames, beam);
+      if (need > 0x7fffffffLL) return fail(CTCD_EUNSUPPORTED, "stream too long for this beam width");
+      if (need > cc::pool_capacity(st->cap_frames, beam) && (rc = stream_grow(st, need, stream))) return rc;
+    }
+  }
+  return CTCD_OK;
+}
+
+int ctcd_stream_compact(ctcd_decoder *d, ctcd_stream **states, int B, int32_t *live_nodes_host, void *stream_) {
+  if (!d || B < 0 || (B > 0 && !states)) return fail(CTCD_EINVAL, "bad arguments");
+  if (B == 0) return CTCD_OK;
+  CTC_ON_DEVICE(d->device);
+  const unsigned long long call_id = ++g_stream_call_id;
+  for (int b = 0; b < B; ++b) {
+    ctcd_stream *st = states[b];
+    if (!st || st->device != d->device || st->beam != states[0]->beam || st->V != states[0]->V)
+      return fail(CTCD_EINVAL, "stream state does not match the decoder configuration");
+    if (st->scorer != states[0]->scorer) return fail(CTCD_EINVAL, "the streams of one batch must share their scorer");
+    if (st->seen_in_call == call_id) return fail(CTCD_EINVAL, "the same stream state appears twice in one batch");
+    st->seen_in_call = call_id;
+  }
+  return compact_streams(d, states, B, live_nodes_host, (hipStream_t)stream_);
+}
+
+long long ctcd_stream_pool_nodes(const ctcd_stream *st) {
+  return st ? ctccompact::pool_bound(st->frames, st->base_nodes, st->base_frames, st->beam) : -1;
+}
+long long ctcd_stream_pool_capacity(const ctcd_stream *st) { return st ? ctccompact::pool_capacity(st->cap_frames, st->beam) : -1; }
+long long ctcd_stream_bytes(const ctcd_stream *st) { return st ? (long long)st->bytes : -1; }
+
+int ctcd_set_stream_compaction(ctcd_decoder *d, long long min_nodes) {
+  if (!d || min_nodes < 0) return fail(CTCD_EINVAL, "the compaction threshold is a node count (0: off)");
+  d->compact_min_nodes = min_nodes;
   return CTCD_OK;
 }
 

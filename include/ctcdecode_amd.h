@@ -266,6 +266,31 @@ int ctcd_stream_peek(ctcd_decoder *dec, ctcd_stream **states, int B, int n_best,
                      float *out_scores, int32_t *out_lens /* DEVICE [B, n_best] */,
                      int32_t *n_results, int32_t *stable_lens /* DEVICE [B] */, void *stream);
 
+/* Compaction of parked streams (extension; the reference frees a trie node as soon as no beam prefix hangs below it,
+ * path_trie.cpp remove()).  A stream's node pool is append-only and sized for frames * beam + 1 nodes; the nodes a later chunk, peek
+ * or stream end can reach are the ancestors of the current beam entries.  ctcd_stream_compact keeps exactly those per stream -- the
+ * root, then every entry's own part of its path in beam order -- drops the rest and rewrites every stored pool index.  Nothing a
+ * later call computes changes: chunks, ctcd_stream_peek and the stream-ending call give bit-identical results whether or not, how
+ * often and at which chunk boundaries a stream was compacted.  live_nodes_host[b] (HOST, or NULL) receives the nodes stream b keeps
+ * (1 for a stream without frames: the root; such a stream is left as it is).  Afterwards the stream's pool count is bounded by
+ * live + (frames fed since) * beam (ctcd_stream_pool_nodes): the "stream too long for this beam width" refusal applies to that
+ * bound, not to frames * beam.  A stream whose new need -- max(the capacity it was created with, 2 * live) nodes -- is at most a
+ * quarter of its pool's capacity moves to a block of that size (ctcd_stream_bytes falls); every other stream keeps its block.
+ * Queued on `stream` behind the chunks already queued there (ctcd_stream_decode calls nobody has checked yet included), and
+ * synchronous: the node counts come back before the new layouts are written.  Streams behind the built-in scorer and behind a
+ * callback scorer are compacted like any other (the scorer is not touched).
+ * CTCD_EINVAL: a state that is not this decoder's (device) or differs from states[0] in beam or V, a state twice in the batch,
+ * streams with different scorers.  CTCD_EINTERNAL: a parked state no decode wrote (that stream's block is unchanged). */
+int ctcd_stream_compact(ctcd_decoder *dec, ctcd_stream **states, int B, int32_t *live_nodes_host /* [B] or NULL */, void *stream);
+/* upper bound of the stream's pool count | nodes its pool holds | bytes of its HBM block (-1: st == NULL) */
+long long ctcd_stream_pool_nodes(const ctcd_stream *st);
+long long ctcd_stream_pool_capacity(const ctcd_stream *st);
+long long ctcd_stream_bytes(const ctcd_stream *st);
+/* Policy of the streaming calls on this decoder: min_nodes > 0 -- a stream whose chunk does not fit its pool and whose bound is at
+ * least min_nodes is compacted first (all such streams of the call together) and grows by doubling only if the chunk still does
+ * not fit; 0 (the default): it doubles, as without this call.  With the policy on, a stream's memory follows its live set. */
+int ctcd_set_stream_compaction(ctcd_decoder *dec, long long min_nodes);
+
 /* Host check of the per-item status words written by the last ctcd_beam_decode (synchronises the device). */
 int ctcd_check_status(ctcd_decoder *dec, int B);
 /* ... without blocking: enqueues the copy of the B status words (0 = ok) into `host_status` (page-locked memory) on
