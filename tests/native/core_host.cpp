@@ -686,6 +686,73 @@ extern "C" int ctccore_decode_chunked_pruned_f32(const float *probs, int B, int 
   return 1;
 }
 
+// A stream handed from one instantiation of the core to another between chunks (tests/stream_matrix_util.py HAND_OVERS: what a
+// serving process does when the batch size crosses the CU count, the shape statistic flips the subtree search, or a switch is
+// changed): ctccore_decode_chunked_f32 / _pruned_f32 with an instantiation per chunk, inst[c] in
+//   0  the run-time layout                        decode_utterance<IDENT>
+//   1  the fixed layout                           decode_utterance<IDENT, 1>           (beam <= 128, <= 32 labels)
+//   2  the fixed layout's far-replay build        decode_utterance<IDENT, 1, false, false, true> on carve<0, true>: what OCC2 runs
+//   3  the pruned default's class                 decode_utterance<false, 2>            (pruned calls within kMidK / kMidVc / kMidV)
+// Pruned when cutoff_prob / cutoff_top_n prune (as decode_impl decides).  seq_lens (or null: T each): item b's chunk is
+// clip(len_b - lo, 0, hi - lo) frames long, as the streaming entry's per-chunk seq_lens; every stream ends at the last chunk.
+// Returns 1, -status of a chunk that failed, or 0 for an instantiation the shape does not allow.
+extern "C" int ctccore_decode_chunked_mixed_f32(const float *probs, const int32_t *seq_lens, int B, int T, int V, int beam, double cutoff_prob,
+                                                int cutoff_top_n, int blank_id, const int32_t *bounds, int nchunks, const int32_t *inst,
+                                                int32_t *out_tokens, int32_t *out_timesteps, float *out_scores, int32_t *out_lens,
+                                                int32_t *n_results) {
+  using namespace ctcbeam;
+  const bool pruned = std::log(cutoff_prob) < 0.0 || cutoff_top_n < V;
+  Dims d;
+  d.K = beam; d.V = V; d.Vc_max = pruned ? std::min(V, cutoff_top_n) : V; d.use_rank_table = pruned ? 1 : 0; d.lm = 0;
+  const bool small = beam <= kSmallK && V <= kSmallV, mid = pruned && !small && beam <= kMidK && d.Vc_max <= kMidVc && V <= kMidV;
+  for (int c = 0; c < nchunks; ++c)
+    if (inst[c] < 0 || inst[c] > 3 || ((inst[c] == 1 || inst[c] == 2) && !small) || (inst[c] == 3 && !mid)) return 0;
+  // the compile-time layouts' workspaces are cut for their class, not for the call (decode_kernel.h)
+  auto layout_dims = [&d](int id) { return id == 3 ? mid_layout_dims() : id ? fixed_layout_dims() : d; };
+  Work w;
+  size_t mem_bytes = 0, far_bytes = 0;
+  for (int c = 0; c < nchunks; ++c) {
+    size_t fb = 0;
+    const Dims cd = layout_dims(inst[c]);
+    mem_bytes = std::max(mem_bytes, inst[c] == 2 ? carve<0, true>(w, nullptr, nullptr, cd, &fb) : carve<0>(w, nullptr, nullptr, cd, &fb));
+    far_bytes = std::max(far_bytes, fb);
+  }
+  std::vector<char> mem(mem_bytes + 64), far(far_bytes + 64);
+  std::vector<int> pcnt(T), pch((size_t)T * d.Vc_max);
+  std::vector<float> plp((size_t)T * d.Vc_max);
+  for (int b = 0; b < B; ++b) {
+    std::vector<PoolNode> pool((size_t)1 + (size_t)beam * T);
+    std::vector<int> pool_up(2 * pool.size());
+    std::vector<int> hdr(SH_WORDS, 0), arrays((size_t)kStateArrays * beam, 0);
+    const int len_b = seq_lens ? std::max(0, std::min(seq_lens[b], T)) : T;
+    if (pruned)
+      for (int t = 0; t < len_b; ++t)
+        prune_row(probs + ((size_t)b * T + t) * V, V, cutoff_prob, cutoff_top_n, &pcnt[t], &pch[(size_t)t * d.Vc_max], &plp[(size_t)t * d.Vc_max]);
+    for (int c = 0; c < nchunks; ++c) {
+      const int lo = bounds[c], hi = bounds[c + 1], len = std::max(0, std::min(len_b - lo, hi - lo));
+      std::fill(mem.begin(), mem.end(), (char)0x5a);  // a fresh workspace every chunk, as a new kernel launch would have
+      std::fill(far.begin(), far.end(), (char)0x5a);
+      if (inst[c] == 2) carve<0, true>(w, mem.data(), far.data(), layout_dims(2), nullptr);
+      else carve<0>(w, mem.data(), far.data(), layout_dims(inst[c]), nullptr);
+      HostX x;
+      StreamState ss{hdr.data(), arrays.data(), c == nchunks - 1 ? 1 : 0};
+      const OutRefs outs{out_tokens, out_timesteps, out_scores, out_lens, n_results, beam, T, nullptr, nullptr, nullptr, nullptr, 0u, nullptr, nullptr, nullptr, nullptr, 0u};
+      const float *rows = pruned ? nullptr : probs + ((size_t)b * T + lo) * V;
+      const PrunedRows prc{pcnt.data() + lo, pch.data() + (size_t)lo * d.Vc_max, plp.data() + (size_t)lo * d.Vc_max, d.Vc_max};
+      const PrunedRows *pr = pruned ? &prc : nullptr;
+#define CTC_MIXED_ARGS x, w, d, blank_id, rows, pr, len, pool.data(), pool_up.data(), (int)pool.size(), ctcmath::host_tables().w, &outs, b, &ss
+      int st;
+      if (inst[c] == 3) st = decode_utterance<false, 2>(CTC_MIXED_ARGS);
+      else if (inst[c] == 2) st = pruned ? decode_utterance<false, 1, false, false, true>(CTC_MIXED_ARGS) : decode_utterance<true, 1, false, false, true>(CTC_MIXED_ARGS);
+      else if (inst[c] == 1) st = pruned ? decode_utterance<false, 1>(CTC_MIXED_ARGS) : decode_utterance<true, 1>(CTC_MIXED_ARGS);
+      else st = pruned ? decode_utterance<false>(CTC_MIXED_ARGS) : decode_utterance<true>(CTC_MIXED_ARGS);
+#undef CTC_MIXED_ARGS
+      if (st != ST_OK) return -st;
+    }
+  }
+  return 1;
+}
+
 // Small helpers of beam_core.h checked exhaustively / on random patterns (tests/test_core_host.py).  Returns the
 // number of violations found.
 extern "C" long long ctccore_check_helpers(unsigned long long seed, long long n_random) {

@@ -384,3 +384,29 @@ def decode_core_host_chunked_pruned(probs, bounds, beam=100, cutoff_prob=1.0, cu
     if rc != 1:
         raise RuntimeError("core returned %d" % rc)
     return dict(tokens=tok, timesteps=ts, scores=sc, lens=ln, nres=nres)
+
+
+def decode_core_host_chunked_mixed(probs, bounds, inst, seq_lens=None, beam=100, cutoff_prob=1.0, cutoff_top_n=40, blank_id=0):
+    """The host build of the core fed chunk by chunk, every chunk by an instantiation of its own (tests/native/core_host.cpp
+    ctccore_decode_chunked_mixed_f32: inst[c] in 0 run-time layout / 1 fixed layout / 2 its far-replay build / 3 the pruned default's
+    class).  bounds: ALL chunk boundaries, 0 first and T last (a repeated bound is an empty chunk); seq_lens: a ragged batch."""
+    probs = np.ascontiguousarray(probs, dtype=np.float32)
+    B, T, V = probs.shape
+    bounds = np.ascontiguousarray(bounds, dtype=np.int32)
+    inst = np.ascontiguousarray(inst, dtype=np.int32)
+    assert bounds[0] == 0 and bounds[-1] == T and len(inst) == len(bounds) - 1
+    if seq_lens is not None:
+        seq_lens = np.ascontiguousarray(seq_lens, dtype=np.int32)
+    tok = np.zeros((B, beam, T), np.int32)
+    ts = np.zeros((B, beam, T), np.int32)
+    sc = np.zeros((B, beam), np.float32)
+    ln = np.zeros((B, beam), np.int32)
+    nres = np.zeros((B,), np.int32)
+    fn = ctypes.CDLL(build_core_host()).ctccore_decode_chunked_mixed_f32
+    fn.argtypes = [_f32p, _i32p] + [ctypes.c_int] * 4 + [ctypes.c_double, ctypes.c_int, ctypes.c_int, _i32p, ctypes.c_int, _i32p, _i32p, _i32p, _f32p,
+                                                         _i32p, _i32p]
+    rc = fn(_ptr(probs, _f32p), _ptr(seq_lens, _i32p), B, T, V, beam, cutoff_prob, cutoff_top_n, blank_id, _ptr(bounds, _i32p), len(bounds) - 1,
+            _ptr(inst, _i32p), _ptr(tok, _i32p), _ptr(ts, _i32p), _ptr(sc, _f32p), _ptr(ln, _i32p), _ptr(nres, _i32p))
+    if rc != 1:
+        raise RuntimeError("core returned %d" % rc)
+    return dict(tokens=tok, timesteps=ts, scores=sc, lens=ln, nres=nres)

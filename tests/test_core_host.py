@@ -231,6 +231,35 @@ def test_core_streaming_equals_one_shot():
         ou.assert_same(ou.decode(lp, beam=K), ou.decode_core_host_chunked(lp, bounds, beam=K), "chunks %s" % bounds)
 
 
+def _stream_matrix_host_cases():
+    import stream_matrix_util as sm
+
+    by_kernel = dict((e["kernel"], e) for e in sm.STREAM_CASES if not e["production"])
+    return [(by_kernel[k], x, y) for k, x, y in sm.HOST_HAND_OVERS]
+
+
+@pytest.mark.parametrize("e,x,y", _stream_matrix_host_cases(), ids=["%s-%d-%d" % ("k%d%d%d%d_%d_lm%d_occ%d" % e["kernel"], x, y) for e, x, y in _stream_matrix_host_cases()])
+def test_core_stream_hand_over_between_instantiations(e, x, y):
+    """The streamed kernel matrix's inputs and chunk bounds (tests/stream_matrix_util.py: ragged, ties, the overflow frames split by a
+    boundary, an empty chunk, a boundary behind the -inf frame) on the host twin: every chunk by instantiation x, every chunk by y,
+    and the stream handed from one to the other at the T // 2 bound, in both directions -- each equal to the oracle's one-shot
+    decode of the ragged batch.  (CTC_ASSUME_CHECKED build: a bound the parked state breaks for the next instantiation fails here.)"""
+    import kernel_matrix_util as km
+    import stream_matrix_util as sm
+
+    c = e["case"]
+    lp, sl = km.inputs(c)
+    kw = sm.oracle_args(c)
+    want = ou.decode(lp, sl, which="restated", **kw)
+    if ou.have_reference():
+        ou.assert_same(ou.decode(lp, sl, which="reference", **kw), want, "the two oracles")
+    b = sm.bounds(e)
+    n, m = len(b) - 1, sm.mid_index(e)
+    for inst in ([x] * n, [y] * n, [x] * m + [y] * (n - m), [y] * m + [x] * (n - m)):
+        got = ou.decode_core_host_chunked_mixed(lp, b, inst, seq_lens=sl, **kw)
+        ou.assert_same(got, want, "%s bounds %s instantiations %s" % (sm.entry_id(e), b, inst))
+
+
 def test_core_time_steps_beyond_16_bits():
     """A pool node packs its label and the low 16 bits of its time step into one word (12-byte nodes); launches that can pass
     frame 65535 keep the high bits in a side array.  One-shot and streamed across the boundary."""

@@ -65,20 +65,31 @@ def _peek_view(res, b):
     return dict(tokens=tok[b].numpy(), timesteps=ts[b].numpy(), scores=scores, lens=lens, nres=max(nres, 1), stable=int(stable[b]))
 
 
-def _walk_device(torch_mod, lp, kw, every, chunk=10, labels=None, lm=None, scorer=None, which=None, late=2, frames_hint=0, peeks=True):
+def _walk_device(torch_mod, lp, kw, every, chunk=10, labels=None, lm=None, scorer=None, which=None, late=2, frames_hint=0, peeks=True,
+                 bounds=None, seq_lens=None, configure=None, kernel=None, layout=None, decoder_scorer=None, check=False):
     """B streams, the last one `late` chunks younger than the others, and one more that is never fed.  Chunks go in with check=False;
     after every `every`-th call ALL streams are compacted together, twice: kept nodes and pool bound against the oracle's live set at
-    each stream's own age.  Peeks (n_best in {1, K}, since in {0, stable}) after every call; every stream's end against the one-shot."""
+    each stream's own age.  Peeks (n_best in {1, K}, since in {0, stable}) after every call; every stream's end against the one-shot.
+
+    bounds: the chunk boundaries (default: every `chunk` frames; an empty chunk is fed as one); seq_lens: per-item lengths of a ragged
+    batch (every chunk then carries its own seq_lens).  configure(dec): sets the new decoder's switches; kernel / layout: what
+    last_kernel() / last_layout() must report after every chunk that held a frame.  decoder_scorer: a CallbackScorer for the decoder
+    (`scorer` stays the oracle's); kw may also hold blank_id and cutoff_prob, for the decoder and the oracle alike."""
     import ctcdecode_amd
 
     which = which or pu.which_oracle()
     B, T, V = lp.shape
     K = kw["beam"]
     labels = labels or [str(i) for i in range(V)]
-    dkw = dict(beam_width=K, cutoff_top_n=kw.get("cutoff_top_n", 40), blank_id=0, log_probs_input=True, device="cuda:0")
-    if lm is not None:
+    dkw = dict(beam_width=K, cutoff_top_n=kw.get("cutoff_top_n", 40), cutoff_prob=kw.get("cutoff_prob", 1.0), blank_id=kw.get("blank_id", 0),
+               log_probs_input=True, device="cuda:0")
+    if decoder_scorer is not None:
+        dkw.update(scorer=decoder_scorer)
+    elif lm is not None:
         dkw.update(model_path=lm[2], alpha=lm[0], beta=lm[1])
     dec = ctcdecode_amd.OnlineCTCBeamDecoder(labels, **dkw)
+    if configure is not None:
+        configure(dec)
     states = [_state(dec, frames_hint) for _ in range(B)]
     idle = _state(dec, frames_hint)
     x = torch_mod.from_numpy(lp).to("cuda:0")
@@ -89,18 +100,32 @@ def _walk_device(torch_mod, lp, kw, every, chunk=10, labels=None, lm=None, score
             cache[(b, F)] = pu.oracle_prefix(lp[b:b + 1], F, which, scorer=scorer, **kw)
         return cache[(b, F)]
 
-    frames = [0] * B
-    steps = T // chunk
-    assert steps * chunk == T and steps > late
+    if bounds is None:
+        assert (T // chunk) * chunk == T
+        bounds = list(range(0, T + 1, chunk))
+    assert bounds[0] == 0 and bounds[-1] == T
+    item_len = [T] * B if seq_lens is None else [int(v) for v in seq_lens]
+    frames = [0] * B  # frames a stream has decoded
+    pos = [0] * B     # rows of its item that have been handed over (past a short item's end too)
+    steps = len(bounds) - 1
+    assert steps > late
     compacted = 0
     out = None
     for c in range(steps):
+        n = bounds[c + 1] - bounds[c]
         idx = [b for b in range(B) if b < B - 1 or c >= late]
-        rows = torch_mod.stack([x[b, frames[b]:frames[b] + chunk] for b in idx])
+        rows = torch_mod.stack([x[b, pos[b]:pos[b] + n] for b in idx])
+        lens = [max(0, min(item_len[b] - pos[b], n)) for b in idx]
         end = c == steps - 1
-        out = dec.decode(rows, [states[b] for b in idx], [end] * len(idx), check=False)
-        for b in idx:
-            frames[b] += chunk
+        out = dec.decode(rows, [states[b] for b in idx], [end] * len(idx), seq_lens=None if seq_lens is None else torch_mod.tensor(lens, dtype=torch_mod.int32),
+                         check=check)
+        if n > 0 and kernel is not None:
+            assert dec.last_kernel() == tuple(kernel), "chunk %d launched %s, expected %s" % (c, dec.last_kernel(), tuple(kernel))
+        if n > 0 and layout is not None:
+            assert dec.last_layout() == layout
+        for i, b in enumerate(idx):
+            pos[b] += n
+            frames[b] += lens[i]
         if end:
             break
         if c % every == every - 1:
