@@ -1037,6 +1037,50 @@ class OnlineCTCBeamDecoder(object):
             _native.check(_native.lib.ctcd_check_status(self._handle, unchecked))
         return [int(v) for v in live]
 
+    def commit(self, states):
+        """Hand out the final labels of live streams and drop them from the streams (extension): of the ``stable_lens`` labels every
+        hypothesis of a stream shares (see ``peek``), all but the last are returned -- once -- and their trie nodes leave the node
+        pool together with the dead ones (see ``compact``).  Returns a list of ``(tokens, timesteps)`` int32 CPU tensors, one pair
+        per stream: the labels committed by THIS call with their absolute time steps; the caller keeps the transcript, the library
+        does not.  From then on ``peek`` (lengths, ``since``, ``stable_lens``) and the stream-ending ``decode`` report every row
+        without its first ``DecoderState.committed_len`` labels: committed ++ reported row is the reference's row, scores and row
+        order unchanged.  A stream with nothing new to commit is compacted.  Works behind ``decode(..., check=False)`` chunks;
+        synchronous.  Streams with a scorer raise ``NotImplementedError`` (their scores use a prefix's absolute length)."""
+        B = len(states)
+        if B == 0:
+            return []
+        ptrs = (ctypes.c_void_p * B)(*[st._ptr(self) for st in states])
+        counts = (ctypes.c_int32 * B)()
+        made = {}
+
+        def alloc(_user, _R, L, p_tok, p_ts):
+            try:
+                made["tok"] = torch.zeros((B, L), dtype=torch.int32)
+                made["ts"] = torch.zeros((B, L), dtype=torch.int32)
+                p_tok[0] = made["tok"].data_ptr()
+                p_ts[0] = made["ts"].data_ptr()
+                return 0
+            except Exception as e:  # (reported through the return code: no exception crosses the C frame)
+                made["error"] = e
+                return 1
+
+        cb = _native.RESULT_ALLOC_FN(alloc)
+        with torch.cuda.device(self._device):
+            stream = torch.cuda.current_stream(self._device).cuda_stream
+            rc = _native.lib.ctcd_stream_commit(self._handle, ptrs, B, cb, None, counts, None, None, stream)
+            if "error" in made:
+                raise made["error"]
+            self._check(rc)
+            # (the call has waited for the chunks queued in front of it: their status words are looked at now, as peek() does)
+            unchecked, self._unchecked = getattr(self, "_unchecked", 0), 0
+            _native.check(_native.lib.ctcd_check_status(self._handle, unchecked))
+        # (rows of the two [B, L] tensors the allocator made; a stream that committed nothing gets the one pair of empty tensors)
+        none = (made["tok"][0, :0], made["ts"][0, :0])
+        if made["tok"].shape[1] == 0:
+            return [none] * B
+        rows_tok, rows_ts = made["tok"].unbind(0), made["ts"].unbind(0)
+        return [(rows_tok[b][:n], rows_ts[b][:n]) if n else none for b, n in enumerate(counts)]
+
     def character_based(self):
         return bool(_native.lib.ctcd_scorer_is_character_based(self._scorer.handle)) if self._scorer else None
 
@@ -1081,6 +1125,11 @@ class DecoderState(object):
     def nbytes(self):
         """Bytes of HBM the stream's block holds now (it doubles as the stream grows; ``OnlineCTCBeamDecoder.compact`` can shrink it)."""
         return int(_native.lib.ctcd_stream_bytes(self.state))
+
+    @property
+    def committed_len(self):
+        """Labels ``OnlineCTCBeamDecoder.commit`` has handed out for this stream so far: what it reports now counts from there."""
+        return int(_native.lib.ctcd_stream_committed(self.state))
 
     @property
     def pool_nodes(self):

@@ -31,6 +31,7 @@
 #include "compact_results.h"
 #include "stream_peek.h"
 #include "stream_compact.h"
+#include "stream_commit.h"
 
 namespace {
 
@@ -1411,6 +1412,7 @@ struct ctcd_stream {
   // base_nodes + (frames - base_frames) * beam; (1, 0) until the first one: frames * beam + 1
   long long base_nodes = 1, base_frames = 0;
   long long hint_frames = 0;  // the capacity the stream was created with: a compacted stream does not shrink below it
+  long long committed = 0;    // ctcd_stream_commit (stream_commit.h): labels handed out so far -- everything the stream reports counts from there
 };
 
 // The external scorer (ctcdecode/src/scorer.h:41-110, created by paddle_get_scorer, binding.cpp:143-150): built on the host
@@ -2957,6 +2959,154 @@ int ctcd_stream_compact(ctcd_decoder *d, ctcd_stream **states, int B, int32_t *l
   }
   return compact_streams(d, states, B, live_nodes_host, (hipStream_t)stream_);
 }
+
+// Commits the final labels of B parked scorer-free streams of one beam width and drops their trunks (stream_commit.h), behind whatever
+// is queued on `stream`: count -> the host sizes scratch and results (the allocator is called here) and decides which streams move
+// to a smaller block -> gather -> store -> the labels come over.  The caller has checked the states.  Synchronous; shares the
+// compaction's scratch and page-locked region.
+static int commit_streams(ctcd_decoder *d, ctcd_stream **sts, int B, ctcd_result_alloc_fn alloc, void *alloc_user, int32_t *counts_out,
+                          int32_t *live_out, int *out_L, hipStream_t stream) {
+  namespace cc = ctccompact;
+  namespace cm = ctccommit;
+  std::lock_guard<std::mutex> lock(d->mu);
+  const int beam = sts[0]->beam;
+  if (cc::compact_lds_bytes(beam) + 1024 > (size_t)d->max_lds)
+    return fail(CTCD_EUNSUPPORTED, "stream commit: the layout arrays of this beam width exceed one workgroup's LDS");
+  const size_t n = (size_t)B, o_dst = n * 8, o_scr = 2 * n * 8, o_lab = 3 * n * 8, o_cap = 4 * n * 8, o_dcap = o_cap + n * 4, o_live = o_dcap + n * 4,
+               o_stat = o_live + n * 4, o_drop = o_stat + n * 4, need = o_drop + n * 4;
+  if (d->h_cp_cap < need) {
+    if (d->h_cp) (void)hipHostFree(d->h_cp);
+    d->h_cp = nullptr;
+    d->h_cp_cap = 0;
+    HIP_TRY(hipHostMalloc((void **)&d->h_cp, 2 * need, hipHostMallocMapped | hipHostMallocCoherent));
+    d->h_cp_cap = 2 * need;
+  }
+  char *hb = d->h_cp, *db = nullptr;
+  HIP_TRY(hipHostGetDevicePointer((void **)&db, hb, 0));
+  char **h_blk = (char **)hb, **h_dst = (char **)(hb + o_dst);
+  long long *h_scr = (long long *)(hb + o_scr), *h_lab = (long long *)(hb + o_lab);
+  int *h_cap = (int *)(hb + o_cap), *h_dcap = (int *)(hb + o_dcap);
+  volatile int *h_live = (volatile int *)(hb + o_live), *h_stat = (volatile int *)(hb + o_stat), *h_drop = (volatile int *)(hb + o_drop);
+  for (int b = 0; b < B; ++b) {
+    h_blk[b] = h_dst[b] = sts[b]->block;
+    h_cap[b] = h_dcap[b] = (int)cc::pool_capacity(sts[b]->cap_frames, beam);
+    h_scr[b] = h_lab[b] = 0;
+    h_live[b] = -1;  // ("no result": a workgroup that never ran cannot read back as a count)
+    h_drop[b] = 0;
+    h_stat[b] = cc::COMPACT_OK;
+  }
+  cm::CommitLaunch l;
+  l.ctl.c = cc::CompactCtl{(char *const *)db, (const int *)(db + o_cap), (int *)(db + o_live), (int *)(db + o_stat), (char *const *)(db + o_dst),
+                           (const int *)(db + o_dcap), (const long long *)(db + o_scr)};
+  l.ctl.drop = (int *)(db + o_drop);
+  l.ctl.lab = (const long long *)(db + o_lab);
+  l.scratch = nullptr;
+  l.pool_off = (long long)stream_pool_offset(beam);
+  l.B = B; l.K = beam;
+  int e = cm::launch_commit_count(l, (void *)stream);
+  if (e != (int)hipSuccess) return fail(CTCD_EHIP, std::string("ctc_stream_commit_count_kernel: ") + hipGetErrorString((hipError_t)e));
+  HIP_TRY(hipStreamSynchronize(stream));
+  long long total = 0, labels = 0;
+  int L = 0, bad = -1;
+  for (int b = 0; b < B; ++b) {
+    const int M = h_live[b], D = h_drop[b];
+    if (M < 0 || D < 0 || (M > 0 && D >= M))
+      return fail(CTCD_EINTERNAL, "ctcd_stream_commit: the parked state of item " + std::to_string(b) + " is not one a decode wrote");
+    h_scr[b] = total;
+    total += (long long)cc::compact_out_ints(M > 0 ? M - D : 0);
+    L = D > L ? D : L;
+  }
+  for (int b = 0; b < B; ++b) {  // the labels behind the layouts: tokens, then time steps, per stream
+    h_lab[b] = total + labels;
+    labels += 2LL * h_drop[b];
+  }
+  int32_t *r_tok = nullptr, *r_ts = nullptr;
+  if (alloc(alloc_user, 1, L, &r_tok, &r_ts) != 0) return fail(CTCD_EINVAL, "the result allocator failed");
+  if (L > 0 && (!r_tok || !r_ts)) return fail(CTCD_EINVAL, "the result allocator returned no buffers");
+  if (total > 0) {
+    int rc;
+    const size_t want = (size_t)(total + labels) * 4;
+    if (want > d->cp_scratch.cap && (rc = d->cp_scratch.ensure(want + want / 4)))  // (a quarter of headroom)
+      return rc;
+    l.scratch = (int *)d->cp_scratch.p;
+    // a stream whose live set needs at most a quarter of its block moves to a smaller one: the only allocation of the call
+    std::vector<std::pair<char *, long long>> moved((size_t)B, {nullptr, 0});
+    auto drop_moved = [&] { for (auto &m : moved) if (m.first) (void)hipFree(m.first); };
+    for (int b = 0; b < B; ++b) {
+      const int M = h_live[b] > 0 ? h_live[b] - h_drop[b] : 0;
+      const long long nf = M > 0 ? cc::shrunk_cap_frames(sts[b]->cap_frames, sts[b]->hint_frames, M, beam) : 0;
+      if (!nf) continue;
+      char *nb = nullptr;
+      const hipError_t me = hipMalloc((void **)&nb, stream_block_bytes(nf, beam));
+      if (me != hipSuccess) { drop_moved(); return fail(CTCD_EHIP, std::string("hipMalloc: ") + hipGetErrorString(me)); }
+      moved[b] = {nb, nf};
+      h_dst[b] = nb;
+      h_dcap[b] = (int)cc::pool_capacity(nf, beam);
+    }
+    e = cm::launch_commit_move(l, (void *)stream);
+    if (e == (int)hipSuccess) e = (int)hipStreamSynchronize(stream);
+    if (e != (int)hipSuccess) { drop_moved(); return fail(CTCD_EHIP, std::string("ctc_stream_commit kernels: ") + hipGetErrorString((hipError_t)e)); }
+    std::vector<int32_t> lab((size_t)labels);
+    if (labels > 0) {
+      const hipError_t ce = hipMemcpy(lab.data(), l.scratch + total, (size_t)labels * 4, hipMemcpyDeviceToHost);
+      if (ce != hipSuccess) { drop_moved(); return fail(CTCD_EHIP, std::string("hipMemcpy: ") + hipGetErrorString(ce)); }
+    }
+    for (int b = 0; b < B; ++b) {
+      ctcd_stream *st = sts[b];
+      const int M = h_live[b], D = h_drop[b];
+      if (M <= 0) continue;
+      if (h_stat[b] != cc::COMPACT_OK) {  // a walk left the pool: that stream's block is as it was, nothing of it is committed
+        if (bad < 0) bad = b;
+        if (moved[b].first) (void)hipFree(moved[b].first);
+        h_drop[b] = 0;
+        h_live[b] = -1;
+        continue;
+      }
+      if (moved[b].first) {
+        (void)hipFree(st->block);
+        st->block = moved[b].first;
+        st->cap_frames = moved[b].second;
+        st->bytes = stream_block_bytes(st->cap_frames, beam);
+      }
+      st->base_nodes = M - D;
+      st->base_frames = st->frames;
+      st->committed += D;
+      const int32_t *src = lab.data() + (h_lab[b] - total);
+      for (int i = 0; i < D; ++i) { r_tok[(size_t)b * L + i] = src[i]; r_ts[(size_t)b * L + i] = src[D + i]; }
+    }
+  }
+  for (int b = 0; b < B; ++b) {
+    const int D = h_live[b] > 0 ? h_drop[b] : 0;
+    for (int i = D; i < L; ++i) { r_tok[(size_t)b * L + i] = 0; r_ts[(size_t)b * L + i] = 0; }
+    counts_out[b] = D;
+    if (live_out) live_out[b] = h_live[b] > 0 ? h_live[b] - h_drop[b] : (h_live[b] == 0 ? 1 : -1);  // (a stream without frames: the root alone)
+  }
+  if (out_L) *out_L = L;
+  if (bad >= 0) return fail(CTCD_EINTERNAL, "ctcd_stream_commit: the parked state of item " + std::to_string(bad) + " is not one a decode wrote (it is unchanged)");
+  return CTCD_OK;
+}
+
+int ctcd_stream_commit(ctcd_decoder *d, ctcd_stream **states, int B, ctcd_result_alloc_fn alloc, void *alloc_user, int32_t *counts_host,
+                       int32_t *live_nodes_host, int *out_L, void *stream_) {
+  if (!d || B < 0 || (B > 0 && (!states || !alloc || !counts_host))) return fail(CTCD_EINVAL, "bad arguments");
+  if (out_L) *out_L = 0;
+  if (B == 0) return CTCD_OK;
+  CTC_ON_DEVICE(d->device);
+  const unsigned long long call_id = ++g_stream_call_id;
+  for (int b = 0; b < B; ++b) {
+    ctcd_stream *st = states[b];
+    if (!st || st->device != d->device || st->beam != states[0]->beam || st->V != states[0]->V)
+      return fail(CTCD_EINVAL, "stream state does not match the decoder configuration");
+    if (st->scorer != states[0]->scorer) return fail(CTCD_EINVAL, "the streams of one batch must share their scorer");
+    if (st->seen_in_call == call_id) return fail(CTCD_EINVAL, "the same stream state appears twice in one batch");
+    st->seen_in_call = call_id;
+  }
+  // (with a scorer the result scores use a prefix's absolute depth -- finish(), lm_final_scores: a re-rooted stream would need a base depth there)
+  if (states[0]->scorer) return fail(CTCD_EUNSUPPORTED, "ctcd_stream_commit: streams with a scorer cannot drop their trunk");
+  return commit_streams(d, states, B, alloc, alloc_user, counts_host, live_nodes_host, out_L, (hipStream_t)stream_);
+}
+
+long long ctcd_stream_committed(const ctcd_stream *st) { return st ? st->committed : -1; }
 
 long long ctcd_stream_pool_nodes(const ctcd_stream *st) {
   return st ? ctccompact::pool_bound(st->frames, st->base_nodes, st->base_frames, st->beam) : -1;

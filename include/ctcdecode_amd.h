@@ -291,6 +291,30 @@ long long ctcd_stream_bytes(const ctcd_stream *st);
  * not fit; 0 (the default): it doubles, as without this call.  With the policy on, a stream's memory follows its live set. */
 int ctcd_set_stream_compaction(ctcd_decoder *dec, long long min_nodes);
 
+/* Commit of live streams' final labels (extension).  stable_len labels of every current beam entry of a stream are final
+ * (ctcd_stream_peek): ctcd_stream_commit hands all of them but the last to the caller -- once -- and drops their trie nodes, the
+ * committed trunk, together with the dead nodes: the node of the last committed label becomes the stream's root and the live set is
+ * laid out below it as ctcd_stream_compact lays it out.  Per stream b with C_b labels committed earlier (ctcd_stream_committed) and
+ * absolute stable length s_b: counts_host[b] = m_b = max(0, s_b - 1 - C_b); row b of the buffers the allocator returned holds the
+ * labels and ABSOLUTE time steps at absolute depths C_b + 1 .. C_b + m_b -- row 0 of the one-shot decode of the frames fed so far at
+ * those positions, past frame 65535 too -- and zeros behind them.  The allocator is called once, with (R = 1, L = the largest m_b of
+ * the call; *out_L receives L), before any stream is changed; it returns two int32 buffers of B * L elements (return non-zero to
+ * fail the call: nothing is committed; with L == 0 the buffers are not touched).  live_nodes_host[b] (HOST, or NULL): the nodes
+ * stream b keeps.  m_b == 0 is a plain compaction of that stream; a stream without frames is left as it is.
+ * From then on everything the stream reports counts from its new root: later chunks (on any kernel), ctcd_stream_compact,
+ * ctcd_stream_peek (lengths, `since`, stable_lens) and the stream-ending call report the one-shot decode's rows with their first
+ * C_b + m_b labels removed -- scores, result counts and row order unchanged, time steps absolute -- so committed ++ reported row is
+ * the reference's row, for every row.  The library does not keep the committed labels: the caller does.  The capacity bookkeeping is
+ * the compaction's (bound = live + frames since * beam, the move to a smaller block, the 2^31 bound).  A second commit with no frame
+ * in between commits nothing and changes no byte.  Queued on `stream` behind the chunks already queued there, and synchronous.
+ * CTCD_EINVAL as for ctcd_stream_compact.  CTCD_EUNSUPPORTED: streams with a scorer, built-in or callback (their result scores use
+ * a prefix's absolute depth); no state of the call is changed.  CTCD_EINTERNAL: a parked state no decode wrote (that stream's block
+ * is unchanged and nothing of it is committed). */
+int ctcd_stream_commit(ctcd_decoder *dec, ctcd_stream **states, int B, ctcd_result_alloc_fn alloc, void *alloc_user,
+                       int32_t *counts_host /* [B] */, int32_t *live_nodes_host /* [B] or NULL */, int *out_L /* or NULL */, void *stream);
+/* labels the stream has committed so far (-1: st == NULL) */
+long long ctcd_stream_committed(const ctcd_stream *st);
+
 /* Host check of the per-item status words written by the last ctcd_beam_decode (synchronises the device). */
 int ctcd_check_status(ctcd_decoder *dec, int B);
 /* ... without blocking: enqueues the copy of the B status words (0 = ok) into `host_status` (page-locked memory) on
