@@ -22,7 +22,12 @@ follow a frame in which item 2 replayed std::nth_element (the `fin` order of tha
 test_stream_matrix_plan.py checks this on the host twin.  Where an entry's seed does not give it, MID_BOUND moves the entry's T // 2
 bound to the nearest frame that does; where neither frame 0 nor frame 2 of item 2 replays, so that moving one bound can only ever
 give one such boundary, EXTRA_BOUND adds one more boundary at the next nearest such frame (the entry keeps every bound of the
-list above)."""
+list above).
+
+The commit walks (OnlineCTCBeamDecoder.commit behind every scorer-free entry) need inputs on which a commit hands labels out:
+commit_inputs() appends an item whose confidence fades to km.inputs(c), commit_bounds() adds the boundaries of COMMIT_BOUND, the
+hand-over walks commit at hand_over_commit_mid(), and DEEP_WALKS are the walks whose paths grow past an express level.  What these
+inputs must give is proved on the oracle in test_stream_matrix_plan.py."""
 import numpy as np
 
 import kernel_matrix_util as km
@@ -223,3 +228,122 @@ def mid_index(e):
     """Index of the first chunk behind the T // 2 bound (the moved one, where MID_BOUND moves it) in bounds(e)."""
     mid = MID_BOUND.get(entry_id(e), e["case"]["T"] // 2)
     return bounds(e).index(mid)
+
+
+# ---- commits: inputs whose common prefix grows with every chunk -------------------------------------------------------------------
+# On km.inputs(c) at bounds(e) a commit hands out next to nothing (random rows: the stable prefix stays below 2 at most boundaries), so
+# the commit walks append one item whose confidence fades: the cheapest alternatives always lie in its newest frames, and what is
+# common to all beam entries grows chunk by chunk.
+FADE_FROM, FADE_TO, FADE_NOISE = 40.0, 0.5, 0.3
+
+
+def fading_item(T, V, blank, seed, fade_to=FADE_TO):
+    """[T, V] float32 log-probabilities: even frames peak on a random non-blank label, odd frames on the blank; the margin of the peak
+    over the other labels falls linearly from FADE_FROM at frame 0 to fade_to at frame T - 1 (never below 0: a steeper fade ends in
+    rows of noise alone); Gaussian noise of FADE_NOISE, then a float32 log-softmax."""
+    rng = np.random.default_rng(seed)
+    x = (np.float32(FADE_NOISE) * rng.standard_normal((T, V))).astype(np.float32)
+    others = [v for v in range(V) if v != blank]
+    for t in range(T):
+        margin = FADE_FROM + (fade_to - FADE_FROM) * t / max(1, T - 1)
+        peak = blank if t % 2 else others[int(rng.integers(0, len(others)))]
+        x[t, peak] += np.float32(max(0.0, margin))
+    m = x.max(axis=-1, keepdims=True)
+    lse = m + np.log(np.exp(x - m).sum(axis=-1, keepdims=True, dtype=np.float32), dtype=np.float32)
+    return (x - lse).astype(np.float32)
+
+
+def commit_inputs(c, labels=None):
+    """km.inputs(c) with the fading item appended at full length: (lp [B + 1, T, V], seq_lens [B + 1]).  The tie item, the degenerate
+    item and the one-frame item stay in the batch and are committed along with it."""
+    lp, sl = km.inputs(c, labels)
+    fade = fading_item(c["T"], c["V"], c["blank"], c["seed"] + 7)
+    return np.ascontiguousarray(np.concatenate([lp, fade[None]]), dtype=np.float32), np.concatenate([sl, [c["T"]]]).astype(np.int32)
+
+
+def fading_index(c):
+    """Where commit_inputs(c) puts the fading item."""
+    return c["B"]
+
+
+# entry_id -> boundaries added to bounds(e) for the commit walk, so that at least two commits (one after every chunk but the last) hand
+# the fading item a label and row 0 still keeps two at the end (held by test_stream_matrix_plan.py::test_commit_walk_commits_twice)
+COMMIT_BOUND = {"k0101_1024_lm0_occ0": (19,), "k0101_0_lm0_occ0": (19,), "k0200_0_lm0_occ0": (16,), "k0201_0_lm0_occ0": (16,)}
+
+
+def commit_bounds(e):
+    """Chunk bounds of an entry's commit walk: bounds(e) and the entry's COMMIT_BOUND."""
+    b = sorted(bounds(e) + list(COMMIT_BOUND.get(entry_id(e), ())))
+    assert len(set(b)) == len(b) - 1 and b[-1] == e["case"]["T"], b  # (the empty chunk alone repeats a bound)
+    return b
+
+
+def host_twin_builds(c):
+    """The shapes the streaming host twin decodes (tests/native/peek_host.cpp: the fixed and the run-time layout, 16-bit slot indices --
+    at most 65535 candidate slots; the build for more exists on the device alone)."""
+    return not c["lm"] and c["K"] * (min(c["V"], c["top_n"]) + 2) <= 65535
+
+
+def commit_events(lp, b, F_list, which="restated", **kw):
+    """The oracle's side of a commit walk of item b: a commit after F frames, for every F of F_list in turn, hands out
+    max(0, stable - 1 - committed) labels.  -> [(F, labels handed out, committed before)]."""
+    import peek_util as pu
+
+    out, C = [], 0
+    for F in F_list:
+        m = 0
+        if F > 0:
+            m = max(0, pu.common_prefix_len(pu.oracle_prefix(lp[b:b + 1], F, which, **kw), 0) - 1 - C)
+        out.append((F, m, C))
+        C += m
+    return out
+
+
+# A committed state across a hand-over: the streams that cross are committed at the T // 2 bound, directly before the switch.
+# hand-over name -> the bound that replaces T // 2 where the oracle commits nothing to the fading item there (none needs it: held by
+# test_stream_matrix_plan.py::test_commit_in_front_of_a_hand_over_commits)
+HAND_OVER_COMMIT_MID = {}
+
+
+def hand_over_commit_mid(h):
+    return HAND_OVER_COMMIT_MID.get(h["name"], h["case"]["T"] // 2)
+
+
+def hand_over_commit_bounds(h):
+    T = h["case"]["T"]
+    b = plain_bounds(T)
+    b[b.index(T // 2)] = hand_over_commit_mid(h)
+    assert sorted(b) == b and 3 < hand_over_commit_mid(h) < (2 * T) // 3 + 1, b
+    return b
+
+
+def hand_over_few(c):
+    """The streams of a CU count + 8 batch of commit_inputs that cross a `few` hand-over: item 0, the tie item, the degenerate item
+    and the fading item."""
+    return sorted({0, 2, km.degenerate_item(c), fading_index(c)})
+
+
+# Depth past an express level (beam_core.h kExpress = 32): at T <= 40 no path is deeper than about 20 labels, so the walks above never
+# lay a path out across an express level of the new coordinates.  One walk per key the long commit tests do not reach: two fading
+# items of DEEP_T frames whose fade is steeper (the margin reaches 0 at two fifths of the item, rows of noise alone follow: the
+# common prefix stalls there while row 0 grows on), a commit every DEEP_CHUNK frames.  seeds: offsets to the matrix case's seed, chosen
+# so that an item ends with a committed length that is no multiple of 32 and at least 33 labels of row 0 uncommitted; `deep_commit`:
+# one of its commits itself hands out labels at such a place (held by test_stream_matrix_plan.py::test_deep_walks_end_between_express_levels)
+DEEP_T, DEEP_CHUNK, DEEP_FADE_TO = 128, 16, -60.0
+DEEP_WALKS = [
+    dict(kernel=(0, 0, 1, 0, 1024, 0, 1), seeds=(15, 16), deep_commit=False),
+    dict(kernel=(3, 0, 1, 0, 1024, 0, 0), seeds=(14, 15), deep_commit=False),
+    dict(kernel=(0, 0, 2, 1, 1024, 0, 0), seeds=(12, 13), deep_commit=True),
+    dict(kernel=(0, 2, 0, 0, 0, 0, 0), seeds=(11, 15), deep_commit=False),
+]
+
+
+def deep_walk_id(d):
+    return "k%d%d%d%d_%d_lm%d_occ%d" % d["kernel"]
+
+
+def deep_inputs(d):
+    """-> (the key's matrix case, lp [2, DEEP_T, V], the chunk bounds)."""
+    c = _matrix_case(d["kernel"])
+    lp = np.stack([fading_item(DEEP_T, c["V"], c["blank"], c["seed"] + s, fade_to=DEEP_FADE_TO) for s in d["seeds"]])
+    return c, np.ascontiguousarray(lp), list(range(0, DEEP_T + 1, DEEP_CHUNK))

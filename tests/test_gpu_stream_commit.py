@@ -2,8 +2,9 @@
 hands out the oracle's row 0 at the newly final positions and keeps the oracle's live trie below the new root; afterwards every
 peek and every final result are the oracle's one-shot decode with the committed labels removed from the front of every row, bit for
 bit (streams of three ages and a stream without frames in one call, check=False chunks queued in front of it, kernels of other
-layouts and workgroup sizes continuing a committed state); a block shrinks when the rule says so; streams with a scorer are refused
-and decode on."""
+layouts and workgroup sizes continuing a committed state, commits on both sides of frame 65535); a block shrinks when the rule says
+so; streams with a scorer are refused and decode on.  _walk_device is also the walk of test_gpu_stream_matrix.py, which puts a
+committed state in front of every scorer-free instantiation of the decode kernel a stream can launch."""
 import os
 
 import commit_util as mu
@@ -33,51 +34,81 @@ def _plain_switches(dec):
     _native.check(_native.lib.ctcd_set_cu_sharing(dec._handle, 0))
 
 
-def _walk_device(torch_mod, lp, kw, every, chunk, starts=None, frames_hint=0, before=None, kernel_of=None):
+def _walk_device(torch_mod, lp, kw, every, chunk=None, starts=None, frames_hint=0, before=None, kernel_of=None, bounds=None, seq_lens=None,
+                 configure=None, kernel=None, layout=None, blank_id=0, cutoff_prob=1.0):
     """B streams, stream b first fed at call starts[b] (default 0, 1, 2, ...: streams of different ages), and one more that is never
     fed.  Chunks go in with check=False; after every `every`-th call ALL streams are committed together, twice: counts, labels, time
     steps and kept nodes against the oracle at each stream's own age; the second call commits nothing.  Peeks (n_best in {1, K},
     since in {0, stable'}) after every call against the oracle with the offset applied; every stream's end: committed ++ rows == the
     one-shot decode.  before(c, dec): called in front of call c; kernel_of(c): what last_kernel() must report after it.
+
+    bounds: the chunk boundaries instead of `chunk` (an empty chunk is fed as one); every stream is then fed from call 0 on and ends
+    at the last call.  seq_lens: per-item lengths of a ragged batch (every chunk carries its own seq_lens; a stream's age is the
+    frames of its item fed so far).  configure(dec): sets the new decoder's switches (default: _plain_switches); kernel / layout: what
+    last_kernel() / last_layout() must report after every chunk that held a frame; blank_id, cutoff_prob: for the decoder and the
+    oracle alike.  With bounds the ends are compared with both oracles where the compiled reference was built.
     -> labels committed per stream."""
     import ctcdecode_amd
 
     which = pu.which_oracle()
     B, T, V = lp.shape
     K = kw["beam"]
-    dec = ctcdecode_amd.OnlineCTCBeamDecoder([str(i) for i in range(V)], beam_width=K, cutoff_top_n=kw.get("cutoff_top_n", 40), blank_id=0,
-                                             log_probs_input=True, device="cuda:0")
-    _plain_switches(dec)
+    okw = dict(kw)
+    if blank_id != 0:
+        okw["blank_id"] = blank_id
+    if cutoff_prob != 1.0:
+        okw["cutoff_prob"] = cutoff_prob
+    dec = ctcdecode_amd.OnlineCTCBeamDecoder([str(i) for i in range(V)], beam_width=K, cutoff_top_n=kw.get("cutoff_top_n", 40), cutoff_prob=cutoff_prob,
+                                             blank_id=blank_id, log_probs_input=True, device="cuda:0")
+    if configure is None:
+        _plain_switches(dec)
+    else:
+        configure(dec)
     states = [_state(dec, frames_hint) for _ in range(B)]
     idle = _state(dec, frames_hint)
     x = torch_mod.from_numpy(lp).to("cuda:0")
     cache = {}
 
-    def want_at(b, F):
-        if (b, F) not in cache:
-            cache[(b, F)] = pu.oracle_prefix(lp[b:b + 1], F, which, **kw)
-        return cache[(b, F)]
+    def want_at(b, F, oracle=which):
+        if (b, F, oracle) not in cache:
+            cache[(b, F, oracle)] = pu.oracle_prefix(lp[b:b + 1], F, oracle, **okw)
+        return cache[(b, F, oracle)]
 
-    starts = list(range(B)) if starts is None else starts
-    assert (T // chunk) * chunk == T
-    steps = T // chunk + max(starts)
-    frames = [0] * B
+    item_len = [T] * B if seq_lens is None else [int(v) for v in seq_lens]
+    if bounds is None:
+        starts = list(range(B)) if starts is None else starts
+        assert (T // chunk) * chunk == T and seq_lens is None
+        steps = T // chunk + max(starts)
+    else:
+        assert chunk is None and starts is None and bounds[0] == 0 and bounds[-1] == T
+        starts = [0] * B
+        steps = len(bounds) - 1
+    frames = [0] * B  # frames a stream has decoded
+    pos = [0] * B     # rows of its item that have been handed over (past a short item's end too)
     tok = [np.zeros((0,), np.int32) for _ in range(B)]
     ts = [np.zeros((0,), np.int32) for _ in range(B)]
     ended = {}
     events = 0
     for c in range(steps):
-        idx = [b for b in range(B) if starts[b] <= c and frames[b] < T]
+        idx = [b for b in range(B) if starts[b] <= c and b not in ended]
         if before is not None:
             before(c, dec)
-        ends = [frames[b] + chunk == T for b in idx]
-        out = dec.decode(torch_mod.stack([x[b, frames[b]:frames[b] + chunk] for b in idx]), [states[b] for b in idx], ends, check=False)
+        n = chunk if bounds is None else bounds[c + 1] - bounds[c]
+        lens = [max(0, min(item_len[b] - pos[b], n)) for b in idx]
+        ends = [pos[b] + n == T for b in idx] if bounds is None else [c == steps - 1] * len(idx)
+        out = dec.decode(torch_mod.stack([x[b, pos[b]:pos[b] + n] for b in idx]), [states[b] for b in idx], ends,
+                         seq_lens=None if seq_lens is None else torch_mod.tensor(lens, dtype=torch_mod.int32), check=False)
         if kernel_of is not None and kernel_of(c) is not None:
             assert dec.last_kernel() == tuple(kernel_of(c)), "call %d launched %s, expected %s" % (c, dec.last_kernel(), tuple(kernel_of(c)))
+        if n > 0 and kernel is not None:
+            assert dec.last_kernel() == tuple(kernel), "call %d launched %s, expected %s" % (c, dec.last_kernel(), tuple(kernel))
+        if n > 0 and layout is not None:
+            assert dec.last_layout() == layout, "call %d ran layout %d, expected %d" % (c, dec.last_layout(), layout)
         for i, b in enumerate(idx):
-            frames[b] += chunk
+            pos[b] += n
+            frames[b] += lens[i]
             if ends[i]:
-                ended[b] = _final(out, i, K, T, want_at(b, T))
+                ended[b] = _final(out, i, K, frames[b], want_at(b, frames[b]))
         live_ones = [b for b in range(B) if b not in ended]
         if not live_ones:
             break
@@ -116,9 +147,10 @@ def _walk_device(torch_mod, lp, kw, every, chunk, starts=None, frames_hint=0, be
                                           "call %d stream %d F=%d C=%d n_best=%d since=%d" % (c, b, frames[b], len(tok[b]), nb, since[i]))
     assert sorted(ended) == list(range(B))
     for b in range(B):
-        want = want_at(b, T)
-        mu.assert_committed_prefix(want, 0, tok[b], ts[b], "stream %d: committed" % b)
-        mu.assert_final(ended[b], want, 0, len(tok[b]), "stream %d: the final result after the commits" % b)
+        for oracle in sorted({which, "restated"} if bounds is not None else {which}):
+            want = want_at(b, frames[b], oracle)
+            mu.assert_committed_prefix(want, 0, tok[b], ts[b], "stream %d: committed (%s oracle)" % (b, oracle))
+            mu.assert_final(ended[b], want, 0, len(tok[b]), "stream %d: the final result after the commits (%s oracle)" % (b, oracle))
     assert events > 0
     return [len(t) for t in tok]
 
@@ -214,6 +246,55 @@ def test_commit_device_64_streams_at_random_boundaries(torch_mod):
     for b in range(B):
         mu.assert_committed_prefix(want, b, tok[b], ts[b], "stream %d of 64: committed" % b)
         mu.assert_final(_final(out, b, K, T, dict(nres=want["nres"][b:b + 1])), want, b, len(tok[b]), "stream %d of 64" % b)
+
+
+@pytest.mark.parametrize("beam", [4, 1])
+def test_commit_device_timesteps_beyond_16_bits(torch_mod, beam):
+    """test_commit_host_timesteps_beyond_16_bits on the device, at the shape of test_time_steps_beyond_16_bits (3 labels): one stream
+    across frame 65535, chunks queued with check=False, a commit at frame 65000 and one at frame 65600 -- behind the second the
+    gather kernel assembles the committed time steps from the nodes' 16 bits and their high parts, and the kept nodes keep theirs.
+    frames_hint = 16: the live set below the new root is a few nodes, so the stream moves to a smaller block at both commits, at the
+    second one with the high parts.  Committed labels, absolute time steps (some past frame 65535), kept nodes and a full peek
+    against the oracle after each commit; the end: committed ++ rows == the one-shot decode."""
+    import ctcdecode_amd
+
+    which = pu.which_oracle()
+    T = 65536 + 300
+    lp = ou.synth_logprobs(1, T, 3, 17, blank_bias=2.5)
+    dec = ctcdecode_amd.OnlineCTCBeamDecoder(["0", "1", "2"], beam_width=beam, blank_id=0, log_probs_input=True, device="cuda:0")
+    hint = 16
+    st = _state(dec, hint)
+    x = torch_mod.from_numpy(lp).to("cuda:0")
+    tok, ts = np.zeros((0,), np.int32), np.zeros((0,), np.int32)
+    seen = 0
+    for lo, hi in ((0, 65000), (65000, 65600)):
+        dec.decode(x[:, lo:hi], [st], [False], check=False)
+        want = pu.oracle_prefix(lp, hi, which, beam=beam)
+        C = len(tok)
+        m = max(0, pu.common_prefix_len(want, 0) - 1 - C)
+        need = max(hint * beam + 1, 2 * (cu.oracle_live_count(want, 0) - (C + m)))
+        assert 4 * need <= _capacity(st), "F=%d: the inputs do not exercise the shrink rule" % hi
+        before = st.nbytes
+        (g_tok, g_ts), = dec.commit([st])
+        assert need <= _capacity(st) < need + beam and st.nbytes < before // 4, "F=%d: the block did not move to one of %d nodes" % (hi, need)
+        g_tok, g_ts = g_tok.numpy(), g_ts.numpy()
+        assert len(g_tok) == m > 0 and len(g_ts) == m, "F=%d: %d labels committed, want %d" % (hi, len(g_tok), m)
+        assert np.array_equal(g_tok, want["tokens"][0, 0, C:C + m]), "F=%d: committed tokens differ from the oracle's row 0" % hi
+        assert np.array_equal(g_ts, want["timesteps"][0, 0, C:C + m]), "F=%d: committed time steps differ from the oracle's row 0" % hi
+        tok, ts = np.concatenate([tok, g_tok]), np.concatenate([ts, g_ts])
+        assert st.committed_len == C + m and st.pool_nodes == cu.oracle_live_count(want, 0) - (C + m), "F=%d: nodes kept" % hi
+        (t2, _), = dec.commit([st])
+        assert len(t2) == 0 and st.committed_len == C + m, "F=%d: a second commit committed labels" % hi
+        res = dec.peek([st], n_best=beam)
+        pu.assert_peek_equals(_peek_view(res, 0), mu.shifted(want, 0, C + m), 0, beam, 0, "F=%d after the commit" % hi)
+        seen = int(res[2].max())
+    assert seen > 65535, "no kept node's time step lies past frame 65535"
+    assert int(ts.max()) > 65535, "no committed time step lies past frame 65535"
+    out = dec.decode(x[:, 65600:], [st], [True], check=False)
+    final = pu.oracle_prefix(lp, T, which, beam=beam)
+    mu.assert_committed_prefix(final, 0, tok, ts, "T > 65536: committed")
+    mu.assert_final(_final(out, 0, beam, T, final), final, 0, len(tok), "T > 65536 after the commits")
+    assert int(out[2].max()) > 65535
 
 
 def test_commit_device_block_shrinks_when_the_rule_says_so(torch_mod):

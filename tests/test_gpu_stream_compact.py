@@ -1,7 +1,8 @@
 """-m gpu: OnlineCTCBeamDecoder.compact on the device -- the ctc_stream_compact_* kernels on the parked states of live streams.  What
 a compaction keeps is counted against the trie the oracle's own result rows span; every peek and every final result must equal the
 oracle's one-shot decode bit for bit however often and wherever the streams were compacted (streams of different ages and a stream
-without frames in one call, check=False chunks queued in front of it); the policy bounds a long stream's memory; a block shrinks
+without frames in one call, check=False chunks queued in front of it; a stream compacted on both sides of frame 65535, where the
+time steps' high parts travel through the gather and store kernels); the policy bounds a long stream's memory; a block shrinks
 exactly when the rule says so."""
 import ctypes
 import os
@@ -286,6 +287,44 @@ def test_compact_device_block_shrinks_when_the_rule_says_so(torch_mod):
             assert dec.compact([st])[0] == live and st.nbytes == after
     want = pu.oracle_prefix(lp, T, which, beam=K)
     ou.assert_same(_final(out, 0, K, T, want), want, "after the move to a smaller block")
+
+
+def test_compact_device_timesteps_beyond_16_bits(torch_mod):
+    """test_compact_host_timesteps_beyond_16_bits on the device, at the shape of test_time_steps_beyond_16_bits (3 labels, beam 4): a
+    stream across frame 65535, chunks queued with check=False, compacted at frame 65000 and at frame 65600 -- the gather and store
+    kernels carry the high parts of the kept nodes' time steps.  A second stream of the same rows is compacted at frame 65600 alone:
+    its block has grown to 65536 frames and more, and the move to a smaller one takes nodes with high parts along (the first
+    stream's block moves at frame 65000, before any node has one).  Kept nodes and a full peek against the oracle after each
+    compaction, time steps past 65535 among them; the end against the one-shot decode."""
+    import ctcdecode_amd
+
+    which = pu.which_oracle()
+    T, K = 65536 + 300, 4
+    lp = ou.synth_logprobs(1, T, 3, 17, blank_bias=2.5)
+    dec = ctcdecode_amd.OnlineCTCBeamDecoder(["0", "1", "2"], beam_width=K, blank_id=0, log_probs_input=True, device="cuda:0")
+    sts = [ctcdecode_amd.DecoderState(dec) for _ in range(2)]
+    x = torch_mod.from_numpy(np.concatenate([lp, lp])).to("cuda:0")
+    for lo, hi, who in ((0, 65000, [0]), (65000, 65600, [0, 1])):
+        dec.decode(x[:, lo:hi], sts, [False, False], check=False)
+        want = pu.oracle_prefix(lp, hi, which, beam=K)
+        want_live = cu.oracle_live_count(want, 0)
+        moves = who[-1:]  # the stream compacted for the first time: its block holds hi frames' nodes
+        assert all(4 * 2 * want_live <= _capacity(sts[b]) for b in moves), "the inputs do not exercise the shrink rule"
+        before = [sts[b].nbytes for b in who]
+        live = dec.compact([sts[b] for b in who])
+        assert live == [want_live] * len(who) and [sts[b].pool_nodes for b in who] == live, "F=%d: %s nodes kept, want %d" % (hi, live, want_live)
+        assert all(sts[b].nbytes < n // 4 for b, n in zip(who, before) if b in moves), "F=%d: the block did not move to a smaller one" % hi
+        assert dec.compact([sts[b] for b in who]) == live, "F=%d: a second compaction changed something" % hi
+        res = dec.peek([sts[b] for b in who], n_best=K)
+        for i in range(len(who)):
+            pu.assert_peek_equals(_peek_view(res, i), want, 0, K, 0, "F=%d stream %d after the compaction" % (hi, who[i]))
+        if hi > 65536:
+            assert all(int(res[2][i].max()) > 65535 for i in range(len(who))), "no kept node's time step lies past frame 65535"
+    out = dec.decode(x[:, 65600:], sts, [True, True], check=False)
+    final = pu.oracle_prefix(lp, T, which, beam=K)
+    for b in range(2):
+        ou.assert_same(_final(out, b, K, T, final), final, "T > 65536 after the compactions (stream %d)" % b)
+    assert int(out[2].max()) > 65535
 
 
 def test_compact_device_policy_bounds_the_capacity(torch_mod):

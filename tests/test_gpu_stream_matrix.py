@@ -4,15 +4,24 @@ that reaches it through the batch size alone.  The chunks (a one-frame chunk, a 
 chunk, boundaries behind tie frames and behind the -inf frame) must each launch exactly the expected kernel, and the stream must
 end bit for bit like the oracle's one-shot decode of the ragged batch; ctc_stream_peek_kernel and the ctc_stream_compact_* kernels
 must read what that instantiation's save_state parked; and a stream handed from one kernel to another between two chunks -- as
-serving does when the batch size crosses the CU count or the shape statistic flips the subtree search -- must decode the same."""
+serving does when the batch size crosses the CU count or the shape statistic flips the subtree search -- must decode the same.
+
+Commit behind every scorer-free instantiation: the ctc_stream_commit_* kernels re-root what that instantiation parked, and its
+load_state continues the re-rooted block -- over inputs on which a commit hands out labels at several boundaries (commit_inputs: the
+matrix's items and one whose confidence fades; test_stream_matrix_plan.py proves that they do), across every scorer-free hand-over,
+and, behind four keys the long commit tests never reach, at depths past an express level."""
 import numpy as np
 import pytest
 
+import commit_util as mu
+import compact_util as cu
 import kernel_matrix_util as km
 import oracle_util as ou
+import peek_util as pu
 import stream_matrix_util as sm
 from test_gpu_decode import _with_nres
-from test_gpu_stream_compact import _walk_device
+from test_gpu_stream_commit import _walk_device as _commit_walk
+from test_gpu_stream_compact import _final, _walk_device
 
 pytestmark = pytest.mark.gpu
 
@@ -177,6 +186,31 @@ def test_peek_and_compact_behind_every_instantiation(torch_mod, wide99, monkeypa
             inner.close()
 
 
+@pytest.mark.parametrize("e", [e for e in sm.STREAM_CASES if not e["production"] and not e["case"]["lm"]], ids=sm.entry_id)
+def test_commit_behind_every_instantiation(torch_mod, e):
+    """The walk of test_gpu_stream_commit.py over commit_inputs (the entry's ragged batch and the fading item) at commit_bounds:
+    every chunk that holds a frame launches the entry's kernel and layout; all streams are committed twice after every chunk but the
+    last -- count, labels, absolute time steps and kept nodes per stream against the oracle at that stream's age, the second call
+    hands out nothing; peeks (n_best in {1, K}) after every call against the oracle's rows shifted by the committed length; at the
+    end committed ++ reported row == the one-shot decode for every row of every stream, against both oracles."""
+    c = e["case"]
+    lp, sl = sm.commit_inputs(c)
+    done = _commit_walk(torch_mod, lp, dict(beam=c["K"], cutoff_top_n=c["top_n"]), 1, bounds=sm.commit_bounds(e), seq_lens=sl, configure=_configure(c),
+                        kernel=e["kernel"], layout=km.expected_layout(e["kernel"]), blank_id=c["blank"], cutoff_prob=c["cutoff_prob"])
+    assert done[sm.fading_index(c)] >= 2, done
+
+
+@pytest.mark.parametrize("d", sm.DEEP_WALKS, ids=sm.deep_walk_id)
+def test_commit_deep_walk_behind_an_instantiation(torch_mod, d):
+    """Two fading items of 128 frames behind the key's kernel, committed every 16 frames: a stream ends with a committed length that
+    is no multiple of 32 and more than an express level's labels uncommitted (test_stream_matrix_plan.py proves it on the oracle),
+    so the kernel's load_state, its later chunks and finish() follow express pointers laid out in re-rooted coordinates."""
+    c, lp, bounds = sm.deep_inputs(d)
+    done = _commit_walk(torch_mod, lp, dict(beam=c["K"], cutoff_top_n=c["top_n"]), 1, bounds=bounds, configure=_configure(c), kernel=d["kernel"],
+                        layout=km.expected_layout(d["kernel"]), blank_id=c["blank"], cutoff_prob=c["cutoff_prob"])
+    assert any(n % 32 != 0 for n in done) and min(done) > 0, done
+
+
 @pytest.mark.parametrize("direction", ["x_then_y", "y_then_x"])
 @pytest.mark.parametrize("h", sm.HAND_OVERS, ids=sm.hand_over_id)
 def test_stream_hand_over_between_kernels(torch_mod, wide99, monkeypatch, h, direction):
@@ -219,6 +253,69 @@ def test_stream_hand_over_between_kernels(torch_mod, wide99, monkeypatch, h, dir
     for want in wants:
         w = dict((k, v[src]) for k, v in want.items())
         ou.assert_same(_with_nres(got, w), w, "%s %s: %s -> %s at frame %d" % (h["name"], direction, sides[0][1], sides[1][1], T // 2))
+
+
+@pytest.mark.parametrize("direction", ["x_then_y", "y_then_x"])
+@pytest.mark.parametrize("h", [h for h in sm.HAND_OVERS if not h["case"]["lm"]], ids=sm.hand_over_id)
+def test_commit_in_front_of_a_hand_over(torch_mod, h, direction):
+    """A re-rooted state across a hand-over: commit_inputs fed as in test_stream_hand_over_between_kernels, and every stream that
+    crosses is committed at the T // 2 bound, directly before the switch (count, labels, time steps, kept nodes against the oracle at
+    the stream's age; the fading item commits labels there).  last_kernel() on both sides; the end: committed ++ reported row ==
+    the one-shot decode, against both oracles."""
+    import ctcdecode_amd
+
+    ncu = _cu_count(torch_mod)
+    c = dict(h["case"], B=h["case"]["B"] or ncu + sm.PRODUCTION_EXTRA)
+    lp, sl = sm.commit_inputs(c)
+    fade = sm.fading_index(c)
+    B, T, K = c["B"] + 1, c["T"], c["K"]
+    args = sm.oracle_args(c)
+    oracles = ["restated"] + (["reference"] if ou.have_reference() else [])
+    bounds = sm.hand_over_commit_bounds(h)
+    mid = sm.hand_over_commit_mid(h)
+    m = bounds.index(mid)
+    sides = [(h["x"], h["kernel_x"]), (h["y"], h["kernel_y"])]
+    if direction == "y_then_x":
+        sides.reverse()
+    n = len(bounds) - 1
+    kernels = [sides[0][1]] * m + [sides[1][1]] * (n - m)
+    few = sm.hand_over_few(c)
+    src = few if "few" in h["x"] else list(range(B))  # the streams that cross the hand-over
+    x = torch_mod.from_numpy(lp).to("cuda:0")
+    dec = _decoder(dict(c, **{k: v for k, v in sides[0][0].items() if k != "few"}), [str(i) for i in range(c["V"])], None)
+    states = [ctcdecode_amd.DecoderState(dec) for _ in range(B)]
+    committed = {}
+
+    def items_of(side):
+        return few if side.get("few") else list(range(B))
+
+    def before(i):
+        if i != m:
+            return None
+        got = dec.commit([states[b] for b in src])
+        for j, b in enumerate(src):
+            F = min(int(sl[b]), mid)
+            what = "%s %s: commit of stream %d at frame %d" % (h["name"], direction, b, F)
+            want = pu.oracle_prefix(lp[b:b + 1], F, oracles[-1], **args)
+            k = max(0, pu.common_prefix_len(want, 0) - 1)
+            g_tok, g_ts = got[j][0].numpy(), got[j][1].numpy()
+            assert len(g_tok) == k == len(g_ts), "%s: %d labels committed, want %d" % (what, len(g_tok), k)
+            assert np.array_equal(g_tok, want["tokens"][0, 0, :k]) and np.array_equal(g_ts, want["timesteps"][0, 0, :k]), what
+            assert states[b].committed_len == k and states[b].pool_nodes == cu.oracle_live_count(want, 0) - k, "%s: nodes kept" % what
+            committed[b] = (g_tok, g_ts)
+        assert len(committed[fade][0]) > 0, "the commit in front of the hand-over handed the fading item nothing"
+        _configure(dict(c, **{k: v for k, v in sides[1][0].items() if k != "few"}))(dec)
+        return items_of(sides[1][0])
+
+    out, fed = _feed(torch_mod, dec, states, x, sl, bounds, kernels, before=before, items=items_of(sides[0][0]))
+    assert sorted(committed) == sorted(src)
+    for b in src:
+        F = int(sl[b])
+        for oracle in oracles:
+            what = "%s %s: %s -> %s at frame %d, stream %d (%s oracle)" % (h["name"], direction, sides[0][1], sides[1][1], mid, b, oracle)
+            want = pu.oracle_prefix(lp[b:b + 1], F, oracle, **args)
+            mu.assert_committed_prefix(want, 0, committed[b][0], committed[b][1], what + ": committed")
+            mu.assert_final(_final(out, fed.index(b), K, F, want), want, 0, len(committed[b][0]), what)
 
 
 def test_stream_hand_over_through_the_automatic_subtree_switch(torch_mod):

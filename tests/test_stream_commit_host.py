@@ -26,15 +26,17 @@ def _walk(lp, kw, bounds, every, frames_hint=None, order="commit", min_nodes=0):
     """Feed every item of lp chunk by chunk (bounds: frame boundaries, repeats = empty chunks); after every `every`-th chunk commit
     TWICE (count, labels, pool against the oracle; the second one commits nothing and changes no byte) -- order: "commit" alone,
     "commit+compact" or "compact+commit"; after every chunk peek with n_best in {1, K} and since in {0, stable'} against the oracle
-    with the offset applied; the final result: committed ++ rows == the one-shot decode.  -> per item (commits that committed
-    something, committed length, labels of row 0 left uncommitted)."""
+    with the offset applied; the final result: committed ++ rows == the one-shot decode.  kw: the oracle's arguments, and the
+    stream's (beam, cutoff_top_n, cutoff_prob, blank_id).  -> per item (commits that committed something, committed length, labels
+    of row 0 left uncommitted)."""
     which = pu.which_oracle()
     B, T, V = lp.shape
     K = kw["beam"]
     final = _want_at(lp, kw, T, which)
     stats = []
     for b in range(B):
-        st = mu.HostStream(V, K, frames_hint or T + 1, cutoff_top_n=kw.get("cutoff_top_n", 40), min_nodes=min_nodes)
+        st = mu.HostStream(V, K, frames_hint or T + 1, cutoff_prob=kw.get("cutoff_prob", 1.0), cutoff_top_n=kw.get("cutoff_top_n", 40),
+                           blank_id=kw.get("blank_id", 0), min_nodes=min_nodes)
         frames = 0
         hits = 0
 

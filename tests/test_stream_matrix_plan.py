@@ -1,12 +1,20 @@
 """The streamed kernel matrix on the CPU (tests/stream_matrix_util.py): its table covers exactly the keys of CTC_KERNEL_LIST a stream
 can launch, the host's planner (launch_plan.h plan_launch, through the core's host build) plans each entry's kernel from the entry's
 arguments, switches and batch size, and the chunk bounds put at least two boundaries of every scorer-free entry directly behind a
-frame in which item 2 replayed std::nth_element (a condition of the inputs, checked on the host twin)."""
+frame in which item 2 replayed std::nth_element (a condition of the inputs, checked on the host twin).
+
+The commit walks of test_gpu_stream_matrix.py rest on conditions of their inputs as well, proved here on the oracle alone: over
+commit_inputs at commit_bounds at least two commits hand the fading item labels (the second one re-roots a re-rooted state) and row
+0 keeps labels to the end, for all 20 scorer-free entries; the commit in front of every hand-over hands the fading item labels; every
+deep walk ends between two express levels with more than one level's labels uncommitted.  And the host twin (stream_commit.h on the
+host build of the core) walks the same inputs -- the overflowed, the one-frame and the tie item among them -- before any GPU does."""
 import os
 
 import pytest
 
 import kernel_matrix_util as km
+import numpy as np
+import peek_util as pu
 import stream_matrix_util as sm
 from test_launch_plan import CU_COUNT, plan
 
@@ -84,3 +92,140 @@ def test_plan_of_the_automatic_subtree_switch():
     for on, prof in ((False, 0), (True, 3)):
         assert plan(a["V"], a["K"], a["V"], B=a["B"], threads=a["threads"], subtree=-1, subtree_on=on)[1] == (prof, 0, 1, 0, 1024, 0, 0)
     assert a["bounds"][0] == 0 and a["blank_frames"] in a["bounds"]
+
+
+# ---- the commit walks: what their inputs must give, on the oracle alone -------------------------------------------------------------
+SCORER_FREE = [e for e in sm.STREAM_CASES if not e["production"] and not e["case"]["lm"]]
+SCORER_FREE_HAND_OVERS = [h for h in sm.HAND_OVERS if not h["case"]["lm"]]
+
+
+def test_commit_tables_cover_the_scorer_free_entries():
+    assert len(SCORER_FREE) == 20 and len(SCORER_FREE_HAND_OVERS) == 8
+    ids = [sm.entry_id(e) for e in SCORER_FREE]
+    assert set(sm.COMMIT_BOUND) <= set(ids)
+    assert set(sm.HAND_OVER_COMMIT_MID) <= set(h["name"] for h in SCORER_FREE_HAND_OVERS)
+    for e in SCORER_FREE:
+        c = e["case"]
+        b, plain = sm.commit_bounds(e), sm.bounds(e)
+        assert set(plain) <= set(b) and 0 <= len(b) - len(plain) <= 2 and all(3 < x < c["T"] for x in set(b) - set(plain))
+        lp, sl = sm.commit_inputs(c)
+        lp0, sl0 = km.inputs(c)
+        f = sm.fading_index(c)
+        assert lp.shape == (c["B"] + 1, c["T"], c["V"]) and lp.dtype == np.float32 and f == c["B"] and sl[f] == c["T"]
+        assert np.array_equal(lp[:f].view(np.uint32), lp0.view(np.uint32)) and np.array_equal(sl[:f], sl0)
+        # the fading item: even frames peak on a label, odd frames on the blank (where the margin still exceeds the noise), and the margin falls
+        top = lp[f].argmax(axis=-1)
+        assert (top[1:c["T"] // 2:2] == c["blank"]).all() and (top[0:c["T"] // 2:2] != c["blank"]).all()
+        part = np.sort(lp[f], axis=-1)
+        margin = part[:, -1] - part[:, -2]
+        assert margin[0] > 35 and margin[-1] < 3 and margin[c["T"] // 2] < margin[0] - 10
+    keys = [d["kernel"] for d in sm.DEEP_WALKS]
+    assert sorted(keys) == sorted([(0, 0, 1, 0, 1024, 0, 1), (3, 0, 1, 0, 1024, 0, 0), (0, 0, 2, 1, 1024, 0, 0), (0, 2, 0, 0, 0, 0, 0)])
+    assert 96 <= sm.DEEP_T <= 128 and sm.DEEP_CHUNK == 16
+
+
+@pytest.mark.parametrize("e", SCORER_FREE, ids=sm.entry_id)
+def test_commit_walk_commits_twice(e):
+    """The GPU walk's rule -- a commit after every chunk that is not the last -- on the oracle: at least two commits hand the fading
+    item a label, the second of them at committed_len > 0 (a re-rooted state is re-rooted again), and at the stream's end row 0 keeps
+    at least 2 uncommitted labels.  Every scorer-free entry, none left out."""
+    c = e["case"]
+    lp, sl = sm.commit_inputs(c)
+    f = sm.fading_index(c)
+    kw = sm.oracle_args(c)
+    b = sm.commit_bounds(e)
+    ev = sm.commit_events(lp, f, b[1:-1], **kw)
+    hits = [x for x in ev if x[1] > 0]
+    final = pu.oracle_prefix(lp[f:f + 1], c["T"], "restated", **kw)
+    left = int(final["lens"][0, 0]) - (ev[-1][1] + ev[-1][2])
+    print(sm.entry_id(e), "bounds", b, "(frame, labels handed out, committed before):", ev, "left at the end:", left)
+    assert len(hits) >= 2, "bounds %s: %s" % (b, ev)
+    assert hits[1][2] > 0
+    assert left >= 2, left
+
+
+@pytest.mark.parametrize("e", [e for e in SCORER_FREE if sm.host_twin_builds(e["case"])], ids=sm.entry_id)
+def test_commit_host_walk_over_the_matrix_inputs(e):
+    """commit_inputs at commit_bounds through the host twin (test_stream_commit_host._walk: a commit after every chunk but the last,
+    twice; counts, labels, time steps, kept nodes, peeks and the end against the oracle), every item at its own length, with the
+    entry's beam, cutoff_top_n, cutoff_prob and blank."""
+    from test_stream_commit_host import _walk
+
+    c = e["case"]
+    lp, sl = sm.commit_inputs(c)
+    f = sm.fading_index(c)
+    kw = sm.oracle_args(c)
+    b = sm.commit_bounds(e)
+    for i in range(lp.shape[0]):
+        n = int(sl[i])
+        stats = _walk(np.ascontiguousarray(lp[i:i + 1, :n]), kw, [min(x, n) for x in b], 1)
+        print(sm.entry_id(e), "item", i, "length", n, "(commits that handed out labels, committed, left):", stats)
+        if i == f:
+            assert stats[0][0] >= 2 and stats[0][2] >= 2, stats
+
+
+def test_host_twin_builds_all_but_the_widest_layout():
+    skipped = [e["kernel"] for e in SCORER_FREE if not sm.host_twin_builds(e["case"])]
+    assert sorted(skipped) == [(0, 3, 0, 0, 0, 0, 0), (0, 3, 0, 1, 0, 0, 0)], skipped
+
+
+@pytest.mark.parametrize("h", SCORER_FREE_HAND_OVERS, ids=sm.hand_over_id)
+def test_commit_in_front_of_a_hand_over_commits(h):
+    """The commit at the hand-over's bound hands the fading item a label; the streams of a `few` side (the fading item among them) still
+    plan that side's kernel."""
+    c = dict(h["case"], B=h["case"]["B"] or CU_COUNT + sm.PRODUCTION_EXTRA)
+    lp, sl = sm.commit_inputs(c)
+    f = sm.fading_index(c)
+    mid = sm.hand_over_commit_mid(h)
+    b = sm.hand_over_commit_bounds(h)
+    assert mid in b and b[:4] == [0, 1, 3, 3] and b[-1] == c["T"]
+    ev = sm.commit_events(lp, f, [mid], **sm.oracle_args(c))
+    print(h["name"], "bounds", b, "the commit at frame %d hands the fading item %d labels" % (mid, ev[0][1]))
+    assert ev[0][1] > 0, ev
+    few = sm.hand_over_few(c)
+    assert f in few and len(few) == len(set(few)) <= 4
+    for side, kernel in ((h["x"], h["kernel_x"]), (h["y"], h["kernel_y"])):
+        cs = dict(c, **{k: v for k, v in side.items() if k != "few"})
+        B = len(few) if side.get("few") else c["B"] + 1
+        rc, key, _ = plan(cs["V"], cs["K"], cs["top_n"], cs["cutoff_prob"], B=B, threads=cs["threads"] or 0, fixed=cs["fixed"],
+                          cu_sharing=cs["cu_sharing"], subtree=cs["subtree"], scorer=km.scorer_kind(cs), streamed=False)
+        assert rc == 0 and key == kernel, (side, key, kernel)
+
+
+def _deep_stats(d):
+    """Per stream of a deep walk, on the oracle: [(frame, labels handed out, committed before, labels of row 0 left behind the
+    commit)] and the labels left at the end."""
+    c, lp, b = sm.deep_inputs(d)
+    kw = sm.oracle_args(c)
+    out = []
+    for i in range(lp.shape[0]):
+        ev = sm.commit_events(lp, i, b[1:-1], **kw)
+        left = [int(pu.oracle_prefix(lp[i:i + 1], F, "restated", **kw)["lens"][0, 0]) - (m + C) for F, m, C in ev]
+        final = int(pu.oracle_prefix(lp[i:i + 1], sm.DEEP_T, "restated", **kw)["lens"][0, 0])
+        out.append(([x + (l,) for x, l in zip(ev, left)], ev[-1][1] + ev[-1][2], final - (ev[-1][1] + ev[-1][2])))
+    return out
+
+
+@pytest.mark.parametrize("d", sm.DEEP_WALKS, ids=sm.deep_walk_id)
+def test_deep_walks_end_between_express_levels(d):
+    """Some stream of the deep walk ends with a committed length that is no multiple of 32 and at least 33 labels of row 0
+    uncommitted: the express levels of the re-rooted coordinates are written (by the commit's layout and by later chunks) and read
+    back by finish().  deep_commit: a commit itself hands out labels and leaves such a state."""
+    stats = _deep_stats(d)
+    for i, (ev, C, left) in enumerate(stats):
+        print(sm.deep_walk_id(d), "stream", i, "(frame, handed out, committed before, left):", ev, "committed", C, "left at the end", left)
+    assert any(C % 32 != 0 and left >= 33 for _, C, left in stats), stats
+    assert all(sum(1 for x in ev if x[1] > 0) >= 2 for ev, _, _ in stats), stats
+    if d["deep_commit"]:
+        assert any(m > 0 and (C + m) % 32 != 0 and l >= 33 for ev, _, _ in stats for _, m, C, l in ev), stats
+
+
+@pytest.mark.parametrize("d", sm.DEEP_WALKS, ids=sm.deep_walk_id)
+def test_commit_host_walk_over_the_deep_inputs(d):
+    from test_stream_commit_host import _walk
+
+    c, lp, b = sm.deep_inputs(d)
+    assert sm.host_twin_builds(c)
+    stats = _walk(lp, sm.oracle_args(c), b, 1)
+    print(sm.deep_walk_id(d), stats)
+    assert any(C % 32 != 0 and left >= 33 for _, C, left in stats), stats
