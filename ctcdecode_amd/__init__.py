@@ -32,7 +32,7 @@ class _Scorer(object):
         h = getattr(self, "handle", None)
         if h is not None and h.value:
             try:
-                _native.lib.ctcd_scorer_destroy(h)
+                _native.destroy(_native.lib.ctcd_scorer_destroy, h)
             except Exception:
                 pass
             self.handle = None
@@ -60,6 +60,7 @@ class CallbackScorer(object):
         self._error = None
 
         def trampoline(_user, words, n, out):
+            _native._in_callback += 1  # (a destructor that runs in here waits: _native.destroy)
             try:
                 r = self._fn(tuple(words[i].decode("utf-8") for i in range(n)))
                 if r is None:
@@ -69,6 +70,8 @@ class CallbackScorer(object):
             except BaseException as e:  # (an exception must not unwind through the C frames)
                 self._error = e
                 return -1
+            finally:
+                _native._in_callback -= 1
 
         self._c_fn = _native.COND_LOG10_FN(trampoline)  # kept alive with the scorer
         voc = [str(w).encode("utf-8") for w in vocabulary]
@@ -122,6 +125,7 @@ class CallbackScorer(object):
 
     def _batch_trampoline(self):
         def trampoline(_user, words, n, order, probs, status):
+            _native._in_callback += 1  # (a destructor that runs in here waits: _native.destroy)
             try:
                 flat = [w.decode("utf-8") for w in words[: n * order]]
                 r = list(self._fn([tuple(flat[i * order:(i + 1) * order]) for i in range(n)]))
@@ -137,6 +141,8 @@ class CallbackScorer(object):
             except BaseException as e:  # (an exception must not unwind through the C frames)
                 self._error = e
                 return -1
+            finally:
+                _native._in_callback -= 1
 
         return _native.COND_LOG10_BATCH_FN(trampoline)
 
@@ -195,7 +201,7 @@ class CallbackScorer(object):
         h = getattr(self, "handle", None)
         if h is not None and h.value:
             try:
-                _native.lib.ctcd_scorer_destroy(h)
+                _native.destroy(_native.lib.ctcd_scorer_destroy, h)
             except Exception:
                 pass
             self.handle = None
@@ -701,7 +707,7 @@ class CTCBeamDecoder(object):
         h = getattr(self, "_handle", None)
         if h is not None and h.value:
             try:
-                _native.lib.ctcd_destroy(h)
+                _native.destroy(_native.lib.ctcd_destroy, h)
             except Exception:
                 pass
             self._handle = None
@@ -1098,7 +1104,7 @@ class OnlineCTCBeamDecoder(object):
         h = getattr(self, "_handle", None)
         if h is not None and h.value:
             try:
-                _native.lib.ctcd_destroy(h)
+                _native.destroy(_native.lib.ctcd_destroy, h)
             except Exception:
                 pass
             self._handle = None
@@ -1141,7 +1147,7 @@ class DecoderState(object):
         d = getattr(self, "_decoder", None)
         if h is not None and h.value and d is not None and getattr(d, "_handle", None) is not None:
             try:
-                _native.lib.ctcd_stream_destroy(d._handle, h)
+                _native.destroy(_native.lib.ctcd_stream_destroy, d._handle, h)
             except Exception:
                 pass
             self.state = None

@@ -149,7 +149,36 @@ class NativeError(RuntimeError):
     pass
 
 
+# Destroying a scorer, a decoder or a stream frees HBM, and hipFree waits for the device.  A launch of the scorer hook that waits on
+# the GPU for its answers runs the callback on the calling thread; the interpreter may collect garbage there, and a destructor run by
+# that collection waited for the very launch that was waiting for the callback's answer -- until its workgroups gave up waiting, about
+# six seconds later (results unchanged, one more launch).  So a destructor that runs inside a scorer callback only queues its call;
+# the queue is emptied by the next checked call outside a callback (the decode that ran the callback among them).
+_in_callback = 0
+_deferred = []
+
+
+def destroy(fn, *handles):
+    """Call fn(*handles) -- a ctcd_*_destroy -- now, or after the scorer callback that is running has returned to its launch's end."""
+    if _in_callback:
+        _deferred.append((fn, handles))
+        return
+    _run_deferred()
+    fn(*handles)
+
+
+def _run_deferred():
+    while _deferred and not _in_callback:
+        fn, handles = _deferred.pop(0)
+        try:
+            fn(*handles)
+        except Exception:
+            pass
+
+
 def check(rc):
+    if _deferred:
+        _run_deferred()
     if rc != 0:
         msg = lib.ctcd_last_error().decode("utf-8", "replace")
         if rc == -1:

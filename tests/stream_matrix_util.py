@@ -43,6 +43,18 @@ MID_BOUND = {"k0011_1024_lm0_occ1": 23, "k0011_0_lm0_occ0": 22, "k3010_1024_lm0_
 EXTRA_BOUND = {"k0010_1024_lm0_occ0": 22, "k0010_1024_lm0_occ1": 21, "k3010_1024_lm0_occ0": 25, "k0001_0_lm0_occ0": 17,
                "k0130_1024_lm0_occ0": 17, "k0100_1024_lm0_occ0": 14, "k0101_0_lm0_occ0": 14}
 
+# The scorer entries over select_path_util.select_path_inputs (test_gpu_select_paths.py), bounds of select_path_util.select_path_bounds.
+# Item 0 is in danger mode from its overflow frames on and replays in every frame behind them, so the bounds T // 2 and 2T/3 + 1 of
+# every entry directly follow a replay of item 0.  Item 2's replays are the ones a tie forces (the boundary splits a group of equivalent
+# prefixes): where it has one mid-utterance, the entry gets one more bound directly behind it.  entry_id -> that bound (found with
+# select_path_util.replay_frames_lm(); held by test_stream_matrix_plan.py::test_select_path_bounds_follow_replays).  The unpruned fixed-layout entries
+# have none: every tie of their item 2 is settled by character.
+SELECT_PATH_EXTRA = {"k0011_1024_lm2_occ0": 12, "k0011_1024_lm2_occ1": 10, "k0011_1024_lm1_occ0": 10, "k0011_1024_lm1_occ1": 7,
+                     "k0100_0_lm1_occ0": 5, "k0200_0_lm1_occ0": 6, "k0201_0_lm1_occ0": 7, "k0011_1024_lm3_occ0": 10, "k0100_0_lm3_occ0": 5,
+                     "k0101_0_lm3_occ0": 7}
+# ... and the entries whose T // 2 bound already follows a replay of item 2
+ITEM2_AT_MID = ["k0001_0_lm1_occ0", "k0301_0_lm3_occ0"]
+
 
 def stream_reachable(key):
     """A key of CTC_KERNEL_LIST that ctcd_stream_decode / ctcd_stream_decode_to_host can plan."""

@@ -128,3 +128,30 @@ def test_reference_import_name():
 
     assert ctcdecode.CTCBeamDecoder is ctcdecode_amd.CTCBeamDecoder
     assert ctcdecode.OnlineCTCBeamDecoder is ctcdecode_amd.OnlineCTCBeamDecoder and ctcdecode.DecoderState is ctcdecode_amd.DecoderState
+
+
+def test_destructors_inside_a_scorer_callback_are_queued():
+    """_native.destroy: a ctcd_*_destroy asked for while a scorer callback runs (the collector ran a destructor there) frees HBM and
+    would wait for the launch that waits for the callback; it is queued, and the next checked call outside a callback makes it --
+    in the order the destructors ran (a stream before its decoder).  test_gpu_lm.py holds the decode that does this on the device."""
+    from ctcdecode_amd import _native
+
+    calls = []
+    assert _native._in_callback == 0 and _native._deferred == []
+    _native._in_callback += 1
+    try:
+        _native.destroy(lambda *h: calls.append(h), "decoder", "stream")
+        _native.destroy(lambda *h: calls.append(h), "decoder")
+        _native.check(0)  # (a checked call inside the callback: still queued)
+        assert calls == [] and len(_native._deferred) == 2
+    finally:
+        _native._in_callback -= 1
+    _native.check(0)
+    assert calls == [("decoder", "stream"), ("decoder",)] and _native._deferred == []
+    _native._in_callback += 1
+    try:
+        _native.destroy(lambda *h: calls.append(h), "first")
+    finally:
+        _native._in_callback -= 1
+    _native.destroy(lambda *h: calls.append(h), "second")  # (outside a callback: at once, behind what was queued)
+    assert calls[2:] == [("first",), ("second",)] and _native._deferred == []

@@ -579,3 +579,58 @@ def test_scorer_hook_native_callback_on_several_threads(torch_mod):
         sc.set_callback_threads(1)
     finally:
         py.close()
+
+
+def test_scorer_hook_destructor_inside_the_callback_does_not_stall_the_launch(torch_mod):
+    """Regression: a waiting launch runs the callback on the calling thread, the interpreter collects garbage there, and the destructor
+    of a dropped CallbackScorer (it sits in a reference cycle with its trampoline: only the collector frees it) called
+    ctcd_scorer_destroy -- hipFree waits for the device, i.e. for the launch that was waiting for this very callback; its workgroups
+    gave up after about six seconds and the host launched again.  Seen at random in the callback cases of the kernel matrix (the
+    collector runs where it likes); here the callback collects on its first call.  The destructor must only queue its call
+    (_native.destroy), the decode that ran the callback must make it afterwards, and the decode must take as many launches as the same
+    decode without garbage and give the same results."""
+    import gc
+
+    import ctcdecode_amd
+    from ctcdecode_amd import _native
+
+    lp = ou.synth_logprobs(3, 30, 29, 77, blank_bias=0.5)
+    lp[:, :, LABELS29.index(" ")] += np.float32(1.0)
+    want = ou.decode(lp, beam=40, cutoff_top_n=29, scorer=ou.Scorer(0.5, 1.0, TEST_ARPA, LABELS29, "restated"))
+    inner = _BuiltinBehindCallback(dict(labels=LABELS29, lm_path=TEST_ARPA))
+    seen = []
+
+    def collecting(words):
+        if not seen:
+            before = len(_native._deferred)
+            gc.collect()
+            seen.append((_native._in_callback, len(_native._deferred) - before))
+        return inner(words)
+
+    def run(fn):
+        sc = ctcdecode_amd.CallbackScorer(fn, inner.vocabulary, inner.order, LABELS29, alpha=0.5, beta=1.0, device="cuda:0")
+        dec = ctcdecode_amd.CTCBeamDecoder(LABELS29, scorer=sc, beam_width=40, cutoff_top_n=29, log_probs_input=True, device="cuda:0")
+        dec.set_scorer_wait(True)
+        out, scores, ts, ln = dec.decode(torch_mod.from_numpy(lp))
+        ou.assert_same(_with_nres(dict(tokens=out.numpy(), timesteps=ts.numpy(), scores=scores.numpy(), lens=ln.numpy()), want), want, "hook")
+        assert sc.callback_calls() > 0
+        return dec.last_scorer_launches()[0]
+
+    try:
+        gc.collect()
+        control = run(inner)
+        gc.collect()
+        gc.disable()  # (the collection must happen inside the callback, not while the objects below are made)
+        try:
+            dropped = ctcdecode_amd.CallbackScorer(inner, inner.vocabulary, inner.order, LABELS29, alpha=0.5, beta=1.0, device="cuda:0")
+            handle = dropped.handle.value
+            del dropped  # (garbage now, but for the cycle)
+            launches = run(collecting)
+        finally:
+            gc.enable()
+        print("launches: %d without garbage, %d with a scorer collected inside the callback; (in a callback, destructors queued): %s" % (control, launches, seen))
+        assert handle and len(seen) == 1 and seen[0][0] == 1 and seen[0][1] >= 1, seen
+        assert _native._deferred == [], "the decode that ran the callback makes the queued calls when it is done"
+        assert launches == control, (launches, control)
+    finally:
+        inner.close()

@@ -7,7 +7,11 @@ The commit walks of test_gpu_stream_matrix.py rest on conditions of their inputs
 commit_inputs at commit_bounds at least two commits hand the fading item labels (the second one re-roots a re-rooted state) and row
 0 keeps labels to the end, for all 20 scorer-free entries; the commit in front of every hand-over hands the fading item labels; every
 deep walk ends between two express levels with more than one level's labels uncommitted.  And the host twin (stream_commit.h on the
-host build of the core) walks the same inputs -- the overflowed, the one-frame and the tie item among them -- before any GPU does."""
+host build of the core) walks the same inputs -- the overflowed, the one-frame and the tie item among them -- before any GPU does.
+
+The scorer entries are streamed over select_path_inputs (tests/select_path_util.py, test_gpu_select_paths.py): their bounds keep the
+list's properties, at least two of them directly follow a frame in which item 0 or item 2 replayed std::nth_element although it was no
+decode's last frame, and one lies between the two overflow frames of item 0."""
 import os
 
 import pytest
@@ -15,6 +19,7 @@ import pytest
 import kernel_matrix_util as km
 import numpy as np
 import peek_util as pu
+import select_path_util as sp
 import stream_matrix_util as sm
 from test_launch_plan import CU_COUNT, plan
 
@@ -73,6 +78,45 @@ def test_two_boundaries_follow_a_replay(e):
     got = sm.tie_boundaries(e)
     print(sm.entry_id(e), "bounds", sm.bounds(e), "behind a replay frame of item 2:", got)
     assert len(got) >= 2, "bounds %s: only %s directly follow a frame in which item 2 replayed nth_element" % (sm.bounds(e), got)
+
+
+@pytest.fixture(scope="module")
+def wide99(tmp_path_factory):
+    from test_lm import make_wide_label_lm
+
+    return make_wide_label_lm(tmp_path_factory.mktemp("stream_matrix_plan_lm"))
+
+
+def test_select_path_tables_cover_the_scorer_entries():
+    entries = sp.stream_entries()
+    assert len(entries) == 26 and sorted(e["kernel"] for e in entries) == sorted(c["kernel"] for c in sp.scorer_cases())
+    ids = [sm.entry_id(e) for e in entries]
+    assert set(sm.SELECT_PATH_EXTRA) <= set(ids) and set(sm.ITEM2_AT_MID) <= set(ids) and not set(sm.SELECT_PATH_EXTRA) & set(sm.ITEM2_AT_MID)
+    assert len(sm.SELECT_PATH_EXTRA) + len(sm.ITEM2_AT_MID) >= 12  # (every HBM level and both layouts among them)
+    assert set(e["kernel"][1] for e in entries if sm.entry_id(e) in sm.SELECT_PATH_EXTRA) == {0, 1, 2}
+
+
+@pytest.mark.parametrize("e", sp.stream_entries(), ids=sm.entry_id)
+def test_select_path_bounds_follow_replays(monkeypatch, wide99, e):
+    """On the host twin, instantiated as the entry's own class: the replays of item 0 and item 2 that are no decode's last frame."""
+    c = e["case"]
+    T, eid = c["T"], sm.entry_id(e)
+    b = sp.select_path_bounds(e)
+    assert b[:4] == [0, 1, 3, 3] and b[-1] == T and b[-2] == (2 * T) // 3 + 1 and T // 2 in b
+    assert sorted(b) == b and len(set(b)) == len(b) - 1  # (the empty chunk alone repeats a bound)
+    lm = km.lm_spec(c, *wide99)
+    lp, sl = sp.select_path_inputs(c, lm[1])
+    assert sl[0] == T and (lp[0, 2:4] == np.float32(-3.0e38)).all() and 3 in b  # the bound 3 parts the two overflow frames of item 0
+    assert (sum(sm.chunk_lens(sl, lo, hi) for lo, hi in zip(b, b[1:])) == sl).all()  # every item's frames are fed exactly once
+    sp.set_host_env(c, monkeypatch.setenv, lambda name: monkeypatch.delenv(name, raising=False))
+    got = sp.replay_boundaries(e, lm)
+    print(eid, "bounds", b, "behind a replay frame of item 0:", got[0], "of item 2:", got[2])
+    assert len(set(got[0]) | set(got[2])) >= 2, "bounds %s: only %s directly follow a replay of item 0 or item 2" % (b, got)
+    assert got[0], "item 0 is in danger mode behind its overflow frames: %s" % (got,)
+    if eid in sm.SELECT_PATH_EXTRA:
+        assert sm.SELECT_PATH_EXTRA[eid] in got[2], (b, got)
+    if eid in sm.ITEM2_AT_MID:
+        assert T // 2 in got[2], (b, got)
 
 
 @pytest.mark.parametrize("h", sm.HAND_OVERS, ids=sm.hand_over_id)
