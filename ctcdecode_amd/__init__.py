@@ -12,7 +12,7 @@ import torch
 from . import _native
 from ._native import NativeError  # noqa: F401
 
-__all__ = ["CTCBeamDecoder", "OnlineCTCBeamDecoder", "DecoderState", "NativeError", "CallbackScorer", "KenlmScorer", "DecodePipeline"]
+__all__ = ["CTCBeamDecoder", "OnlineCTCBeamDecoder", "DecoderState", "NativeError", "CallbackScorer", "KenlmScorer", "DecodePipeline", "snapshot_info"]
 HAVE_LM = True  # the external-scorer tier (model_path / alpha / beta) is part of this build
 
 
@@ -1087,6 +1087,88 @@ class OnlineCTCBeamDecoder(object):
         rows_tok, rows_ts = made["tok"].unbind(0), made["ts"].unbind(0)
         return [(rows_tok[b][:n], rows_ts[b][:n]) if n else none for b, n in enumerate(counts)]
 
+    def save(self, states):
+        """Images of live streams in host memory (extension): one 1-D ``torch.uint8`` CPU tensor per stream -- views of one allocation
+        -- that holds everything the stream is: ``restore`` on this decoder, on another one with the same labels, beam width and blank
+        (another kernel choice, another GPU, another process) gives a stream that behaves bit-identically from then on, for every
+        later ``decode``, ``peek``, ``compact``, ``commit`` and stream end.  ``committed_len``, the absolute frame numbers and the
+        scorer's fingerprint travel; the committed labels themselves are the caller's (see ``commit``).
+
+        ``save`` has exactly ``compact(states)``'s effect on the saved streams -- an image is the layout a compaction leaves, and a
+        compaction changes nothing a later call returns -- and changes nothing else about them: they stay live and decode on.  The
+        image is canonical (saving twice with no frame in between gives identical bytes) and small: 4 * (28 + A * beam + 5 * M)
+        bytes for the M trie nodes the beam can still reach, A = 14 without a scorer and 26 with one.  Works behind
+        ``decode(..., check=False)`` chunks; synchronous.  Streams behind a callback scorer raise ``NotImplementedError`` (their
+        states index a per-process cache) and are left untouched."""
+        B = len(states)
+        if B == 0:
+            return []
+        if self._scorer is not None and isinstance(self._scorer, CallbackScorer):
+            raise NotImplementedError("ctcdecode_amd: images of streams behind a callback scorer")
+        ptrs = (ctypes.c_void_p * B)(*[st._ptr(self) for st in states])
+        sizes = (ctypes.c_ulonglong * B)()
+        made = {}
+
+        def alloc(_user, total):
+            try:
+                made["buf"] = torch.empty((int(total),), dtype=torch.uint8, pin_memory=int(total) > 0)  # (every byte is written)
+                return made["buf"].data_ptr()
+            except Exception as e:  # (reported through the return value: no exception crosses the C frame)
+                made["error"] = e
+                return None
+
+        cb = _native.BYTES_ALLOC_FN(alloc)
+        with torch.cuda.device(self._device):
+            stream = torch.cuda.current_stream(self._device).cuda_stream
+            rc = _native.lib.ctcd_stream_save(self._handle, ptrs, B, cb, None, sizes, stream)
+            if "error" in made:
+                raise made["error"]
+            self._check(rc)
+            # (the call has waited for the chunks queued in front of it: their status words are looked at now, as peek() does)
+            unchecked, self._unchecked = getattr(self, "_unchecked", 0), 0
+            _native.check(_native.lib.ctcd_check_status(self._handle, unchecked))
+        out, at = [], 0
+        for n in sizes:  # (image b starts at the sum of the earlier sizes, each rounded up to 16 bytes)
+            out.append(made["buf"][at:at + int(n)])
+            at += (int(n) + 15) // 16 * 16
+        return out
+
+    def restore(self, blobs, frames_hint=0):
+        """New ``DecoderState`` objects, bound to this decoder, from images ``save`` made (uint8 tensors or ``bytes``) -- on this
+        decoder or on any other with the same labels, beam width and blank, and a scorer built from the same model if the streams had
+        one.  Every image is validated on the host before anything is allocated or uploaded; an image that is truncated, corrupted,
+        of another beam width / label count or saved behind another scorer raises ``ValueError`` naming the item and the check, and
+        then no stream is created.  ``frames_hint``: the capacity the streams start with (as for a new ``DecoderState``)."""
+        B = len(blobs)
+        if B == 0:
+            return []
+        if self._scorer is not None and isinstance(self._scorer, CallbackScorer):
+            raise NotImplementedError("ctcdecode_amd: images of streams behind a callback scorer")
+        keep = []
+        for b, blob in enumerate(blobs):
+            if isinstance(blob, torch.Tensor):
+                if blob.dtype != torch.uint8 or blob.dim() != 1:
+                    raise ValueError("restore: item %d is not a 1-D uint8 tensor" % b)
+                t = blob.detach().cpu().contiguous()
+            else:
+                t = torch.frombuffer(bytearray(bytes(blob)), dtype=torch.uint8) if len(blob) else torch.zeros((0,), dtype=torch.uint8)
+            keep.append(t)
+            try:
+                inf = snapshot_info(t)
+            except ValueError as e:
+                raise ValueError("restore: item %d is refused: %s" % (b, e))
+            if inf["beam"] != self._beam_width or inf["labels"] != self._num_labels:
+                raise ValueError("restore: item %d was saved with beam width %d over %d labels; this decoder has %d over %d"
+                                 % (b, inf["beam"], inf["labels"], self._beam_width, self._num_labels))
+        ptrs = (ctypes.c_void_p * B)(*[t.data_ptr() for t in keep])
+        sizes = (ctypes.c_ulonglong * B)(*[t.numel() for t in keep])
+        outs = (ctypes.c_void_p * B)()
+        with torch.cuda.device(self._device):
+            stream = torch.cuda.current_stream(self._device).cuda_stream
+            self._check(_native.lib.ctcd_stream_restore(self._handle, self._scorer.handle if self._scorer is not None else None, ptrs, sizes, B,
+                                                        int(frames_hint), outs, stream))
+        return [DecoderState._adopt(self, outs[b]) for b in range(B)]
+
     def character_based(self):
         return bool(_native.lib.ctcd_scorer_is_character_based(self._scorer.handle)) if self._scorer else None
 
@@ -1110,6 +1192,21 @@ class OnlineCTCBeamDecoder(object):
             self._handle = None
 
 
+def snapshot_info(blob):
+    """What an image made by ``OnlineCTCBeamDecoder.save`` says about itself (a uint8 tensor or ``bytes``), without a GPU: a dict with
+    ``version, beam, labels, frames, committed, nodes, scorer_kind`` (0 none / 1 built-in), ``fingerprint`` and ``bytes``.
+    ``ValueError``: not an image."""
+    if isinstance(blob, torch.Tensor):
+        t = blob.detach().cpu().contiguous().view(torch.uint8).reshape(-1)
+        ptr, n = t.data_ptr(), t.numel()
+    else:
+        t = bytes(blob)
+        ptr, n = ctypes.cast(ctypes.c_char_p(t), ctypes.c_void_p), len(t)
+    info = _native.SnapshotInfo()
+    _native.check(_native.lib.ctcd_snapshot_info(ptr if n else None, n, ctypes.byref(info)))
+    return dict((k, int(getattr(info, k))) for k in ("version", "beam", "labels", "frames", "committed", "nodes", "scorer_kind", "fingerprint", "bytes"))
+
+
 class DecoderState(object):
     """State of one audio stream (ctcdecode/__init__.py:253-272).  Bound to the decoder it is first used with; not reusable
     after its stream ended, as in the reference."""
@@ -1122,10 +1219,23 @@ class DecoderState(object):
                                                         sc.handle if sc is not None else None))
         self.state = h
 
+    @classmethod
+    def _adopt(cls, decoder, handle):
+        """A DecoderState around a stream handle the library made (``OnlineCTCBeamDecoder.restore``); it owns the handle from here on."""
+        self = cls.__new__(cls)
+        self._decoder = decoder
+        self.state = ctypes.c_void_p(handle)
+        return self
+
     def _ptr(self, decoder):
         if decoder is not self._decoder:
             raise ValueError("DecoderState used with a different decoder than it was created for")
         return self.state.value
+
+    @property
+    def frames(self):
+        """Frames the stream has been fed so far."""
+        return int(_native.lib.ctcd_stream_frames(self.state))
 
     @property
     def nbytes(self):

@@ -18,10 +18,18 @@ COND_LOG10_BATCH_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.POI
 
 # ctcd_result_alloc_fn: int fn(void *user, int R, int L, int32_t **tokens, int32_t **timesteps)
 RESULT_ALLOC_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p))
+# ctcd_bytes_alloc_fn: void *fn(void *user, unsigned long long bytes)
+BYTES_ALLOC_FN = ctypes.CFUNCTYPE(ctypes.c_void_p, ctypes.c_void_p, ctypes.c_ulonglong)
+
+
+class SnapshotInfo(ctypes.Structure):  # ctcd_snapshot_info_t
+    _fields_ = [("version", ctypes.c_int32), ("beam", ctypes.c_int32), ("labels", ctypes.c_int32), ("scorer_kind", ctypes.c_int32),
+                ("nodes", ctypes.c_int32), ("reserved", ctypes.c_int32), ("frames", ctypes.c_longlong), ("committed", ctypes.c_longlong),
+                ("fingerprint", ctypes.c_ulonglong), ("bytes", ctypes.c_ulonglong)]
 
 SYMBOLS = ["ctcd_log_softmax", "ctcd_compact_label_capacity", "ctcd_beam_decode_compact", "ctcd_expand_compact", "ctcd_beam_decode_to_host", "ctcd_scorer_create", "ctcd_scorer_destroy", "ctcd_scorer_is_character_based", "ctcd_scorer_max_order", "ctcd_scorer_dict_size",
            "ctcd_scorer_reset_params", "ctcd_scorer_cond_log_prob", "ctcd_scorer_create_callback", "ctcd_scorer_cond_log10", "ctcd_scorer_callback_calls", "ctcd_scorer_callback_seconds", "ctcd_scorer_set_callback_threads", "ctcd_scorer_create_callback_batch", "ctcd_scorer_cond_log10_batch", "ctcd_scorer_callback_batches", "ctcd_beam_decode_lm", "ctcd_beam_decode_lm_host", "ctcd_stream_create_lm",
-           "ctcd_create", "ctcd_destroy", "ctcd_beam_decode", "ctcd_beam_decode_host", "ctcd_check_status", "ctcd_fetch_status_async", "ctcd_stream_create", "ctcd_stream_destroy", "ctcd_stream_frames", "ctcd_stream_decode", "ctcd_stream_decode_to_host", "ctcd_stream_peek", "ctcd_stream_compact", "ctcd_stream_commit", "ctcd_stream_committed", "ctcd_stream_pool_nodes", "ctcd_stream_pool_capacity", "ctcd_stream_bytes", "ctcd_set_stream_compaction", "ctcd_last_prune_host_rows", "ctcd_last_prune_flagged_rows", "ctcd_last_scorer_rounds", "ctcd_last_scorer_waits", "ctcd_set_scorer_wait", "ctcd_set_scorer_filter", "ctcd_last_scorer_pairs",
+           "ctcd_create", "ctcd_destroy", "ctcd_beam_decode", "ctcd_beam_decode_host", "ctcd_check_status", "ctcd_fetch_status_async", "ctcd_stream_create", "ctcd_stream_destroy", "ctcd_stream_frames", "ctcd_stream_decode", "ctcd_stream_decode_to_host", "ctcd_stream_peek", "ctcd_stream_compact", "ctcd_stream_commit", "ctcd_stream_committed", "ctcd_stream_save", "ctcd_stream_restore", "ctcd_snapshot_info", "ctcd_scorer_fingerprint", "ctcd_stream_pool_nodes", "ctcd_stream_pool_capacity", "ctcd_stream_bytes", "ctcd_set_stream_compaction", "ctcd_last_prune_host_rows", "ctcd_last_prune_flagged_rows", "ctcd_last_scorer_rounds", "ctcd_last_scorer_waits", "ctcd_set_scorer_wait", "ctcd_set_scorer_filter", "ctcd_last_scorer_pairs",
            "ctcd_set_threads", "ctcd_set_cu_sharing", "ctcd_set_input_dtype", "ctcd_last_input_dtype", "ctcd_set_launch_order", "ctcd_debug_last_launch_order", "ctcd_set_subtree_search", "ctcd_last_subtree_search", "ctcd_debug_last_layout", "ctcd_debug_last_kernel", "ctcd_debug_last_prepass", "ctcd_debug_prepass_table", "ctcd_debug_set_host_path", "ctcd_set_timing", "ctcd_last_kernel_ms", "ctcd_last_prune_ms", "ctcd_last_resolve_ms", "ctcd_debug_math_check", "ctcd_debug_set_profile", "ctcd_debug_set_fixed_layout", "ctcd_debug_set_prune_resolve", "ctcd_debug_set_fused_logits", "ctcd_debug_set_prune_registers", "ctcd_debug_prune_rows", "ctcd_debug_timeline", "ctcd_debug_timeline_cap", "ctcd_debug_get_profile", "ctcd_debug_beam_dump", "ctcd_workgroup_lds_bytes", "ctcd_last_error", "ctcd_version"]
 
 
@@ -92,6 +100,13 @@ def _load():
     lib.ctcd_stream_compact.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
     lib.ctcd_stream_commit.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, RESULT_ALLOC_FN, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                        ctypes.POINTER(ctypes.c_int), ctypes.c_void_p]
+    lib.ctcd_stream_save.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, BYTES_ALLOC_FN, ctypes.c_void_p, ctypes.POINTER(ctypes.c_ulonglong),
+                                     ctypes.c_void_p]
+    lib.ctcd_stream_restore.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_ulonglong), ctypes.c_int,
+                                        ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.c_void_p]
+    lib.ctcd_snapshot_info.argtypes = [ctypes.c_void_p, ctypes.c_ulonglong, ctypes.POINTER(SnapshotInfo)]
+    lib.ctcd_scorer_fingerprint.argtypes = [ctypes.c_void_p]
+    lib.ctcd_scorer_fingerprint.restype = ctypes.c_ulonglong
     for name in ("ctcd_stream_pool_nodes", "ctcd_stream_pool_capacity", "ctcd_stream_bytes", "ctcd_stream_committed"):
         getattr(lib, name).argtypes = [ctypes.c_void_p]
         getattr(lib, name).restype = ctypes.c_longlong

@@ -32,6 +32,7 @@
 #include "stream_peek.h"
 #include "stream_compact.h"
 #include "stream_commit.h"
+#include "stream_snapshot.h"
 
 namespace {
 
@@ -1485,6 +1486,7 @@ struct ctcd_scorer {
   ctclm::HostScorer host;
   int device = 0;
   char *blob = nullptr;      // one HBM allocation holding every table
+  unsigned long long fingerprint = 0;  // of the tables as uploaded (stream_snapshot.h scorer_fingerprint): images of its streams carry it
   ctclm::LmView dview;       // the tables as the kernel sees them (alpha / beta are refreshed at every launch)
   // Host-side scorer hook (ctcd_scorer_create_callback, lm_callback.h): the device tables are a cache of the callback's
   // answers -- grown between launches (cb_sync); `host` keeps the scalar facts the accessors report
@@ -2195,6 +2197,7 @@ int ctcd_scorer_create(ctcd_scorer **out, double alpha, double beta, const char 
   s->dview.ng = (const ctclm::NgSlot *)(s->blob + o_ng); s->dview.dict = (const ctclm::DictNode *)(s->blob + o_dc);
   s->dview.label_word = (const uint32_t *)(s->blob + o_lw);
   s->dview.dict_lab = (const uint32_t *)(s->blob + o_dl);
+  s->fingerprint = ctcsnap::scorer_fingerprint(h);
   *out = s;
   return CTCD_OK;
 }
@@ -3107,6 +3110,223 @@ int ctcd_stream_commit(ctcd_decoder *d, ctcd_stream **states, int B, ctcd_result
 }
 
 long long ctcd_stream_committed(const ctcd_stream *st) { return st ? st->committed : -1; }
+
+// ---- images of live streams (stream_snapshot.h) -----------------------------------------------------------------------------------
+// the decoder's page-locked region (shared with the compaction and the commit) with room for `need` bytes
+static int snap_region(ctcd_decoder *d, size_t need, char **hb, char **db) {
+  if (d->h_cp_cap < need) {
+    if (d->h_cp) (void)hipHostFree(d->h_cp);
+    d->h_cp = nullptr;
+    d->h_cp_cap = 0;
+    HIP_TRY(hipHostMalloc((void **)&d->h_cp, 2 * need, hipHostMallocMapped | hipHostMallocCoherent));
+    d->h_cp_cap = 2 * need;
+  }
+  *hb = d->h_cp;
+  HIP_TRY(hipHostGetDevicePointer((void **)db, *hb, 0));
+  return CTCD_OK;
+}
+// offsets of the per-stream arrays in that region: blocks | image offsets | meta | pool capacities | node counts
+struct SnapRegion {
+  size_t o_off, o_meta, o_cap, o_nodes, need;
+  explicit SnapRegion(size_t n) {
+    o_off = n * 8;
+    o_meta = 2 * n * 8;
+    o_cap = o_meta + n * sizeof(ctcsnap::SnapMeta);
+    o_nodes = o_cap + n * 4;
+    need = o_nodes + n * 4;
+  }
+};
+
+int ctcd_stream_save(ctcd_decoder *d, ctcd_stream **states, int B, ctcd_bytes_alloc_fn alloc, void *alloc_user, unsigned long long *bytes_out,
+                     void *stream_) {
+  namespace sn = ctcsnap;
+  if (!d || B < 0 || (B > 0 && (!states || !alloc || !bytes_out))) return fail(CTCD_EINVAL, "bad arguments");
+  if (B == 0) return CTCD_OK;
+  CTC_ON_DEVICE(d->device);
+  hipStream_t stream = (hipStream_t)stream_;
+  const unsigned long long call_id = ++g_stream_call_id;
+  for (int b = 0; b < B; ++b) {
+    ctcd_stream *st = states[b];
+    if (!st || st->device != d->device || st->beam != states[0]->beam || st->V != states[0]->V)
+      return fail(CTCD_EINVAL, "stream state does not match the decoder configuration");
+    if (st->scorer != states[0]->scorer) return fail(CTCD_EINVAL, "the streams of one batch must share their scorer");
+    if (st->seen_in_call == call_id) return fail(CTCD_EINVAL, "the same stream state appears twice in one batch");
+    st->seen_in_call = call_id;
+  }
+  const ctcd_scorer *sc = states[0]->scorer;
+  if (sc && sc->cbl) return fail(CTCD_EUNSUPPORTED, "ctcd_stream_save: the states of a stream behind a callback scorer index a per-process cache");
+  const int beam = states[0]->beam, lm = sc ? 1 : 0;
+  // the image is the layout a compaction leaves
+  std::vector<int32_t> live((size_t)B, 0);
+  int rc = compact_streams(d, states, B, live.data(), stream);
+  if (rc) return rc;
+  std::lock_guard<std::mutex> lock(d->mu);
+  const SnapRegion r((size_t)B);
+  char *hb = nullptr, *db = nullptr;
+  if ((rc = snap_region(d, r.need, &hb, &db))) return rc;
+  char **h_blk = (char **)hb;
+  long long *h_off = (long long *)(hb + r.o_off);
+  sn::SnapMeta *h_meta = (sn::SnapMeta *)(hb + r.o_meta);
+  int *h_cap = (int *)(hb + r.o_cap), *h_nodes = (int *)(hb + r.o_nodes);
+  size_t total = 0;
+  for (int b = 0; b < B; ++b) {
+    const ctcd_stream *st = states[b];
+    const int M = st->frames > 0 ? live[b] : 1;
+    if (M < 1 || (long long)M > ctccompact::pool_capacity(st->cap_frames, beam))
+      return fail(CTCD_EINTERNAL, "ctcd_stream_save: node count " + std::to_string(M) + " for item " + std::to_string(b));
+    h_blk[b] = st->block;
+    h_cap[b] = (int)ctccompact::pool_capacity(st->cap_frames, beam);
+    h_nodes[b] = M;
+    h_off[b] = (long long)(total / 4);
+    h_meta[b] = sn::SnapMeta{st->frames, st->committed, sc ? sc->fingerprint : 0ull, st->V, lm ? sn::SNAP_SCORER_BUILTIN : sn::SNAP_SCORER_NONE};
+    bytes_out[b] = sn::snapshot_bytes(beam, lm, M);
+    total += sn::snapshot_padded((size_t)bytes_out[b]);
+  }
+  void *host = alloc(alloc_user, (unsigned long long)total);
+  if (!host) return fail(CTCD_EINVAL, "the image allocator returned no buffer");
+  if (total > d->cp_scratch.cap && (rc = d->cp_scratch.ensure(total + total / 4))) return rc;
+  sn::SnapLaunch l;
+  l.ctl = sn::SnapCtl{(char *const *)db, (const int *)(db + r.o_cap), (const int *)(db + r.o_nodes), (const long long *)(db + r.o_off),
+                      (const sn::SnapMeta *)(db + r.o_meta)};
+  l.staging = (int *)d->cp_scratch.p;
+  l.pool_off = (long long)stream_pool_offset(beam);
+  l.B = B; l.K = beam;
+  HIP_TRY(hipMemsetAsync(l.staging, 0, total, stream));  // (the padding between images travels as zero)
+  const int e = sn::launch_snapshot_export(l, (void *)stream);
+  if (e != (int)hipSuccess) return fail(CTCD_EHIP, std::string("ctc_stream_export_kernel: ") + hipGetErrorString((hipError_t)e));
+  HIP_TRY(hipMemcpyAsync(host, l.staging, total, hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipStreamSynchronize(stream));
+  return CTCD_OK;
+}
+
+int ctcd_snapshot_info(const void *blob, unsigned long long bytes, ctcd_snapshot_info_t *info) {
+  if (!blob || !info || bytes == 0) return fail(CTCD_EINVAL, "ctcd_snapshot_info: bad arguments");
+  ctcsnap::SnapInfo in;
+  const int c = ctcsnap::snapshot_info(blob, (size_t)bytes, &in);
+  if (c != ctcsnap::SNAP_OK) return fail(CTCD_EINVAL, std::string("not a stream image: ") + ctcsnap::snapshot_error_name(c));
+  info->version = in.version; info->beam = in.beam; info->labels = in.labels; info->scorer_kind = in.scorer_kind; info->nodes = in.nodes;
+  info->reserved = 0; info->frames = in.frames; info->committed = in.committed; info->fingerprint = in.fingerprint; info->bytes = in.bytes;
+  return CTCD_OK;
+}
+
+unsigned long long ctcd_scorer_fingerprint(const ctcd_scorer *s) { return s && !s->cbl ? s->fingerprint : 0ull; }
+
+int ctcd_stream_restore(ctcd_decoder *d, ctcd_scorer *scorer, const void *const *blobs, const unsigned long long *bytes, int B, int frames_hint,
+                        ctcd_stream **out, void *stream_) {
+  namespace sn = ctcsnap;
+  namespace cc = ctccompact;
+  if (!d || B < 0 || frames_hint < 0 || (B > 0 && (!blobs || !bytes || !out))) return fail(CTCD_EINVAL, "bad arguments");
+  if (B == 0) return CTCD_OK;
+  for (int b = 0; b < B; ++b) {
+    out[b] = nullptr;
+    if (!blobs[b] || bytes[b] == 0) return fail(CTCD_EINVAL, "ctcd_stream_restore: item " + std::to_string(b) + " is empty");
+  }
+  if (scorer && scorer->cbl) return fail(CTCD_EUNSUPPORTED, "ctcd_stream_restore: no image is saved behind a callback scorer");
+  if (scorer && scorer->device != d->device) return fail(CTCD_EINVAL, "the scorer lives on another device than the decoder");
+  // every image is checked before anything is allocated or uploaded
+  sn::SnapInfo first;
+  {
+    const int c = sn::snapshot_info(blobs[0], (size_t)bytes[0], &first);
+    if (c != sn::SNAP_OK) return fail(CTCD_EINVAL, std::string("ctcd_stream_restore: item 0 is refused: ") + sn::snapshot_error_name(c));
+  }
+  sn::SnapExpect ex;
+  ex.K = first.beam; ex.V = first.labels;
+  ex.scorer_kind = scorer ? sn::SNAP_SCORER_BUILTIN : sn::SNAP_SCORER_NONE;
+  ex.fingerprint = scorer ? scorer->fingerprint : 0ull;
+  ex.lm_states = scorer ? (long long)scorer->host.st_bo.size() : 0;
+  ex.lm_dict = scorer ? (long long)scorer->host.dict.size() : 0;
+  ex.lm_dict_lab = scorer ? (long long)scorer->host.dict_lab.size() : 0;
+  ex.lm_char_based = scorer && scorer->host.char_based ? 1 : 0;
+  ex.lm_dict_wide = scorer ? scorer->dview.dict_wide : 0;
+  if (ex.V < 1 || ex.V > kMaxVocab) return fail(CTCD_EINVAL, "ctcd_stream_restore: item 0 is refused: label count");
+  if (scorer && (size_t)ex.V != scorer->host.labels.size()) return fail(CTCD_EINVAL, "ctcd_stream_restore: item 0 is refused: label count against the scorer");
+  const int beam = ex.K, lm = scorer ? 1 : 0;
+  std::vector<int> nodes((size_t)B);
+  std::vector<long long> frames((size_t)B), committed((size_t)B);
+  size_t total = 0;
+  // (the check reads every word of every image: a large batch is shared among a few threads)
+  std::vector<sn::SnapError> errs((size_t)B);
+  {
+    unsigned long long all = 0;
+    for (int b = 0; b < B; ++b) all += bytes[b];
+    const int nth = all < (4ull << 20) ? 1 : (B < 8 ? B : 8);
+    auto run = [&](int t) { for (int b = t; b < B; b += nth) (void)sn::snapshot_check(blobs[b], (size_t)bytes[b], ex, &errs[(size_t)b]); };
+    std::vector<std::thread> th;
+    for (int t = 1; t < nth; ++t) th.emplace_back(run, t);
+    run(0);
+    for (auto &t : th) t.join();
+  }
+  for (int b = 0; b < B; ++b) {
+    const sn::SnapError &err = errs[(size_t)b];
+    if (err.code != sn::SNAP_OK)
+      return fail(CTCD_EINVAL, "ctcd_stream_restore: item " + std::to_string(b) + " is refused: " + sn::snapshot_error_name(err.code) +
+                                   (err.at >= 0 ? " (at " + std::to_string(err.at) + ")" : std::string()));
+    sn::SnapInfo in;
+    (void)sn::snapshot_info(blobs[b], (size_t)bytes[b], &in);
+    nodes[b] = in.nodes; frames[b] = in.frames; committed[b] = in.committed;
+    total += sn::snapshot_padded((size_t)bytes[b]);
+  }
+  CTC_ON_DEVICE(d->device);
+  hipStream_t stream = (hipStream_t)stream_;
+  std::lock_guard<std::mutex> lock(d->mu);
+  // capacities as after a compaction that left M nodes: max(capacity of the hint, 2 * M) nodes in whole frames
+  const long long hint = frames_hint > 0 ? frames_hint : 1024;
+  std::vector<ctcd_stream *> made;
+  auto drop = [&] { for (ctcd_stream *st : made) { if (st->block) (void)hipFree(st->block); delete st; } };
+  for (int b = 0; b < B; ++b) {
+    const long long for_2m = (2LL * nodes[b] - 1 + beam - 1) / beam;
+    ctcd_stream *st = new ctcd_stream;
+    made.push_back(st);
+    st->device = d->device; st->scorer = scorer; st->V = ex.V; st->beam = beam;
+    st->frames = frames[b]; st->committed = committed[b];
+    st->hint_frames = hint;
+    st->cap_frames = hint > for_2m ? hint : for_2m;
+    if (frames[b] > 0) { st->base_nodes = nodes[b]; st->base_frames = frames[b]; }
+    if (cc::pool_capacity(st->cap_frames, beam) > 0x7fffffffLL) { drop(); return fail(CTCD_EUNSUPPORTED, "stream too long for this beam width"); }
+    st->bytes = stream_block_bytes(st->cap_frames, beam);
+    const hipError_t me = hipMalloc((void **)&st->block, st->bytes);
+    if (me != hipSuccess) { st->block = nullptr; drop(); return fail(CTCD_EHIP, std::string("hipMalloc: ") + hipGetErrorString(me)); }
+  }
+  int rc;
+  const SnapRegion r((size_t)B);
+  char *hb = nullptr, *db = nullptr;
+  if ((rc = snap_region(d, r.need, &hb, &db))) { drop(); return rc; }
+  if (total > d->cp_scratch.cap && (rc = d->cp_scratch.ensure(total + total / 4))) { drop(); return rc; }
+  char **h_blk = (char **)hb;
+  long long *h_off = (long long *)(hb + r.o_off);
+  int *h_cap = (int *)(hb + r.o_cap), *h_nodes = (int *)(hb + r.o_nodes);
+  // one copy brings every image in: straight from the caller's memory where the images lie as ctcd_stream_save laid them out (one
+  // allocation, each at the next multiple of 16 bytes), else from a packed copy
+  bool as_saved = ((uintptr_t)blobs[0] & 3) == 0;
+  size_t at = 0;
+  for (int b = 0; b < B; ++b) {
+    h_blk[b] = made[b]->block;
+    h_cap[b] = (int)cc::pool_capacity(made[b]->cap_frames, beam);
+    h_nodes[b] = nodes[b];
+    h_off[b] = (long long)(at / 4);
+    as_saved = as_saved && (const char *)blobs[b] == (const char *)blobs[0] + at;
+    at += sn::snapshot_padded((size_t)bytes[b]);
+  }
+  const size_t span = total - (sn::snapshot_padded((size_t)bytes[B - 1]) - (size_t)bytes[B - 1]);  // (nothing behind the last image is read)
+  std::vector<char> pack;
+  if (!as_saved) {
+    pack.assign(total, 0);
+    for (int b = 0; b < B; ++b) memcpy(pack.data() + (size_t)h_off[b] * 4, blobs[b], (size_t)bytes[b]);
+  }
+  sn::SnapLaunch l;
+  l.ctl = sn::SnapCtl{(char *const *)db, (const int *)(db + r.o_cap), (const int *)(db + r.o_nodes), (const long long *)(db + r.o_off),
+                      (const sn::SnapMeta *)(db + r.o_meta)};
+  l.staging = (int *)d->cp_scratch.p;
+  l.pool_off = (long long)stream_pool_offset(beam);
+  l.B = B; l.K = beam;
+  (void)lm;
+  hipError_t e = hipMemcpyAsync(l.staging, as_saved ? blobs[0] : (const void *)pack.data(), span, hipMemcpyHostToDevice, stream);
+  if (e == hipSuccess) e = (hipError_t)sn::launch_snapshot_import(l, (void *)stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(stream);
+  if (e != hipSuccess) { drop(); return fail(CTCD_EHIP, std::string("ctc_stream_import_kernel: ") + hipGetErrorString(e)); }
+  for (int b = 0; b < B; ++b) out[b] = made[b];
+  return CTCD_OK;
+}
 
 long long ctcd_stream_pool_nodes(const ctcd_stream *st) {
   return st ? ctccompact::pool_bound(st->frames, st->base_nodes, st->base_frames, st->beam) : -1;

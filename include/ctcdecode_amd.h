@@ -315,6 +315,48 @@ int ctcd_stream_commit(ctcd_decoder *dec, ctcd_stream **states, int B, ctcd_resu
 /* labels the stream has committed so far (-1: st == NULL) */
 long long ctcd_stream_committed(const ctcd_stream *st);
 
+/* Images of live streams in host memory (extension).  ctcd_stream_save writes, per stream, one contiguous byte string that holds
+ * everything the stream is: 32-bit little-endian words [16-word header: magic, format version 1, total words, beam, labels, scorer
+ * kind (0 none / 1 built-in), scorer fingerprint (64 bits), frames fed (64), labels committed (64), nodes M, beam arrays A, two
+ * reserved | the 12 header words of the parked state | A * beam beam-array words | M nodes of 12 bytes | M express words | M high
+ * parts of the time steps]; bytes = 4 * (16 + 12 + A * beam + 5 * M) with A = 14 without a scorer and 26 with one -- a function of
+ * beam, scorer kind and M alone, nothing of it depends on the block's capacity or address.  The image is canonical: saving twice
+ * with no frame in between, or save -> restore -> save, gives identical bytes.
+ * ctcd_stream_save HAS EXACTLY ctcd_stream_compact's EFFECT on the saved streams (an image is the layout a compaction leaves, so the
+ * call compacts first; compaction changes nothing a later call computes) and changes nothing else about them: they stay live and
+ * decode on.  The allocator is called once, when the sizes are known, with the size of the whole batch: image b starts at the sum
+ * of the earlier images' sizes, each rounded up to a multiple of 16 bytes; bytes_out_host[b] receives image b's size.  A stream
+ * without frames saves as the root alone (M = 1) and restores to a fresh stream.  Queued on `stream` behind the chunks already
+ * queued there, and synchronous.
+ * CTCD_EINVAL as for ctcd_stream_compact (a state twice in the batch, another decoder's state, ...), or the allocator returned NULL.
+ * CTCD_EUNSUPPORTED: streams behind a callback scorer (their states index a per-process cache); nothing of them is touched.
+ *
+ * ctcd_stream_restore creates B new streams on `dec` from B images; stream b then behaves bit-identically to the stream image b was
+ * saved from, for every later chunk (on any kernel), peek, compact, commit and stream end: committed labels, absolute frame
+ * numbers, the danger flag, the speculative select's prediction and the order array travel.  `dec` may be another decoder, on
+ * another device or in another process, with the same labels, beam width and blank.  scorer: NULL for images without a scorer, else
+ * a built-in scorer with the image's fingerprint (a 64-bit hash of its tables and of order, char_based, space_id and dictionary size;
+ * alpha / beta are not part of it).  Every image is validated on the host before anything is allocated or uploaded (magic, version,
+ * size, beam / labels / scorer against the call, every index a kernel follows, and the node layout against the image's own depth
+ * and LCP arrays): the call is all or nothing -- if one image is refused (CTCD_EINVAL; ctcd_last_error names the item and the
+ * check) no stream is created and nothing stays allocated.  The restored stream's capacity is max(frames_hint frames (0: 1024),
+ * 2 * M nodes), its bound M + frames since * beam: as after a compaction.  Synchronous. */
+typedef void *(*ctcd_bytes_alloc_fn)(void *user, unsigned long long bytes);
+int ctcd_stream_save(ctcd_decoder *dec, ctcd_stream **states, int B, ctcd_bytes_alloc_fn alloc, void *alloc_user,
+                     unsigned long long *bytes_out_host /* [B] */, void *stream);
+int ctcd_stream_restore(ctcd_decoder *dec, ctcd_scorer *scorer /* or NULL */, const void *const *blobs /* [B] HOST */,
+                        const unsigned long long *bytes /* [B] */, int B, int frames_hint, ctcd_stream **out_states /* [B] */, void *stream);
+/* What an image says about itself; needs no device (a router can look at an image without a GPU).  CTCD_EINVAL: not an image
+ * (NULL, too short, wrong magic / version, or a size that is not the one its own beam / scorer kind / node count give). */
+typedef struct ctcd_snapshot_info_t {
+  int32_t version, beam, labels, scorer_kind, nodes, reserved;
+  long long frames, committed;
+  unsigned long long fingerprint, bytes;
+} ctcd_snapshot_info_t;
+int ctcd_snapshot_info(const void *blob, unsigned long long bytes, ctcd_snapshot_info_t *info);
+/* the fingerprint images saved behind this scorer carry (0: NULL or a callback scorer) */
+unsigned long long ctcd_scorer_fingerprint(const ctcd_scorer *scorer);
+
 /* Host check of the per-item status words written by the last ctcd_beam_decode (synchronises the device). */
 int ctcd_check_status(ctcd_decoder *dec, int B);
 /* ... without blocking: enqueues the copy of the B status words (0 = ok) into `host_status` (page-locked memory) on
