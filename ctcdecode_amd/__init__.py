@@ -5,6 +5,7 @@ ctcdecode/__init__.py:6-123 of the reference; the prefix beam search itself runs
 (one workgroup per utterance, beam in LDS) behind the C ABI in include/ctcdecode_amd.h.
 """
 import ctypes
+import math
 import weakref
 
 import torch
@@ -325,6 +326,23 @@ def _adopt_scorer(scorer, model_path, num_labels, device_index):
     return scorer
 
 
+def _blank_skip_threshold(thr):
+    """The constructor's ``blank_skip``: None (off) or a float in (0, 1]."""
+    if thr is None:
+        return None
+    if isinstance(thr, bool) or not isinstance(thr, (int, float)):
+        raise ValueError("blank_skip must be None or a float in (0, 1], not %r" % (thr,))
+    thr = float(thr)
+    if not (0.0 < thr <= 1.0):  # (NaN fails both compares)
+        raise ValueError("blank_skip must be None or a float in (0, 1], not %r" % (thr,))
+    return thr
+
+
+def _f32(x):
+    """``x`` rounded to float32 (numpy.float32(x)), as a Python float."""
+    return ctypes.c_float(x).value
+
+
 class CTCBeamDecoder(object):
     """See ctcdecode/__init__.py:6-51 of the reference for the meaning of the arguments.
 
@@ -334,10 +352,17 @@ class CTCBeamDecoder(object):
       * positions the reference leaves uninitialised (``[b, p, out_len:]``, rows ``p >= #results``) are zero.
       * ``model_path`` must be an ARPA text model (binary kenlm files are not supported); the scorer's tables are mirrored
         into HBM and queried inside the decode kernel (include/ctcdecode_amd.h, "LM tier").
+      * ``blank_skip``: None (default, off) or a threshold in (0, 1]: every one-shot call drops, on the device and before the beam
+        search, the frames whose blank posterior is GREATER than the threshold, decodes the kept frames, and reports time steps
+        as original frame numbers (include/ctcdecode_amd.h "Blank-frame filter").  The outputs keep their [B, K, T] shapes.
+        The results are those of the reference on the kept frames -- not those of the full decode: a repeated label whose
+        separating blank frames are all skipped collapses.  ``OnlineCTCBeamDecoder`` does not have it.
     """
 
     def __init__(self, labels, model_path=None, alpha=0, beta=0, cutoff_top_n=40, cutoff_prob=1.0, beam_width=100,
-                 num_processes=4, blank_id=0, log_probs_input=False, device=None, logits_input=False, scorer=None):
+                 num_processes=4, blank_id=0, log_probs_input=False, device=None, logits_input=False, scorer=None, blank_skip=None):
+        self._blank_skip = _blank_skip_threshold(blank_skip)
+        self._last_skip = None
         self.cutoff_top_n = cutoff_top_n
         self._beam_width = beam_width
         self._scorer = None
@@ -494,6 +519,70 @@ class CTCBeamDecoder(object):
         _native.check(_native.lib.ctcd_last_resolve_ms(self._handle, ctypes.byref(ms)))
         return float(ms.value)
 
+    def _skip_rows(self, probs, seq_lens):
+        """The blank-frame filter in front of a one-shot call.  ``probs``: the call's rows as ``_input_rows`` returned them, ``seq_lens``
+        on the device or None.  -> (rows, seq_lens', kept, log mode the decode is to be told), or None when the filter is off or there
+        is nothing to filter.  Everything is queued on the current stream; the temporaries are torch allocations there.  Raw logits
+        go through the log-softmax pass first (float32), are filtered in log mode, and the decode is told log-probabilities."""
+        B, T, V = probs.shape
+        if self._blank_skip is None:
+            return None
+        if B == 0 or T == 0:
+            self._last_skip = (None, None, 0, 0)
+            return None
+        if not 0 <= int(self._blank_id) < V:
+            raise ValueError("ctcdecode_amd: blank_id must index the vocabulary")
+        mode = self._log_probs
+        cmp = _f32(self._blank_skip) if mode == 0 else _f32(math.log(self._blank_skip))
+        with torch.cuda.device(self._device):
+            stream = torch.cuda.current_stream(self._device).cuda_stream
+            lens_ptr = seq_lens.data_ptr() if seq_lens is not None else None
+            if mode == 2:
+                lsm = torch.empty((B, T, V), dtype=torch.float32, device=self._device)  # (frames beyond seq_lens: never read)
+                _native.check(_native.lib.ctcd_log_softmax(self._handle, probs.data_ptr(), lens_ptr, B, T, V, lsm.data_ptr(), stream))
+                probs, mode = lsm, 1
+                _set_input_dtype(self, DTYPE_F32)
+            rows = torch.empty_like(probs)
+            kept = torch.empty((B, T), dtype=torch.int32, device=self._device)
+            lens = torch.empty((B,), dtype=torch.int32, device=self._device)
+            _native.check(_native.lib.ctcd_blank_skip(self._handle, probs.data_ptr(), lens_ptr, B, T, V, int(self._blank_id), cmp,
+                                                      rows.data_ptr(), lens.data_ptr(), kept.data_ptr(), stream))
+        self._last_skip = (seq_lens, lens, B, T)
+        return rows, lens, kept, mode
+
+    def skip_blank_frames(self, probs, seq_lens=None):
+        """The filter ``blank_skip`` puts in front of every one-shot call, on its own (the counterpart of ``log_softmax``): returns
+        (rows [B, T, V], seq_lens' [B], kept [B, T]) in HBM -- rows ``[b, :seq_lens'[b]]`` are the kept frames of utterance b in order
+        (the rest is unspecified), ``kept[b, i]`` the original index of the i-th of them (0 from ``seq_lens'[b]`` on).  Follows the
+        decoder's ``blank_id`` and input mode; with ``logits_input=True`` the rows are those of ``log_softmax`` (float32), otherwise
+        they keep the dtype ``decode_device`` would read."""
+        if self._blank_skip is None:
+            raise ValueError("skip_blank_frames needs a decoder built with blank_skip")
+        if probs.dim() != 3:
+            raise ValueError("probs must be [batch, time, labels]")
+        probs = _input_rows(self, probs)
+        B, T, V = probs.shape
+        if seq_lens is not None:
+            seq_lens = seq_lens.to(device=self._device, dtype=torch.int32).contiguous()
+            if seq_lens.numel() != B:
+                raise ValueError("seq_lens must have one entry per batch item")
+        sk = self._skip_rows(probs, seq_lens)
+        if sk is None:  # no utterance or no frame
+            return (probs, torch.zeros((B,), dtype=torch.int32, device=self._device), torch.zeros((B, T), dtype=torch.int32, device=self._device))
+        return sk[0], sk[1], sk[2]
+
+    def last_blank_skip(self):
+        """Test hook: (frames considered, frames kept) of the last call's filter, or None if no call has filtered yet.  Waits for
+        that call."""
+        st = self._last_skip
+        if st is None:
+            return None
+        lens, kept_lens, B, T = st
+        if kept_lens is None:
+            return 0, 0
+        considered = B * T if lens is None else int(lens.clamp(0, T).sum().item())
+        return considered, int(kept_lens.sum().item())
+
     def decode_device(self, probs, seq_lens=None, check=True):
         """``probs``: [B, T, V] tensor (any device / float dtype).  Returns (beam_results, beam_scores, timesteps,
         out_lens) as tensors in HBM on the decoder's device; asynchronous on the current stream when ``check`` is False.
@@ -510,6 +599,10 @@ class CTCBeamDecoder(object):
             if seq_lens.numel() != B:
                 raise ValueError("seq_lens must have one entry per batch item")
         K = self._beam_width
+        log_mode, kept = self._log_probs, None
+        sk = self._skip_rows(probs, seq_lens)
+        if sk is not None:  # blank_skip: the decode sees the kept rows and their counts
+            probs, seq_lens, kept, log_mode = sk
         with torch.cuda.device(self._device):
             output = torch.empty((B, K, T), dtype=torch.int32, device=self._device)
             timesteps = torch.empty((B, K, T), dtype=torch.int32, device=self._device)
@@ -519,15 +612,18 @@ class CTCBeamDecoder(object):
             if self._scorer is not None:  # ctcdecode/__init__.py:87-104 (paddle_beam_decode_lm)
                 self._check(_native.lib.ctcd_beam_decode_lm(
                     self._handle, probs.data_ptr(), seq_lens.data_ptr() if seq_lens is not None else None, B, T, V, K,
-                    self._num_processes, float(self._cutoff_prob), int(self.cutoff_top_n), int(self._blank_id), self._log_probs,
+                    self._num_processes, float(self._cutoff_prob), int(self.cutoff_top_n), int(self._blank_id), log_mode,
                     self._scorer.handle, output.data_ptr(), timesteps.data_ptr(), scores.data_ptr(), out_len.data_ptr(), None, stream))
                 self._last_batch = B  # (last_launch_order: the batch of the last call that was queued)
             else:
                 _native.check(_native.lib.ctcd_beam_decode(
                     self._handle, probs.data_ptr(), seq_lens.data_ptr() if seq_lens is not None else None, B, T, V, K,
-                    self._num_processes, float(self._cutoff_prob), int(self.cutoff_top_n), int(self._blank_id), self._log_probs,
+                    self._num_processes, float(self._cutoff_prob), int(self.cutoff_top_n), int(self._blank_id), log_mode,
                     output.data_ptr(), timesteps.data_ptr(), scores.data_ptr(), out_len.data_ptr(), None, stream))
                 self._last_batch = B  # (last_launch_order: the batch of the last call that was queued)
+            if kept is not None and K > 0:  # time steps back to original frame numbers, behind the decode on its stream
+                _native.check(_native.lib.ctcd_remap_timesteps(self._handle, timesteps.data_ptr(), out_len.data_ptr(), kept.data_ptr(),
+                                                               seq_lens.data_ptr(), B, K, T, stream))
             if check:
                 _native.check(_native.lib.ctcd_check_status(self._handle, B))
         return output, scores, timesteps, out_len
@@ -556,6 +652,22 @@ class CTCBeamDecoder(object):
             if seq_lens.numel() != B:
                 raise ValueError("seq_lens must have one entry per batch item")
         K = self._beam_width
+        log_mode, kept_host = self._log_probs, None
+        if self._blank_skip is not None and B > 0 and T > 0:
+            # blank_skip: a CPU input is uploaded whole (it is not streamed in on this route), the filter runs on the device, and the
+            # map and the counts start their way to page-locked memory while the decode runs
+            if not on_dev:
+                probs = probs.to(device=self._device)
+                if seq_lens is not None:
+                    seq_lens = seq_lens.to(device=self._device)
+                on_dev = True
+            probs, seq_lens, kept, log_mode = self._skip_rows(probs, seq_lens)
+            with torch.cuda.device(self._device):
+                kept_host = (torch.empty((B, T), dtype=torch.int32, pin_memory=True), torch.empty((B,), dtype=torch.int32, pin_memory=True))
+                kept_host[0].copy_(kept, non_blocking=True)
+                kept_host[1].copy_(seq_lens, non_blocking=True)
+        elif self._blank_skip is not None:
+            self._last_skip = (None, None, 0, 0)
         pin = B * K * T > 0
         output = torch.empty((B, K, T), dtype=torch.int32, pin_memory=pin)
         timesteps = torch.empty((B, K, T), dtype=torch.int32, pin_memory=pin)
@@ -565,10 +677,16 @@ class CTCBeamDecoder(object):
             stream = torch.cuda.current_stream(self._device).cuda_stream
             self._check(_native.lib.ctcd_beam_decode_to_host(
                 self._handle, probs.data_ptr(), seq_lens.data_ptr() if seq_lens is not None else None, 1 if on_dev else 0, B, T, V, K,
-                self._num_processes, float(self._cutoff_prob), int(self.cutoff_top_n), int(self._blank_id), self._log_probs,
+                self._num_processes, float(self._cutoff_prob), int(self.cutoff_top_n), int(self._blank_id), log_mode,
                 self._scorer.handle if self._scorer is not None else None, output.data_ptr(), timesteps.data_ptr(), scores.data_ptr(),
                 out_len.data_ptr(), None, stream))
             self._last_batch = B  # (last_launch_order: the batch of the last call that was queued)
+            if kept_host is not None and K > 0:
+                # the map applied on the host, to the valid prefixes alone -- no second pass over the padded tensors -- by as many threads
+                # as the native call expands the results with (max(num_processes, 16))
+                torch.cuda.current_stream(self._device).synchronize()
+                _native.check(_native.lib.ctcd_remap_timesteps_host(timesteps.data_ptr(), out_len.data_ptr(), kept_host[0].data_ptr(),
+                                                                    kept_host[1].data_ptr(), B, K, T, max(int(self._num_processes), 16)))
         return output, scores, timesteps, out_len
 
     def log_softmax(self, logits, seq_lens=None):
@@ -605,6 +723,10 @@ class CTCBeamDecoder(object):
             seq_lens = seq_lens.to(device=self._device, dtype=torch.int32).contiguous()
         K = self._beam_width
         cap = int(_native.lib.ctcd_compact_label_capacity(B, K, T))
+        log_mode, kept = self._log_probs, None
+        sk = self._skip_rows(probs, seq_lens)
+        if sk is not None:  # blank_skip: the decode sees the kept rows and their counts
+            probs, seq_lens, kept, log_mode = sk
         with torch.cuda.device(self._device):
             if getattr(self, "_c_labels", None) is None or self._c_labels.numel() < max(cap, 1):
                 self._c_labels = torch.empty((max(cap, 1),), dtype=torch.int32, device=self._device)  # worst case, reused
@@ -616,10 +738,13 @@ class CTCBeamDecoder(object):
             stream = torch.cuda.current_stream(self._device).cuda_stream
             self._check(_native.lib.ctcd_beam_decode_compact(
                 self._handle, probs.data_ptr(), seq_lens.data_ptr() if seq_lens is not None else None, B, T, V, K, self._num_processes,
-                float(self._cutoff_prob), int(self.cutoff_top_n), int(self._blank_id), self._log_probs,
+                float(self._cutoff_prob), int(self.cutoff_top_n), int(self._blank_id), log_mode,
                 self._scorer.handle if self._scorer is not None else None, hdr.data_ptr(), ent.data_ptr(), self._c_labels.data_ptr(),
                 cnt.data_ptr(), cap, scores.data_ptr(), out_len.data_ptr(), None, stream))
             self._last_batch = B  # (last_launch_order: the batch of the last call that was queued)
+            if kept is not None and K > 0:  # the records' frame numbers back to original frames, behind the decode on its stream
+                _native.check(_native.lib.ctcd_remap_compact(self._handle, hdr.data_ptr(), ent.data_ptr(), self._c_labels.data_ptr(), kept.data_ptr(),
+                                                             seq_lens.data_ptr(), B, K, T, stream))
             _native.check(_native.lib.ctcd_check_status(self._handle, B))
             n = int(cnt.item())
         # (an owned copy: the per-decoder buffer is overwritten by this decoder's next call, possibly while an asynchronous
@@ -642,6 +767,10 @@ class CTCBeamDecoder(object):
             seq_lens = seq_lens.to(device=self._device, dtype=torch.int32).contiguous()
         K = self._beam_width
         cap = int(_native.lib.ctcd_compact_label_capacity(B, K, T))
+        log_mode, kept = self._log_probs, None
+        sk = self._skip_rows(probs, seq_lens)
+        if sk is not None:  # blank_skip: the decode sees the kept rows and their counts
+            probs, seq_lens, kept, log_mode = sk
         with torch.cuda.device(self._device):
             if getattr(self, "_c_labels", None) is None or self._c_labels.numel() < max(cap, 1):
                 self._c_labels = torch.empty((max(cap, 1),), dtype=torch.int32, device=self._device)  # worst case, reused
@@ -653,10 +782,13 @@ class CTCBeamDecoder(object):
             stream = torch.cuda.current_stream(self._device)
             self._check(_native.lib.ctcd_beam_decode_compact(
                 self._handle, probs.data_ptr(), seq_lens.data_ptr() if seq_lens is not None else None, B, T, V, K, self._num_processes,
-                float(self._cutoff_prob), int(self.cutoff_top_n), int(self._blank_id), self._log_probs,
+                float(self._cutoff_prob), int(self.cutoff_top_n), int(self._blank_id), log_mode,
                 self._scorer.handle if self._scorer is not None else None, hdr.data_ptr(), ent.data_ptr(), self._c_labels.data_ptr(),
                 cnt.data_ptr(), cap, scores.data_ptr(), out_len.data_ptr(), None, stream.cuda_stream))
             self._last_batch = B  # (last_launch_order: the batch of the last call that was queued)
+            if kept is not None and K > 0:  # the records' frame numbers back to original frames, behind the decode on its stream
+                _native.check(_native.lib.ctcd_remap_compact(self._handle, hdr.data_ptr(), ent.data_ptr(), self._c_labels.data_ptr(), kept.data_ptr(),
+                                                             seq_lens.data_ptr(), B, K, T, stream.cuda_stream))
             status = torch.empty((max(B, 1),), dtype=torch.int32, pin_memory=True)
             cnt_host = torch.empty((1,), dtype=torch.int32, pin_memory=True)
             _native.check(_native.lib.ctcd_fetch_status_async(self._handle, B, status.data_ptr(), stream.cuda_stream))
@@ -664,7 +796,7 @@ class CTCBeamDecoder(object):
             ev = torch.cuda.Event()
             ev.record(stream)
         return dict(B=B, hdr=hdr, ent=ent, labels=self._c_labels, cnt=cnt, scores=scores, lens=out_len, status=status, cnt_host=cnt_host,
-                    event=ev, keep=(probs, seq_lens))
+                    event=ev, keep=(probs, seq_lens, kept))
 
     def finish_compact(self, ticket):
         """Waits for a ``decode_compact_async`` batch (its own event only, not the stream) and returns what ``decode_compact``

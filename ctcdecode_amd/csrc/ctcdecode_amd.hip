@@ -33,6 +33,7 @@
 #include "stream_compact.h"
 #include "stream_commit.h"
 #include "stream_snapshot.h"
+#include "blank_skip.h"
 
 namespace {
 
@@ -1398,6 +1399,17 @@ struct ctcd_decoder {
   std::mutex mu;
   std::mutex mu_host;  // the host-tensor entry points: compact buffers, page-locked staging and the worker threads are per decoder
 };
+
+// what the blank-frame filter's entry points (blank_skip.hip) need of this file: the decoder's device and input dtype, ctcd_last_error
+namespace ctcskip {
+int skip_decoder_info(const ctcd_decoder *d, SkipDecoderInfo *out) {
+  if (!d || !out) return fail(CTCD_EINVAL, "decoder == NULL");
+  out->device = d->device;
+  out->in_dtype = d->in_dtype;
+  return CTCD_OK;
+}
+int skip_fail(int code, const char *msg) { return fail(code, msg ? msg : ""); }
+}  // namespace ctcskip
 
 // One audio stream's parked decoder state (ctcd_stream_*): a single HBM block [header | beam arrays | node pool].
 struct ctcd_stream {

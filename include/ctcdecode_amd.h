@@ -457,6 +457,40 @@ int ctcd_last_input_dtype(ctcd_decoder *dec);
 int ctcd_set_launch_order(ctcd_decoder *dec, int mode);
 int ctcd_debug_last_launch_order(ctcd_decoder *dec, int32_t *out, int B);
 
+/* ---- Blank-frame filter (no reference counterpart): drop the frames whose blank posterior exceeds a threshold BEFORE the beam
+ * search, on the device, and map the reported time steps back afterwards.  A launch lasts as long as its slowest utterance
+ * walks its frames; CTC posteriors put almost all mass on blank in most frames.  Three calls a C user composes around any
+ * one-shot decode (INTEGRATION.md has the recipe); no existing entry point knows about them.
+ *
+ * ctcd_blank_skip: for utterance b with n = seq_lens[b] clamped to [0, T] (seq_lens NULL: T), frame t < n is SKIPPED iff v > cmp,
+ * v = the float32 value of x[b][t][blank_id] (the element type follows ctcd_set_input_dtype; a half element is widened exactly).
+ * The compare is ordered and strict: NaN is kept, a value equal to cmp is kept; frames at or beyond n are never read.  The caller
+ * chooses cmp for its rows: the threshold itself for probabilities, its logarithm for log-probabilities (raw logits: run
+ * ctcd_log_softmax first and filter its float32 output).  Writes
+ *   out_kept int32 [B][T]   out_kept[b][i] = original index of the i-th kept frame, in order; 0 from out_lens[b] on
+ *   out_lens int32 [B]      the number of kept frames
+ *   out_rows [B][T][V]      of x's element type: rows [b][0 .. out_lens[b]) = the kept rows in order, the rest unspecified;
+ *                           must not be x (an in-place filter is not offered)
+ * A decode of out_rows with seq_lens = out_lens is the decode of the kept frames.
+ * ctcd_remap_timesteps: out_timesteps[b][p][i] = kept[b][out_timesteps[b][p][i]] for i < out_lens[b][p] (read on the device), in
+ * place on the padded [B, K, T] tensor; a word that is no index below kept_lens[b] is left as it is.
+ * ctcd_remap_compact: the same on compact results -- the frame half (upper 16 bits) of every label record the entries of c_ent
+ * own, inside each item's range of c_hdr; T <= 65536 as for compact delivery.  Expanding the remapped records gives the remapped
+ * padded tensors.
+ * ctcd_remap_timesteps_host: ctcd_remap_timesteps on HOST tensors (all four pointers host memory), valid prefixes only, items
+ * spread over num_threads threads; synchronous; needs no decoder.  `kept` is a map ctcd_blank_skip wrote (strictly increasing per
+ * utterance): an utterance none of whose frames was skipped is recognised by its last entry and its rows are not touched.
+ * The device calls are asynchronous on `stream`.  Every call refuses a NULL pointer (seq_lens excepted) and B, T, V or K <= 0 with
+ * CTCD_EINVAL before it touches the device. */
+int ctcd_blank_skip(ctcd_decoder *dec, const void *x, const int32_t *seq_lens, int B, int T, int V, int blank_id, float cmp,
+                    void *out_rows, int32_t *out_lens, int32_t *out_kept, void *stream);
+int ctcd_remap_timesteps(ctcd_decoder *dec, int32_t *out_timesteps, const int32_t *out_lens, const int32_t *kept,
+                         const int32_t *kept_lens, int B, int K, int T, void *stream);
+int ctcd_remap_compact(ctcd_decoder *dec, const int32_t *c_hdr, const int32_t *c_ent, uint32_t *c_labels, const int32_t *kept,
+                       const int32_t *kept_lens, int B, int K, int T, void *stream);
+int ctcd_remap_timesteps_host(int32_t *out_timesteps, const int32_t *out_lens, const int32_t *kept, const int32_t *kept_lens, int B,
+                              int K, int T, int num_threads);
+
 /* Tuning / introspection. */
 int ctcd_set_threads(ctcd_decoder *dec, int threads_per_workgroup); /* 0 = automatic (default); else a power of two in [64, 1024] */
 /* Two workgroups per CU.  The fixed-layout class (beam <= 128, <= 32 labels) has a second build of its kernel that fits
