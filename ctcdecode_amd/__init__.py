@@ -5,7 +5,9 @@ ctcdecode/__init__.py:6-123 of the reference; the prefix beam search itself runs
 (one workgroup per utterance, beam in LDS) behind the C ABI in include/ctcdecode_amd.h.
 """
 import ctypes
+import inspect
 import math
+import operator
 import weakref
 
 import torch
@@ -343,6 +345,21 @@ def _f32(x):
     return ctypes.c_float(x).value
 
 
+def _n_best(n_best, beam_width):
+    """A one-shot call's ``n_best``: None (every row, today's path) or an integer in [1, beam_width]."""
+    if n_best is None:
+        return None
+    if isinstance(n_best, bool) or isinstance(n_best, float):
+        raise ValueError("n_best must be None or an integer in [1, beam_width], not %r" % (n_best,))
+    try:
+        n = operator.index(n_best)
+    except TypeError:
+        raise ValueError("n_best must be None or an integer in [1, beam_width], not %r" % (n_best,))
+    if not 1 <= n <= int(beam_width):
+        raise ValueError("n_best must be None or an integer in [1, beam_width = %d], not %r" % (int(beam_width), n_best))
+    return n
+
+
 class CTCBeamDecoder(object):
     """See ctcdecode/__init__.py:6-51 of the reference for the meaning of the arguments.
 
@@ -352,6 +369,10 @@ class CTCBeamDecoder(object):
       * positions the reference leaves uninitialised (``[b, p, out_len:]``, rows ``p >= #results``) are zero.
       * ``model_path`` must be an ARPA text model (binary kenlm files are not supported); the scorer's tables are mirrored
         into HBM and queried inside the decode kernel (include/ctcdecode_amd.h, "LM tier").
+      * ``n_best`` on every one-shot call (``decode``, ``decode_device``, ``decode_padded``, ``expand_compact``,
+        ``DecodePipeline.submit``): None (default) returns all ``beam_width`` rows as ever; an integer n in [1, beam_width] returns
+        rows 0 .. n-1 alone -- ``output`` / ``timesteps`` [B, n, T], ``scores`` / ``out_lens`` [B, n] -- equal to the full call's
+        ``[:, :n]`` and zero wherever the full call defines nothing (include/ctcdecode_amd.h "n-best results").
       * ``blank_skip``: None (default, off) or a threshold in (0, 1]: every one-shot call drops, on the device and before the beam
         search, the frames whose blank posterior is GREATER than the threshold, decodes the kept frames, and reports time steps
         as original frame numbers (include/ctcdecode_amd.h "Blank-frame filter").  The outputs keep their [B, K, T] shapes.
@@ -583,13 +604,14 @@ class CTCBeamDecoder(object):
         considered = B * T if lens is None else int(lens.clamp(0, T).sum().item())
         return considered, int(kept_lens.sum().item())
 
-    def decode_device(self, probs, seq_lens=None, check=True):
+    def decode_device(self, probs, seq_lens=None, check=True, n_best=None):
         """``probs``: [B, T, V] tensor (any device / float dtype).  Returns (beam_results, beam_scores, timesteps,
         out_lens) as tensors in HBM on the decoder's device; asynchronous on the current stream when ``check`` is False.
         A HIP tensor of dtype bfloat16 / float16 is decoded as it is, without a float32 copy: the results are those of
-        ``probs.float()``, bit for bit.  Other dtypes are cast to float32 first."""
+        ``probs.float()``, bit for bit.  Other dtypes are cast to float32 first.  ``n_best``: rows 0 .. n-1 alone (see the class)."""
         if probs.dim() != 3:
             raise ValueError("probs must be [batch, time, labels]")
+        n_best = _n_best(n_best, self._beam_width)
         probs = _input_rows(self, probs)
         B, T, V = probs.shape
         if V != self._num_labels:
@@ -603,13 +625,21 @@ class CTCBeamDecoder(object):
         sk = self._skip_rows(probs, seq_lens)
         if sk is not None:  # blank_skip: the decode sees the kept rows and their counts
             probs, seq_lens, kept, log_mode = sk
+        R = K if n_best is None else n_best  # result rows per item
         with torch.cuda.device(self._device):
-            output = torch.empty((B, K, T), dtype=torch.int32, device=self._device)
-            timesteps = torch.empty((B, K, T), dtype=torch.int32, device=self._device)
-            scores = torch.empty((B, K), dtype=torch.float32, device=self._device)
-            out_len = torch.empty((B, K), dtype=torch.int32, device=self._device)
+            output = torch.empty((B, R, T), dtype=torch.int32, device=self._device)
+            timesteps = torch.empty((B, R, T), dtype=torch.int32, device=self._device)
+            scores = torch.empty((B, R), dtype=torch.float32, device=self._device)
+            out_len = torch.empty((B, R), dtype=torch.int32, device=self._device)
             stream = torch.cuda.current_stream(self._device).cuda_stream
-            if self._scorer is not None:  # ctcdecode/__init__.py:87-104 (paddle_beam_decode_lm)
+            if n_best is not None:  # compact records into the decoder's scratch, the n-best expansion behind them on the stream
+                self._check(_native.lib.ctcd_beam_decode_nbest(
+                    self._handle, probs.data_ptr(), seq_lens.data_ptr() if seq_lens is not None else None, B, T, V, K,
+                    self._num_processes, float(self._cutoff_prob), int(self.cutoff_top_n), int(self._blank_id), log_mode,
+                    self._scorer.handle if self._scorer is not None else None, n_best, output.data_ptr(), timesteps.data_ptr(),
+                    scores.data_ptr(), out_len.data_ptr(), None, stream))
+                self._last_batch = B  # (last_launch_order: the batch of the last call that was queued)
+            elif self._scorer is not None:  # ctcdecode/__init__.py:87-104 (paddle_beam_decode_lm)
                 self._check(_native.lib.ctcd_beam_decode_lm(
                     self._handle, probs.data_ptr(), seq_lens.data_ptr() if seq_lens is not None else None, B, T, V, K,
                     self._num_processes, float(self._cutoff_prob), int(self.cutoff_top_n), int(self._blank_id), log_mode,
@@ -623,21 +653,24 @@ class CTCBeamDecoder(object):
                 self._last_batch = B  # (last_launch_order: the batch of the last call that was queued)
             if kept is not None and K > 0:  # time steps back to original frame numbers, behind the decode on its stream
                 _native.check(_native.lib.ctcd_remap_timesteps(self._handle, timesteps.data_ptr(), out_len.data_ptr(), kept.data_ptr(),
-                                                               seq_lens.data_ptr(), B, K, T, stream))
+                                                               seq_lens.data_ptr(), B, R, T, stream))
             if check:
                 _native.check(_native.lib.ctcd_check_status(self._handle, B))
         return output, scores, timesteps, out_len
 
-    def decode(self, probs, seq_lens=None):
+    def decode(self, probs, seq_lens=None, *, n_best=None):
         """Drop-in for ctcdecode/__init__.py:53-123: returns CPU tensors (output, scores, timesteps, out_seq_len).
 
         The results leave the GPU in compact form (every beam only the labels it does not share with its neighbour in the
         trie, include/ctcdecode_amd.h) and ``num_processes`` host threads expand them into the four tensors.
 
         A HIP tensor of dtype bfloat16 / float16 is decoded without a float32 copy (the results of ``probs.float()``, bit for
-        bit); a CPU tensor of any dtype is cast to float32 on the host, as the reference does (ctcdecode/__init__.py:77)."""
+        bit); a CPU tensor of any dtype is cast to float32 on the host, as the reference does (ctcdecode/__init__.py:77).
+
+        ``n_best``: rows 0 .. n-1 alone (see the class): the page-locked tensors are [B, n, T] and the host threads expand those rows only."""
         if probs.dim() != 3:
             raise ValueError("probs must be [batch, time, labels]")
+        n_best = _n_best(n_best, self._beam_width)
         on_dev = probs.is_cuda
         if on_dev:
             probs = _input_rows(self, probs)
@@ -668,26 +701,41 @@ class CTCBeamDecoder(object):
                 kept_host[1].copy_(seq_lens, non_blocking=True)
         elif self._blank_skip is not None:
             self._last_skip = (None, None, 0, 0)
-        pin = B * K * T > 0
-        output = torch.empty((B, K, T), dtype=torch.int32, pin_memory=pin)
-        timesteps = torch.empty((B, K, T), dtype=torch.int32, pin_memory=pin)
-        scores = torch.empty((B, K), dtype=torch.float32, pin_memory=pin)
-        out_len = torch.empty((B, K), dtype=torch.int32, pin_memory=pin)
+        R = K if n_best is None else n_best  # result rows per item
+        pin = B * R * T > 0
+        output = torch.empty((B, R, T), dtype=torch.int32, pin_memory=pin)
+        timesteps = torch.empty((B, R, T), dtype=torch.int32, pin_memory=pin)
+        scores = torch.empty((B, R), dtype=torch.float32, pin_memory=pin)
+        out_len = torch.empty((B, R), dtype=torch.int32, pin_memory=pin)
         with torch.cuda.device(self._device):
             stream = torch.cuda.current_stream(self._device).cuda_stream
-            self._check(_native.lib.ctcd_beam_decode_to_host(
-                self._handle, probs.data_ptr(), seq_lens.data_ptr() if seq_lens is not None else None, 1 if on_dev else 0, B, T, V, K,
-                self._num_processes, float(self._cutoff_prob), int(self.cutoff_top_n), int(self._blank_id), log_mode,
-                self._scorer.handle if self._scorer is not None else None, output.data_ptr(), timesteps.data_ptr(), scores.data_ptr(),
-                out_len.data_ptr(), None, stream))
+            if n_best is not None:
+                self._check(_native.lib.ctcd_beam_decode_to_host_nbest(
+                    self._handle, probs.data_ptr(), seq_lens.data_ptr() if seq_lens is not None else None, 1 if on_dev else 0, B, T, V, K,
+                    self._num_processes, float(self._cutoff_prob), int(self.cutoff_top_n), int(self._blank_id), log_mode,
+                    self._scorer.handle if self._scorer is not None else None, n_best, output.data_ptr(), timesteps.data_ptr(),
+                    scores.data_ptr(), out_len.data_ptr(), None, stream))
+            else:
+                self._check(_native.lib.ctcd_beam_decode_to_host(
+                    self._handle, probs.data_ptr(), seq_lens.data_ptr() if seq_lens is not None else None, 1 if on_dev else 0, B, T, V, K,
+                    self._num_processes, float(self._cutoff_prob), int(self.cutoff_top_n), int(self._blank_id), log_mode,
+                    self._scorer.handle if self._scorer is not None else None, output.data_ptr(), timesteps.data_ptr(), scores.data_ptr(),
+                    out_len.data_ptr(), None, stream))
             self._last_batch = B  # (last_launch_order: the batch of the last call that was queued)
             if kept_host is not None and K > 0:
                 # the map applied on the host, to the valid prefixes alone -- no second pass over the padded tensors -- by as many threads
                 # as the native call expands the results with (max(num_processes, 16))
                 torch.cuda.current_stream(self._device).synchronize()
                 _native.check(_native.lib.ctcd_remap_timesteps_host(timesteps.data_ptr(), out_len.data_ptr(), kept_host[0].data_ptr(),
-                                                                    kept_host[1].data_ptr(), B, K, T, max(int(self._num_processes), 16)))
+                                                                    kept_host[1].data_ptr(), B, R, T, max(int(self._num_processes), 16)))
         return output, scores, timesteps, out_len
+
+    # The drop-in call declares the reference's parameters and nothing else (ctcdecode/__init__.py:53; tests/test_abi.py holds the class
+    # to it): code that inspects ``decode`` sees ``(self, probs, seq_lens=None)``.  ``n_best`` is an extension that can only be given by
+    # keyword; it is documented in the docstring above and in the class's.
+    decode.__signature__ = inspect.Signature([inspect.Parameter("self", inspect.Parameter.POSITIONAL_OR_KEYWORD),
+                                              inspect.Parameter("probs", inspect.Parameter.POSITIONAL_OR_KEYWORD),
+                                              inspect.Parameter("seq_lens", inspect.Parameter.POSITIONAL_OR_KEYWORD, default=None)])
 
     def log_softmax(self, logits, seq_lens=None):
         """The float32 log_softmax that ``logits_input=True`` applies before decoding, as a tensor in HBM ([B, T, V]; frames at
@@ -706,9 +754,10 @@ class CTCBeamDecoder(object):
                                                        B, T, V, out.data_ptr(), stream))
         return out
 
-    def decode_padded(self, probs, seq_lens=None):
-        """The same call with the padded [B, K, T] tensors crossing PCIe (the delivery of round 1; kept for comparison)."""
-        return _to_host(self.decode_device(probs, seq_lens))
+    def decode_padded(self, probs, seq_lens=None, n_best=None):
+        """The same call with the padded [B, K, T] tensors crossing PCIe (the delivery of round 1; kept for comparison); with ``n_best``
+        the [B, n, T] ones."""
+        return _to_host(self.decode_device(probs, seq_lens, n_best=n_best))
 
     def decode_compact(self, probs, seq_lens=None):
         """Device-resident compact results: (c_hdr [B,4], c_ent [B,K,4], c_labels [n], scores [B,K], out_lens [B,K]) in HBM --
@@ -811,9 +860,28 @@ class CTCBeamDecoder(object):
             labels = ticket["labels"][:n].clone()  # owned: the decoder's label buffer belongs to its next call
         return ticket["hdr"], ticket["ent"], labels, ticket["scores"], ticket["lens"]
 
-    def expand_compact(self, hdr, ent, labels, T):
-        """(c_hdr, c_ent, c_labels) of any number of items -> (output [B,K,T], timesteps [B,K,T]) in HBM."""
+    def expand_compact(self, hdr, ent, labels, T, n_best=None):
+        """(c_hdr, c_ent, c_labels) of any number of items -> (output [B,K,T], timesteps [B,K,T]) in HBM.  ``n_best`` = n: rows 0 .. n-1
+        alone, [B,n,T], zero outside the valid region; every record index is checked on the device, a malformed record zeroes the rows
+        that depend on it and raises NativeError here (this form waits for the expansion)."""
         B, K = int(ent.shape[0]), int(ent.shape[1])
+        n_best = _n_best(n_best, K)
+        if n_best is not None:
+            with torch.cuda.device(self._device):
+                output = torch.empty((B, n_best, T), dtype=torch.int32, device=self._device)
+                timesteps = torch.empty((B, n_best, T), dtype=torch.int32, device=self._device)
+                status = torch.zeros((max(B, 1),), dtype=torch.int32, device=self._device)
+                n_labels = int(labels.numel())
+                labels = labels.contiguous() if n_labels else torch.zeros((1,), dtype=torch.int32, device=self._device)  # (no label at all: a non-null pointer)
+                stream = torch.cuda.current_stream(self._device).cuda_stream
+                _native.check(_native.lib.ctcd_expand_compact_nbest(self._handle, hdr.contiguous().data_ptr(), ent.contiguous().data_ptr(), labels.data_ptr(),
+                                                                    n_labels, B, K, T, n_best, output.data_ptr(), timesteps.data_ptr(),
+                                                                    status.data_ptr(), stream))
+                st = status.cpu()
+            if bool((st != 0).any()):
+                b = int((st != 0).nonzero()[0])
+                raise _native.NativeError("ctcdecode_amd: malformed compact record (status %d) for item %d" % (int(st[b]), b))
+            return output, timesteps
         with torch.cuda.device(self._device):
             output = torch.empty((B, K, T), dtype=torch.int32, device=self._device)
             timesteps = torch.empty((B, K, T), dtype=torch.int32, device=self._device)
@@ -886,14 +954,16 @@ class DecodePipeline(object):
         dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
         return 2 if batch < torch.cuda.get_device_properties(dev).multi_processor_count else 1
 
-    def submit(self, probs, seq_lens=None):
+    def submit(self, probs, seq_lens=None, n_best=None):
+        """Queues a batch; ``n_best`` as in ``CTCBeamDecoder.decode_device``."""
         slot = self._serial % len(self._decs)
+        n_best = _n_best(n_best, self._decs[slot]._beam_width)  # (refused before the slot's previous launch is waited for)
         if self._pending[slot] is not None:
             self._finish(self._pending[slot])
         dec, stream = self._decs[slot], self._streams[slot]
         stream.wait_stream(torch.cuda.current_stream(self._device))  # (the caller's tensors are ready on its own stream)
         with torch.cuda.stream(stream):
-            res = dec.decode_device(probs, seq_lens, check=False)
+            res = dec.decode_device(probs, seq_lens, check=False, n_best=n_best)
             ev = torch.cuda.Event()
             ev.record(stream)
         # (the launch reads the caller's tensors on the side stream: they stay referenced until it has finished -- a tensor

@@ -34,6 +34,7 @@
 #include "stream_commit.h"
 #include "stream_snapshot.h"
 #include "blank_skip.h"
+#include "nbest.h"
 
 namespace {
 
@@ -1410,6 +1411,17 @@ int skip_decoder_info(const ctcd_decoder *d, SkipDecoderInfo *out) {
 }
 int skip_fail(int code, const char *msg) { return fail(code, msg ? msg : ""); }
 }  // namespace ctcskip
+
+// ... and the n-best expansion's (nbest.hip): the decoder's device and LDS limit
+namespace ctcnbest {
+int nbest_decoder_info(const ctcd_decoder *d, NbestDecoderInfo *out) {
+  if (!d || !out) return fail(CTCD_EINVAL, "decoder == NULL");
+  out->device = d->device;
+  out->max_lds = d->max_lds;
+  return CTCD_OK;
+}
+int nbest_fail(int code, const char *msg) { return fail(code, msg ? msg : ""); }
+}  // namespace ctcnbest
 
 // One audio stream's parked decoder state (ctcd_stream_*): a single HBM block [header | beam arrays | node pool].
 struct ctcd_stream {
@@ -3620,18 +3632,72 @@ int ctcd_expand_compact(ctcd_decoder *d, const int32_t *c_hdr, const int32_t *c_
   return CTCD_OK;
 }
 
+// Rows 0 .. n-1 alone, device tensors in and out, nothing read back in between: the decode hands its results over in compact
+// form into the decoder's own scratch and the n-best expansion (nbest.hip) follows on the same stream.  Where the compact form
+// is not to be had (T > 65536, T == 0, a callback scorer, a beam the expansion's tables do not fit) the decode writes its padded
+// tensors into scratch and rows [:, :n] are copied out of them: the same results.  The scratch belongs to the decoder's next
+// call, which is ordered behind this one on `stream`.
+int ctcd_beam_decode_nbest(ctcd_decoder *d, const float *probs, const int32_t *seq_lens, int B, int T, int V, int beam, int /*num_processes*/,
+                           double cutoff_prob, int cutoff_top_n, int blank_id, int log_input, ctcd_scorer *scorer, int n_best, int32_t *out_tok,
+                           int32_t *out_ts, float *out_sc, int32_t *out_len, int32_t *n_results, void *stream_) {
+  if (!d) return fail(CTCD_EINVAL, "decoder == NULL");
+  int rc = check_args(B, T, V, beam, cutoff_top_n, blank_id, probs, out_tok, out_ts, out_sc, out_len);
+  if (rc) return rc;
+  if (n_best < 1 || n_best > beam) return fail(CTCD_EINVAL, "n_best must be an integer in [1, beam_width]");
+  if (B == 0) return CTCD_OK;
+  std::lock_guard<std::mutex> host_lock(d->mu_host);  // (the scratch is the host-tensor entry points')
+  CTC_ON_DEVICE(d->device);
+  hipStream_t stream = (hipStream_t)stream_;
+  const size_t kk = (size_t)B * beam;
+  const bool hook = scorer && scorer->cbl;
+  const long long cap = ctcd_compact_label_capacity(B, beam, T);
+  const ctcnbest::NbestDecoderInfo inf{d->device, d->max_lds};
+  if (T > 65536 || V > 65535 || T == 0 || hook || cap > 0xFFFFFFFFLL || !ctcnbest::nbest_expand_fits(inf, beam, n_best)) {
+    const size_t rowb = (size_t)T * 4, kt = kk * rowb, nb = (size_t)n_best;
+    const size_t o_ts = (kt + 15) / 16 * 16, o_sc = o_ts * 2, o_ln = o_sc + (kk * 4 + 15) / 16 * 16, o_nr = o_ln + (kk * 4 + 15) / 16 * 16;
+    if ((rc = d->stage_out.ensure(o_nr + (size_t)B * 4 + 16))) return rc;
+    char *dout = (char *)d->stage_out.p;
+    int32_t *nr = n_results ? n_results : (int32_t *)(dout + o_nr);
+    if (hook)
+      rc = decode_lm_callback(d, probs, seq_lens, B, T, V, beam, cutoff_prob, cutoff_top_n, blank_id, log_input, scorer, (int32_t *)dout,
+                              (int32_t *)(dout + o_ts), (float *)(dout + o_sc), (int32_t *)(dout + o_ln), nr, stream);
+    else
+      rc = decode_common(d, probs, seq_lens, B, T, V, beam, cutoff_prob, cutoff_top_n, blank_id, log_input, (int32_t *)dout, (int32_t *)(dout + o_ts),
+                         (float *)(dout + o_sc), (int32_t *)(dout + o_ln), nr, stream, nullptr, scorer);
+    if (rc) return rc;
+    if (rowb) {
+      HIP_TRY(hipMemcpy2DAsync(out_tok, nb * rowb, dout, (size_t)beam * rowb, nb * rowb, (size_t)B, hipMemcpyDeviceToDevice, stream));
+      HIP_TRY(hipMemcpy2DAsync(out_ts, nb * rowb, dout + o_ts, (size_t)beam * rowb, nb * rowb, (size_t)B, hipMemcpyDeviceToDevice, stream));
+    }
+    HIP_TRY(hipMemcpy2DAsync(out_sc, nb * 4, dout + o_sc, (size_t)beam * 4, nb * 4, (size_t)B, hipMemcpyDeviceToDevice, stream));
+    HIP_TRY(hipMemcpy2DAsync(out_len, nb * 4, dout + o_ln, (size_t)beam * 4, nb * 4, (size_t)B, hipMemcpyDeviceToDevice, stream));
+    return CTCD_OK;
+  }
+  if ((rc = d->c_hdr.ensure((size_t)B * 16)) || (rc = d->c_ent.ensure(kk * 16)) || (rc = d->c_rag.ensure((size_t)cap * 4)) ||
+      (rc = d->c_cnt.ensure(256)) || (rc = d->c_sc.ensure(kk * 4)) || (rc = d->c_ln.ensure(kk * 4 + (size_t)B * 4)))
+    return rc;
+  int32_t *nr = n_results ? n_results : (int32_t *)((char *)d->c_ln.p + kk * 4);
+  CompactOut co{(int32_t *)d->c_hdr.p, (int32_t *)d->c_ent.p, (uint32_t *)d->c_rag.p, (unsigned *)d->c_cnt.p, (unsigned)cap};
+  rc = decode_common(d, probs, seq_lens, B, T, V, beam, cutoff_prob, cutoff_top_n, blank_id, log_input, nullptr, nullptr, (float *)d->c_sc.p,
+                     (int32_t *)d->c_ln.p, nr, stream, nullptr, scorer, &co);
+  if (rc) return rc;
+  return ctcnbest::launch_nbest_expand(inf, co.hdr, co.ent, co.rag, (unsigned long long)cap, (const float *)d->c_sc.p, (const int32_t *)d->c_ln.p, B, beam, T,
+                                       n_best, out_tok, out_ts, out_sc, out_len, (int32_t *)d->status.p, stream);
+}
+
 // The reference's call as its Python makes it (ctcdecode/__init__.py:77-123 -> paddle_beam_decode[_lm]): the four results
-// arrive as HOST tensors.  probs / seq_lens may live on either side (probs_on_device != 0: both are device pointers).
+// arrive as HOST tensors. probs / seq_lens may live on either side (probs_on_device != 0: both are device pointers).
 // The kernel hands its results over in compact form, they cross PCIe compact, and host threads expand them.
 static int decode_to_host_locked(ctcd_decoder *d, const float *probs, const int32_t *seq_lens, int probs_on_device, int B, int T, int V,
                                  int beam, int num_processes, double cutoff_prob, int cutoff_top_n, int blank_id, int log_input,
                                  ctcd_scorer *scorer, int32_t *out_tok, int32_t *out_ts, float *out_sc, int32_t *out_len,
-                                 int32_t *n_results, void *stream_);
+                                 int32_t *n_results, void *stream_, int n_best);
 
-int ctcd_beam_decode_to_host(ctcd_decoder *d, const float *probs, const int32_t *seq_lens, int probs_on_device, int B, int T, int V,
-                             int beam, int num_processes, double cutoff_prob, int cutoff_top_n, int blank_id, int log_input,
-                             ctcd_scorer *scorer, int32_t *out_tok, int32_t *out_ts, float *out_sc, int32_t *out_len,
-                             int32_t *n_results, void *stream_) {
+// (n_best: 0 = every row, the [B, beam, ...] tensors; n in [1, beam] = rows 0 .. n-1 alone, [B, n, ...] tensors)
+static int decode_to_host(ctcd_decoder *d, const float *probs, const int32_t *seq_lens, int probs_on_device, int B, int T, int V,
+                          int beam, int num_processes, double cutoff_prob, int cutoff_top_n, int blank_id, int log_input,
+                          ctcd_scorer *scorer, int32_t *out_tok, int32_t *out_ts, float *out_sc, int32_t *out_len,
+                          int32_t *n_results, void *stream_, int n_best) {
   if (!d) return fail(CTCD_EINVAL, "decoder == NULL");
   int rc = check_args(B, T, V, beam, cutoff_top_n, blank_id, probs, out_tok, out_ts, out_sc, out_len);
   if (rc) return rc;
@@ -3639,7 +3705,7 @@ int ctcd_beam_decode_to_host(ctcd_decoder *d, const float *probs, const int32_t 
   if (B == 0) return CTCD_OK;
   std::lock_guard<std::mutex> host_lock(d->mu_host);
   rc = decode_to_host_locked(d, probs, seq_lens, probs_on_device, B, T, V, beam, num_processes, cutoff_prob, cutoff_top_n, blank_id, log_input,
-                             scorer, out_tok, out_ts, out_sc, out_len, n_results, stream_);
+                             scorer, out_tok, out_ts, out_sc, out_len, n_results, stream_, n_best);
   if (rc == CTCD_EINTERNAL && d->input_timed_out) {
     // The streamed rows did not reach the kernel in time (its row fetch gives up after about a second): on this system the
     // copy stream evidently does not run beside the kernel.  Decode again the plain way, and stay with it.
@@ -3647,15 +3713,32 @@ int ctcd_beam_decode_to_host(ctcd_decoder *d, const float *probs, const int32_t 
     d->no_input_streaming = true;
     if (d->copy_stream) (void)hipStreamSynchronize(d->copy_stream);
     rc = decode_to_host_locked(d, probs, seq_lens, probs_on_device, B, T, V, beam, num_processes, cutoff_prob, cutoff_top_n, blank_id, log_input,
-                               scorer, out_tok, out_ts, out_sc, out_len, n_results, stream_);
+                               scorer, out_tok, out_ts, out_sc, out_len, n_results, stream_, n_best);
   }
   return rc;
+}
+
+int ctcd_beam_decode_to_host(ctcd_decoder *d, const float *probs, const int32_t *seq_lens, int probs_on_device, int B, int T, int V,
+                             int beam, int num_processes, double cutoff_prob, int cutoff_top_n, int blank_id, int log_input,
+                             ctcd_scorer *scorer, int32_t *out_tok, int32_t *out_ts, float *out_sc, int32_t *out_len,
+                             int32_t *n_results, void *stream_) {
+  return decode_to_host(d, probs, seq_lens, probs_on_device, B, T, V, beam, num_processes, cutoff_prob, cutoff_top_n, blank_id, log_input, scorer, out_tok,
+                        out_ts, out_sc, out_len, n_results, stream_, 0);
+}
+
+int ctcd_beam_decode_to_host_nbest(ctcd_decoder *d, const float *probs, const int32_t *seq_lens, int probs_on_device, int B, int T, int V,
+                                   int beam, int num_processes, double cutoff_prob, int cutoff_top_n, int blank_id, int log_input,
+                                   ctcd_scorer *scorer, int n_best, int32_t *out_tok, int32_t *out_ts, float *out_sc, int32_t *out_len,
+                                   int32_t *n_results, void *stream_) {
+  if (beam > 0 && (n_best < 1 || n_best > beam)) return fail(CTCD_EINVAL, "n_best must be an integer in [1, beam_width]");
+  return decode_to_host(d, probs, seq_lens, probs_on_device, B, T, V, beam, num_processes, cutoff_prob, cutoff_top_n, blank_id, log_input, scorer, out_tok,
+                        out_ts, out_sc, out_len, n_results, stream_, n_best);
 }
 
 static int decode_to_host_locked(ctcd_decoder *d, const float *probs, const int32_t *seq_lens, int probs_on_device, int B, int T, int V,
                                  int beam, int num_processes, double cutoff_prob, int cutoff_top_n, int blank_id, int log_input,
                                  ctcd_scorer *scorer, int32_t *out_tok, int32_t *out_ts, float *out_sc, int32_t *out_len,
-                                 int32_t *n_results, void *stream_) {
+                                 int32_t *n_results, void *stream_, int n_best) {
   int rc;
   CTC_ON_DEVICE(d->device);
   hipStream_t stream = (hipStream_t)stream_;
@@ -3721,6 +3804,17 @@ static int decode_to_host_locked(ctcd_decoder *d, const float *probs, const int3
                          (float *)(dout + o_sc), (int32_t *)(dout + o_ln), (int32_t *)(dout + o_nr), stream, nullptr, scorer);
     if (rc) return rc;
     if ((rc = ctcd_check_status(d, B))) return rc;
+    if (n_best) {  // rows [:, :n] alone cross PCIe (the full decode defines them everywhere: zero outside the valid region)
+      const size_t rowb = (size_t)T * 4, nb = (size_t)n_best;
+      if (rowb) {
+        HIP_TRY(hipMemcpy2D(out_tok, nb * rowb, dout, (size_t)beam * rowb, nb * rowb, (size_t)B, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy2D(out_ts, nb * rowb, dout + o_ts, (size_t)beam * rowb, nb * rowb, (size_t)B, hipMemcpyDeviceToHost));
+      }
+      HIP_TRY(hipMemcpy2D(out_sc, nb * 4, dout + o_sc, (size_t)beam * 4, nb * 4, (size_t)B, hipMemcpyDeviceToHost));
+      HIP_TRY(hipMemcpy2D(out_len, nb * 4, dout + o_ln, (size_t)beam * 4, nb * 4, (size_t)B, hipMemcpyDeviceToHost));
+      if (n_results) HIP_TRY(hipMemcpy(n_results, dout + o_nr, (size_t)B * 4, hipMemcpyDeviceToHost));
+      return CTCD_OK;
+    }
     if (kt) {
       HIP_TRY(hipMemcpy(out_tok, dout, kt, hipMemcpyDeviceToHost));
       HIP_TRY(hipMemcpy(out_ts, dout + o_ts, kt, hipMemcpyDeviceToHost));
@@ -3781,15 +3875,21 @@ static int decode_to_host_locked(ctcd_decoder *d, const float *probs, const int3
       if (!d->stall_input_test) HIP_TRY(hipMemcpyAsync(fg, &d->h_cnt[c], 4, hipMemcpyHostToDevice, d->copy_stream));
     }
   }
-  HIP_TRY(hipMemcpyAsync(out_sc, d->c_sc.p, kk * 4, hipMemcpyDeviceToHost, stream));
-  HIP_TRY(hipMemcpyAsync(out_len, d->c_ln.p, kk * 4, hipMemcpyDeviceToHost, stream));
+  if (n_best) {  // columns [:n] of the decode's [B, beam] scores and lengths (zero beyond an item's results)
+    HIP_TRY(hipMemcpy2DAsync(out_sc, (size_t)n_best * 4, d->c_sc.p, (size_t)beam * 4, (size_t)n_best * 4, (size_t)B, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipMemcpy2DAsync(out_len, (size_t)n_best * 4, d->c_ln.p, (size_t)beam * 4, (size_t)n_best * 4, (size_t)B, hipMemcpyDeviceToHost, stream));
+  } else {
+    HIP_TRY(hipMemcpyAsync(out_sc, d->c_sc.p, kk * 4, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipMemcpyAsync(out_len, d->c_ln.p, kk * 4, hipMemcpyDeviceToHost, stream));
+  }
   if (n_results) HIP_TRY(hipMemcpyAsync(n_results, d_nres, (size_t)B * 4, hipMemcpyDeviceToHost, stream));
+  const int rows_out = n_best ? n_best : beam;  // result rows per item in the caller's tensors
   {
     if (!d->workers) d->workers = new HostPool;
     // host threads that expand the results (memory-bound work: 8 bytes written per label position of the padded tensors;
     // the reference's default num_processes = 4 was chosen for its CPU decode): one per 4 MB of output, between 16 and 64,
     // more if the caller asks, never more than the machine has.  The pool grows when a later call wants more.
-    const long long out_mb = (long long)B * beam * T * 8 >> 20;
+    const long long out_mb = (long long)B * rows_out * T * 8 >> 20;
     const int want = std::max<long long>(num_processes, std::min<long long>(64, std::max<long long>(16, out_mb / 4)));
     const int target = std::max(1, std::min(want, (int)std::thread::hardware_concurrency()));
     if (target > (int)d->workers->th.size()) d->workers->start(target - (int)d->workers->th.size());
@@ -3799,6 +3899,11 @@ static int decode_to_host_locked(ctcd_decoder *d, const float *probs, const int3
   std::atomic<int> finished{0}, sync_rc{0};
   std::mutex late_mu;
   std::vector<int> late;  // utterances the kernel did not mirror (labels beyond the mirror) -- or that never reported
+  // n-best: the rows below n alone are expanded (nbest.h); a malformed record is reported, its rows come out zero
+  std::vector<unsigned char> row_ok(n_best ? (size_t)B * n_best : 0);
+  unsigned char *rok = row_ok.data();
+  std::atomic<int> bad_item{-1};
+  const unsigned long long mir_labels = co.m_cap, dev_labels = (unsigned long long)cap;
   const int dev = d->device;
   // job 0 waits for the stream (kernel + the small copies above) and tells the others; jobs 1 .. B expand utterance i - 1
   // as soon as its flag is up
@@ -3815,7 +3920,9 @@ static int decode_to_host_locked(ctcd_decoder *d, const float *probs, const int3
       if (spin > 64) std::this_thread::sleep_for(std::chrono::microseconds(20));
     if (v == 0) v = done[b];  // (the kernel has ended: whatever it wrote is visible)
     std::atomic_thread_fence(std::memory_order_acquire);
-    if (v == 1) {
+    if (v == 1 && n_best) {
+      if (ctcnbest::expand_item_nbest_host(hh, he, hl, mir_labels, b, beam, T, n_best, out_tok, out_ts, rok + (size_t)b * n_best)) bad_item = b;
+    } else if (v == 1) {
       ctcbeam::expand_item_host(hh, he, hl, b, beam, T, out_tok, out_ts);
     } else {
       std::lock_guard<std::mutex> g(late_mu);
@@ -3836,7 +3943,18 @@ static int decode_to_host_locked(ctcd_decoder *d, const float *probs, const int3
     const int *lt = late.data();
     const int32_t *ph = fh.data(), *pe = fe.data();
     const uint32_t *pl = fl.data();
-    d->workers->run((int)late.size(), [=](int i) { ctcbeam::expand_item_host(ph, pe, pl, lt[i], beam, T, out_tok, out_ts); });
+    const unsigned long long fetched = std::min<unsigned long long>(nlab, dev_labels);
+    if (n_best)
+      d->workers->run((int)late.size(), [=, &bad_item](int i) {
+        if (ctcnbest::expand_item_nbest_host(ph, pe, pl, fetched, lt[i], beam, T, n_best, out_tok, out_ts, rok + (size_t)lt[i] * n_best)) bad_item = lt[i];
+      });
+    else
+      d->workers->run((int)late.size(), [=](int i) { ctcbeam::expand_item_host(ph, pe, pl, lt[i], beam, T, out_tok, out_ts); });
+  }
+  if (n_best) {
+    for (size_t i = 0; i < row_ok.size(); ++i)
+      if (!row_ok[i]) { out_sc[i] = 0.0f; out_len[i] = 0; }
+    if (bad_item >= 0) return fail(CTCD_EINTERNAL, "malformed compact record for item " + std::to_string(bad_item.load()));
   }
   return CTCD_OK;
 }

@@ -491,6 +491,38 @@ int ctcd_remap_compact(ctcd_decoder *dec, const int32_t *c_hdr, const int32_t *c
 int ctcd_remap_timesteps_host(int32_t *out_timesteps, const int32_t *out_lens, const int32_t *kept, const int32_t *kept_lens, int B,
                               int K, int T, int num_threads);
 
+/* ---- n-best results (no reference counterpart): rows 0 .. n-1 of every item alone.  The one-shot entry points above return all
+ * `beam` rows -- two padded [B, beam, T] tensors -- and almost every caller reads row 0 or a handful.  With 1 <= n_best <= beam:
+ *   out_tokens, out_timesteps int32 [B][n_best][T]     out_scores float [B][n_best]     out_lens int32 [B][n_best]
+ * equal to rows [:, :n_best] of the full call's tensors, bit for bit, and defined everywhere: label positions at or beyond a
+ * row's length are 0; a row at or beyond the item's result count has length 0, score 0 and zero labels.  n_results (optional)
+ * receives every item's FULL result count.  n_best outside [1, beam] is CTCD_EINVAL; nothing is launched.
+ *
+ * ctcd_expand_compact_nbest: compact records (c_hdr / c_ent of stride `beam` / c_labels, n_labels = the words c_labels holds) ->
+ * the [B, n_best, T] pair.  All device memory, asynchronous on `stream`; beam <= 4096 as for ctcd_expand_compact, T <= 65536.
+ * Every record index is checked before it is followed -- the item's range of c_hdr against n_labels, an entry's labels against the
+ * item's range, its row against beam, its lengths against T and its trie predecessor.  A malformed record zeroes the rows that
+ * would have drawn labels from it and RAISES the item's word of `status` (B device words the caller has zeroed, or NULL) to
+ * CTCD_NBEST_BAD_RECORD; words of well-formed items are not written.
+ * ctcd_beam_decode_nbest: ctcd_beam_decode / ctcd_beam_decode_lm (scorer may be NULL) with the four [B, n_best, ...] DEVICE tensors
+ * out; asynchronous on `stream`, nothing is read back in between.  The decode writes compact records into decoder-owned scratch
+ * and the n-best expansion follows on the same stream; a malformed record raises the item's decode status word
+ * (ctcd_check_status).  The scratch belongs to the decoder's next call: queue that call on the same stream, or wait.
+ * ctcd_beam_decode_to_host_nbest: ctcd_beam_decode_to_host with [B, n_best, ...] HOST tensors: the records cross PCIe compact and
+ * are mirrored as there, the host threads expand the rows below n_best alone, and their number follows B x n_best x T.
+ * Where the compact form is not to be had -- T > 65536, T == 0, a callback scorer -- the call decodes in full on the device and
+ * delivers rows [:, :n_best] (on the host route only those cross PCIe): whatever the full call decodes, the n-best call decodes. */
+#define CTCD_NBEST_BAD_RECORD 7
+int ctcd_expand_compact_nbest(ctcd_decoder *dec, const int32_t *c_hdr, const int32_t *c_ent, const uint32_t *c_labels, long long n_labels,
+                              int B, int beam, int T, int n_best, int32_t *out_tokens, int32_t *out_timesteps, int32_t *status, void *stream);
+int ctcd_beam_decode_nbest(ctcd_decoder *dec, const float *probs, const int32_t *seq_lens, int B, int T, int V, int beam, int num_processes,
+                           double cutoff_prob, int cutoff_top_n, int blank_id, int log_input, ctcd_scorer *scorer, int n_best,
+                           int32_t *out_tokens, int32_t *out_timesteps, float *out_scores, int32_t *out_lens, int32_t *n_results, void *stream);
+int ctcd_beam_decode_to_host_nbest(ctcd_decoder *dec, const float *probs, const int32_t *seq_lens, int probs_on_device, int B, int T, int V,
+                                   int beam, int num_processes, double cutoff_prob, int cutoff_top_n, int blank_id, int log_input,
+                                   ctcd_scorer *scorer, int n_best, int32_t *out_tokens, int32_t *out_timesteps, float *out_scores,
+                                   int32_t *out_lens, int32_t *n_results, void *stream);
+
 /* Tuning / introspection. */
 int ctcd_set_threads(ctcd_decoder *dec, int threads_per_workgroup); /* 0 = automatic (default); else a power of two in [64, 1024] */
 /* Two workgroups per CU.  The fixed-layout class (beam <= 128, <= 32 labels) has a second build of its kernel that fits
