@@ -377,7 +377,7 @@ class CTCBeamDecoder(object):
         search, the frames whose blank posterior is GREATER than the threshold, decodes the kept frames, and reports time steps
         as original frame numbers (include/ctcdecode_amd.h "Blank-frame filter").  The outputs keep their [B, K, T] shapes.
         The results are those of the reference on the kept frames -- not those of the full decode: a repeated label whose
-        separating blank frames are all skipped collapses.  ``OnlineCTCBeamDecoder`` does not have it.
+        separating blank frames are all skipped collapses.  ``OnlineCTCBeamDecoder`` has it as ``set_blank_skip(thr)``.
     """
 
     def __init__(self, labels, model_path=None, alpha=0, beta=0, cutoff_top_n=40, cutoff_prob=1.0, beam_width=100,
@@ -1014,10 +1014,24 @@ class DecodePipeline(object):
 class OnlineCTCBeamDecoder(object):
     """Streaming drop-in for ctcdecode/__init__.py:143-250 (no language model): feed an utterance chunk by chunk through a
     ``DecoderState``; results are produced for the items whose ``is_eos_s`` entry is True.  The beam and node pool of
-    every stream stay in HBM between calls; ``timesteps`` count frames from the beginning of the stream."""
+    every stream stay in HBM between calls; ``timesteps`` count frames from the beginning of the stream.
+
+    ``set_blank_skip(thr)`` (extension; off until it is called, and then the streaming path is exactly what it is without it; the
+    constructor keeps the reference's parameters and does not take the setting): a threshold in (0, 1], as ``CTCBeamDecoder``'s
+    ``blank_skip``: every chunk drops, on the device and before the beam search, the frames whose blank posterior is
+    GREATER than the threshold.  A stream decodes the kept frames alone and reports every time step -- at its end, from ``peek`` and
+    from ``commit`` -- as the kept frame's index among all frames it has been fed, so that, however the frames are cut into chunks,
+    it returns what ``CTCBeamDecoder(blank_skip=thr)`` returns for the concatenation, bit for bit.  ``DecoderState.frames`` counts
+    the frames decoded (the kept ones), ``DecoderState.frames_seen`` the frames fed.  The node pools are sized on the host from the
+    chunk lengths, so a filtered ``decode`` call WAITS on the current stream for the kept counts of its chunk before it launches the
+    decode: one small read per call; ``check=False`` still skips the wait for the status words behind it.  A stream adopts the filter
+    at its first chunk; ``save`` of a filtered stream and ``restore`` on a filtering decoder raise ``NotImplementedError``
+    (include/ctcdecode_amd.h "Blank-frame filter of live streams")."""
 
     def __init__(self, labels, model_path=None, alpha=0, beta=0, cutoff_top_n=40, cutoff_prob=1.0, beam_width=100,
                  num_processes=4, blank_id=0, log_probs_input=False, device=None, logits_input=False, scorer=None, compact_pool_above=None):
+        self._blank_skip = None  # set_blank_skip
+        self._filtered_once = False  # a chunk call has gone through the filter since (last_blank_skip)
         self._cutoff_top_n = cutoff_top_n
         self._beam_width = beam_width
         self._scorer = None
@@ -1082,13 +1096,38 @@ class OnlineCTCBeamDecoder(object):
         """As CTCBeamDecoder.last_scorer_pairs."""
         return _last_scorer_pairs(self._handle)
 
+    def set_blank_skip(self, thr):
+        """The blank-frame filter of live streams (see the class): ``thr`` a threshold in (0, 1], checked as ``CTCBeamDecoder``'s
+        ``blank_skip`` is, or None: off.  Call it before the decoder's streams are created and fed: a stream adopts the setting at its
+        first chunk, and a stream that has frames under the other setting is refused (``ValueError``) and left unchanged.  The decoder
+        does not know its live streams, so nothing stops a change while filtered streams are live: they are then refused by every call
+        until the setting they adopted is back."""
+        thr = _blank_skip_threshold(thr)
+        if thr is None:
+            _native.check(_native.lib.ctcd_set_stream_blank_skip(self._handle, 0, 0.0, 0.0))
+        else:  # (the two float32 bounds of CTCBeamDecoder._skip_rows: probabilities | log-probabilities and logits)
+            _native.check(_native.lib.ctcd_set_stream_blank_skip(self._handle, 1, _f32(thr), _f32(math.log(thr))))
+        self._blank_skip = thr
+        self._filtered_once = False
+
+    def last_blank_skip(self):
+        """As CTCBeamDecoder.last_blank_skip: (frames considered, frames kept) of the last chunk call's filter, or None if the filter
+        is off or no call has filtered yet."""
+        if self._blank_skip is None or not self._filtered_once:
+            return None
+        considered, kept = ctypes.c_longlong(0), ctypes.c_longlong(0)
+        _native.check(_native.lib.ctcd_last_stream_blank_skip(self._handle, ctypes.byref(considered), ctypes.byref(kept)))
+        return int(considered.value), int(kept.value)
+
     def decode(self, probs, states, is_eos_s, seq_lens=None, check=True):
         """Same contract as ctcdecode/__init__.py:189-238: returns CPU tensors (beam_results[B, R, L], beam_scores[B, K],
         timesteps[B, R, L], out_lens[B, K]) with R = most results of any item that ended (0 if none), L = longest beam.
 
         ``check=False`` (extension): a call in which no stream ends returns as soon as the chunk's kernel is queued on the
         current stream instead of waiting for its status words -- a serving loop feeds chunk after chunk without a host
-        synchronisation in between; a failure surfaces at the next checked call (every call that ends a stream is one)."""
+        synchronisation in between; a failure surfaces at the next checked call (every call that ends a stream is one).
+        After ``set_blank_skip`` every call -- ``check=False`` too -- waits on the current stream for the kept counts of its chunk before
+        it launches the decode (the node pools are sized on the host); ``check=False`` then skips only the wait for the status words."""
         if probs.dim() != 3:
             raise ValueError("probs must be [batch, time, labels]")
         B, T, V = probs.shape
@@ -1119,7 +1158,10 @@ class OnlineCTCBeamDecoder(object):
                 if is_eos_s[b]:
                     ln = T if lens_cpu is None else max(0, min(int(lens_cpu[b]), T))
                     out_T = max(out_T, int(_native.lib.ctcd_stream_frames(ptrs[b])) + ln)
-        if any_eos and not (self._scorer is not None and isinstance(self._scorer, CallbackScorer)) and out_T <= 65536 and V <= 65535:
+        self._filtered_once = self._blank_skip is not None
+        # (with blank_skip, compact records would have to hold indices among the frames SEEN in their 16 bits: the native bound)
+        compact_ok = self._blank_skip is None or all(int(_native.lib.ctcd_stream_frames_seen(ptrs[b])) + T <= 65536 for b in range(B))
+        if any_eos and not (self._scorer is not None and isinstance(self._scorer, CallbackScorer)) and out_T <= 65536 and V <= 65535 and compact_ok:
             # streams end: their results leave the GPU as compact records and are expanded on the host, straight into tensors of the
             # reference's sizes (binding.cpp:186-205) -- the allocator below is called once the kernel has run and R, L are known
             made = {}
@@ -1307,6 +1349,8 @@ class OnlineCTCBeamDecoder(object):
             return []
         if self._scorer is not None and isinstance(self._scorer, CallbackScorer):
             raise NotImplementedError("ctcdecode_amd: images of streams behind a callback scorer")
+        if self._blank_skip is not None:
+            raise NotImplementedError("ctcdecode_amd: images of streams that decode behind blank_skip (an image does not hold the frame map)")
         ptrs = (ctypes.c_void_p * B)(*[st._ptr(self) for st in states])
         sizes = (ctypes.c_ulonglong * B)()
         made = {}
@@ -1346,6 +1390,8 @@ class OnlineCTCBeamDecoder(object):
             return []
         if self._scorer is not None and isinstance(self._scorer, CallbackScorer):
             raise NotImplementedError("ctcdecode_amd: images of streams behind a callback scorer")
+        if self._blank_skip is not None:
+            raise NotImplementedError("ctcdecode_amd: restore on a decoder with blank_skip (an image does not hold the frame map)")
         keep = []
         for b, blob in enumerate(blobs):
             if isinstance(blob, torch.Tensor):
@@ -1438,6 +1484,12 @@ class DecoderState(object):
     def frames(self):
         """Frames the stream has been fed so far."""
         return int(_native.lib.ctcd_stream_frames(self.state))
+
+    @property
+    def frames_seen(self):
+        """Frames the stream has been fed so far.  Behind ``OnlineCTCBeamDecoder.set_blank_skip`` ``frames`` counts the frames decoded
+        -- the kept ones -- and this the frames the filter has looked at; elsewhere the two are equal."""
+        return int(_native.lib.ctcd_stream_frames_seen(self.state))
 
     @property
     def nbytes(self):

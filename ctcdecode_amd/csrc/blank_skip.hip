@@ -123,6 +123,15 @@ hipError_t launch_gather(const void *in, void *out, const int32_t *kept, const i
 }
 
 }  // namespace
+
+// the gather on its own, for the filter of live streams (stream_blank_skip.h): `kept` / `kept_lens` are a chunk scan's
+int launch_blank_gather(const void *in, void *out, const int32_t *kept, const int32_t *kept_lens, int B, int T, int V, int dtype, void *stream) {
+  const size_t eb = elem_bytes(dtype), row_bytes = (size_t)V * eb;
+  hipStream_t s = (hipStream_t)stream;
+  if (gather_vec16(row_bytes, (uintptr_t)in, (uintptr_t)out)) return (int)launch_gather<u32x4>(in, out, kept, kept_lens, B, T, row_bytes, s);
+  if (eb == 4) return (int)launch_gather<uint32_t>(in, out, kept, kept_lens, B, T, row_bytes, s);
+  return (int)launch_gather<uint16_t>(in, out, kept, kept_lens, B, T, row_bytes, s);
+}
 }  // namespace ctcskip
 
 using namespace ctcskip;

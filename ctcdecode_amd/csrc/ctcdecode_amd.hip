@@ -34,6 +34,7 @@
 #include "stream_commit.h"
 #include "stream_snapshot.h"
 #include "blank_skip.h"
+#include "stream_blank_skip.h"
 #include "nbest.h"
 
 namespace {
@@ -1397,6 +1398,21 @@ struct ctcd_decoder {
   char *h_cp = nullptr;
   size_t h_cp_cap = 0;
   long long compact_min_nodes = 0;    // ctcd_set_stream_compaction: 0 = a stream that outgrows its pool doubles it, as ever
+  // ctcd_set_stream_blank_skip (stream_blank_skip.h): the filter in front of every chunk of this decoder's streams.  sk_rows / sk_kept /
+  // sk_lsm: the chunk's kept rows, their chunk-local indices and -- raw logits -- the float32 log-softmax rows the scan reads.  h_sk: one
+  // page-locked region both sides read and write in place, [scan table | chunk lengths | kept counts] (a filtered chunk call waits for
+  // the counts before it launches its decode, so the region is free when the call returns) and, behind them, the remap table of the
+  // last call that reported time steps: ev_sk_tab is recorded behind that call's remap kernel and waited for before the table changes.
+  bool sk_on = false;
+  float sk_cmp_prob = 0.f, sk_cmp_log = 0.f;
+  Buf sk_rows, sk_kept, sk_lsm;
+  char *h_sk = nullptr;
+  size_t h_sk_items = 0;
+  hipEvent_t ev_sk_tab = nullptr, ev_sk[4] = {nullptr, nullptr, nullptr, nullptr};  // ev_sk: filter start | end, remap start | end (ctcd_set_timing)
+  bool sk_tab_busy = false, sk_timed = false, sk_remap_timed = false;
+  float sk_wait_ms = 0.f;
+  long long sk_last[2] = {0, 0};      // frames considered | kept by the last filtered chunk call (ctcd_last_stream_blank_skip)
+  std::mutex mu_skip;                 // a filtered streaming call holds it from its scan to its remap
   std::mutex mu;
   std::mutex mu_host;  // the host-tensor entry points: compact buffers, page-locked staging and the worker threads are per decoder
 };
@@ -1438,6 +1454,13 @@ struct ctcd_stream {
   long long base_nodes = 1, base_frames = 0;
   long long hint_frames = 0;  // the capacity the stream was created with: a compacted stream does not shrink below it
   long long committed = 0;    // ctcd_stream_commit (stream_commit.h): labels handed out so far -- everything the stream reports counts from there
+  // the blank-frame filter of live streams (stream_blank_skip.h): `frames` counts the frames decoded, the kept ones; `seen` the frames
+  // fed.  map[i] = index among the seen frames of the i-th kept one, i < frames: an allocation of its own (compaction and doubling move
+  // the block), grown by doubling, never shrunk, freed with the stream.  filtered: the stream took its first chunk through the filter.
+  bool filtered = false;
+  long long seen = 0;
+  int32_t *map = nullptr;
+  long long map_cap = 0;
 };
 
 // The external scorer (ctcdecode/src/scorer.h:41-110, created by paddle_get_scorer, binding.cpp:143-150): built on the host
@@ -1570,6 +1593,7 @@ struct StreamCall {          // extra arguments of a streaming decode (lens: the
   const int32_t *row_lens = nullptr;  // device, [B]: frame_off + lens = the rows the pre-passes (log conversion, pruning) cover
   const char *live = nullptr;         // the scorer's page-locked block as the device sees it (ctcd_scorer::d_live): the launch waits for its answers
   bool one_shot = false;              // the launches of a one-shot decode through a callback scorer: they follow ctcd_set_launch_order
+  int in_dtype = -1;                  // >= 0: the element type of `probs` for this call, whatever ctcd_set_input_dtype says (a filtered chunk's rows)
 };
 
 std::atomic<unsigned long long> g_stream_call_id{0};
@@ -1647,6 +1671,10 @@ void ctcd_destroy(ctcd_decoder *d) {
   d->peek_args.release(); d->peek_status.release();
   d->cp_scratch.release();
   if (d->h_cp) (void)hipHostFree(d->h_cp);
+  d->sk_rows.release(); d->sk_kept.release(); d->sk_lsm.release();
+  if (d->h_sk) (void)hipHostFree(d->h_sk);
+  if (d->ev_sk_tab) (void)hipEventDestroy(d->ev_sk_tab);
+  for (int i = 0; i < 4; ++i) if (d->ev_sk[i]) (void)hipEventDestroy(d->ev_sk[i]);
   if (d->copy_stream) (void)hipStreamDestroy(d->copy_stream);
   if (d->ev_in) (void)hipEventDestroy(d->ev_in);
   if (d->ev_order) (void)hipEventDestroy(d->ev_order);
@@ -1953,7 +1981,7 @@ static int decode_common(ctcd_decoder *d, const float *probs, const int32_t *seq
   const int32_t *pre_lens = (sc && sc->row_lens) ? sc->row_lens : seq_lens;
   // half rows (ctcd_set_input_dtype): the pre-pass kernels read them; `probs` keeps pointing at the caller's rows until a pass has
   // written float32 rows into the workspace (dt = kInF32 from there on).  The decode kernels themselves only ever read float32.
-  int dt = d->in_dtype;
+  int dt = (sc && sc->in_dtype >= 0) ? sc->in_dtype : d->in_dtype;
   d->last_in_dtype = dt;
   if (dt != CTCD_DTYPE_F32 && scorer && log_input != 2 && T > 0) {
     // the LM tier reads the blank's value from the caller's rows (KernelArgs::raw): one widening pass into the workspace, then the
@@ -2449,7 +2477,7 @@ long long ctcd_scorer_callback_batches(const ctcd_scorer *s) { return s && s->cb
 static int cb_rounds(ctcd_decoder *d, ctcd_stream **states, const unsigned char *is_eos, const int32_t *lens, const float *probs, int B, int T, int V,
                      int beam, double cutoff_prob, int cutoff_top_n, int blank_id, int log_input, ctcd_scorer *scorer, int32_t *out_tok,
                      int32_t *out_ts, float *out_sc, int32_t *out_len, int32_t *n_results, int out_T, void *stream_, const CompactOut *co = nullptr,
-                     bool one_shot = false) {
+                     bool one_shot = false, int in_dtype = -1) {
   // (the callback runs under this lock: a callback that decodes with the same scorer deadlocks -- include/ctcdecode_amd.h)
   std::lock_guard<std::mutex> cache_lock(scorer->cb_mu);
   hipStream_t stream = (hipStream_t)stream_;
@@ -2521,6 +2549,7 @@ static int cb_rounds(ctcd_decoder *d, ctcd_stream **states, const unsigned char 
     sc.frames_done = d_done;
     sc.row_lens = d_rows;
     sc.one_shot = one_shot;
+    sc.in_dtype = in_dtype;
     volatile unsigned *h_len = (volatile unsigned *)scorer->h_live;
     volatile int32_t *h_done = (volatile int32_t *)(scorer->h_live + kLiveOffDone);
     volatile uint32_t *h_miss = (volatile uint32_t *)(scorer->h_live + kLiveOffMiss);  // (four words per pair: ctclm::MissEntry)
@@ -2795,6 +2824,11 @@ int ctcd_stream_create(ctcd_decoder *d, ctcd_stream **out, int V, int beam, int 
   e = hipMemset(st->block, 0, stream_pool_offset(beam));  // frames == 0: the first call initialises the beam
   if (e == hipSuccess) e = hipMemset(st->block + stream_thi_offset(st->cap_frames, beam), 0, stream_nodes(st->cap_frames, beam) * sizeof(int));
   if (e != hipSuccess) { (void)hipFree(st->block); delete st; return fail(CTCD_EHIP, std::string("hipMemset: ") + hipGetErrorString(e)); }
+  if (d->sk_on) {  // the blank-frame filter of live streams: the frame map is made with the stream, with room for the frames its pool takes
+    st->map_cap = ctcsskip::map_grown_cap(0, st->cap_frames);
+    e = hipMalloc((void **)&st->map, (size_t)st->map_cap * 4);
+    if (e != hipSuccess) { (void)hipFree(st->block); delete st; return fail(CTCD_EHIP, std::string("hipMalloc: ") + hipGetErrorString(e)); }
+  }
   *out = st;
   return CTCD_OK;
 }
@@ -2803,10 +2837,272 @@ void ctcd_stream_destroy(ctcd_decoder *d, ctcd_stream *st) {
   if (!st) return;
   DeviceGuard guard_(st->device);
   if (st->block) (void)hipFree(st->block);
+  if (st->map) (void)hipFree(st->map);
   delete st;
 }
 
 long long ctcd_stream_frames(const ctcd_stream *st) { return st ? st->frames : -1; }
+
+// ---- the blank-frame filter of live streams (stream_blank_skip.h) -------------------------------------------------------------------
+int ctcd_set_stream_blank_skip(ctcd_decoder *d, int on, float cmp_prob, float cmp_log) {
+  if (!d) return fail(CTCD_EINVAL, "decoder == NULL");
+  if (on && (cmp_prob != cmp_prob || cmp_log != cmp_log)) return fail(CTCD_EINVAL, "ctcd_set_stream_blank_skip: the bounds are float32 numbers, not NaN");
+  std::lock_guard<std::mutex> lock(d->mu_skip);
+  d->sk_on = on != 0;
+  d->sk_cmp_prob = cmp_prob;
+  d->sk_cmp_log = cmp_log;
+  return CTCD_OK;
+}
+
+long long ctcd_stream_frames_seen(const ctcd_stream *st) { return st ? (st->filtered ? st->seen : st->frames) : -1; }
+long long ctcd_stream_map_bytes(const ctcd_stream *st) { return st ? st->map_cap * 4 : -1; }
+
+int ctcd_last_stream_blank_skip(ctcd_decoder *d, long long *considered, long long *kept) {
+  if (!d || !considered || !kept) return fail(CTCD_EINVAL, "ctcd_last_stream_blank_skip: null argument");
+  std::lock_guard<std::mutex> lock(d->mu_skip);
+  *considered = d->sk_last[0];
+  *kept = d->sk_last[1];
+  return CTCD_OK;
+}
+
+int ctcd_last_stream_blank_skip_ms(ctcd_decoder *d, float *filter_ms, float *wait_ms, float *remap_ms) {
+  if (!d || !filter_ms || !wait_ms || !remap_ms) return fail(CTCD_EINVAL, "ctcd_last_stream_blank_skip_ms: null argument");
+  std::lock_guard<std::mutex> lock(d->mu_skip);
+  if (!d->ev_sk[0]) return fail(CTCD_EINVAL, "timing not enabled");
+  CTC_ON_DEVICE(d->device);
+  *filter_ms = *remap_ms = 0.f;
+  *wait_ms = d->sk_wait_ms;
+  if (d->sk_timed) {
+    HIP_TRY(hipEventSynchronize(d->ev_sk[1]));
+    HIP_TRY(hipEventElapsedTime(filter_ms, d->ev_sk[0], d->ev_sk[1]));
+  }
+  if (d->sk_remap_timed) {
+    HIP_TRY(hipEventSynchronize(d->ev_sk[3]));
+    HIP_TRY(hipEventElapsedTime(remap_ms, d->ev_sk[2], d->ev_sk[3]));
+  }
+  return CTCD_OK;
+}
+
+namespace {
+
+// a stream adopts the filter at its first chunk: one that already has frames under the other setting is refused
+int sskip_check_setting(const ctcd_decoder *d, ctcd_stream *const *states, int B, const char *who) {
+  for (int b = 0; b < B; ++b) {
+    const ctcd_stream *st = states[b];
+    if (!st) return fail(CTCD_EINVAL, "stream state does not match the decoder configuration");
+    if (d->sk_on ? (!st->filtered && st->frames > 0) : (st->filtered && st->seen > 0))
+      return fail(CTCD_EINVAL, std::string(who) + ": item " + std::to_string(b) +
+                                   (d->sk_on ? " has frames it took without the blank-frame filter this decoder has on"
+                                             : " has frames it took through the blank-frame filter this decoder has off"));
+  }
+  return CTCD_OK;
+}
+
+// offsets of the arrays in the decoder's page-locked region: scan table | chunk lengths | kept counts | remap table.  Always taken for
+// the region's capacity (d->h_sk_items), never for a call's batch: the remap table lies where no later call's scan arguments reach,
+// whatever its batch size -- a remap kernel may still be reading it when the next chunk call fills in its own arguments.
+struct SkRegion {
+  size_t o_len, o_cnt, o_rtab, need;
+  explicit SkRegion(size_t n) {
+    o_len = n * sizeof(ctcsskip::StreamSkipItem);
+    o_cnt = o_len + n * 4;
+    o_rtab = (o_cnt + n * 4 + 15) & ~(size_t)15;
+    need = o_rtab + n * sizeof(ctcsskip::StreamRemapItem);
+  }
+};
+
+// (d->mu_skip held) the region with room for B items; a remap kernel that still reads the last table is waited for before it moves
+int sskip_region(ctcd_decoder *d, int B, char **hb, char **db) {
+  if (d->h_sk_items < (size_t)B) {
+    if (d->sk_tab_busy) HIP_TRY(hipEventSynchronize(d->ev_sk_tab));
+    d->sk_tab_busy = false;
+    if (d->h_sk) (void)hipHostFree(d->h_sk);
+    d->h_sk = nullptr;
+    d->h_sk_items = 0;
+    const size_t items = std::max<size_t>(2 * (size_t)B, 64);
+    HIP_TRY(hipHostMalloc((void **)&d->h_sk, SkRegion(items).need, hipHostMallocMapped | hipHostMallocCoherent));
+    d->h_sk_items = items;
+  }
+  if (!d->ev_sk_tab) HIP_TRY(hipEventCreateWithFlags(&d->ev_sk_tab, hipEventDisableTiming));
+  *hb = d->h_sk;
+  HIP_TRY(hipHostGetDevicePointer((void **)db, *hb, 0));
+  return CTCD_OK;
+}
+
+// (d->mu_skip held) the remap table of a call, host and device address; the kernel that read the last one has finished
+int sskip_remap_table(ctcd_decoder *d, int B, ctcsskip::StreamRemapItem **h_tab, const ctcsskip::StreamRemapItem **d_tab) {
+  char *hb = nullptr, *db = nullptr;
+  if (const int rc = sskip_region(d, B, &hb, &db)) return rc;
+  if (d->sk_tab_busy) HIP_TRY(hipEventSynchronize(d->ev_sk_tab));
+  d->sk_tab_busy = false;
+  const SkRegion r(d->h_sk_items);
+  *h_tab = (ctcsskip::StreamRemapItem *)(hb + r.o_rtab);
+  *d_tab = (const ctcsskip::StreamRemapItem *)(db + r.o_rtab);
+  return CTCD_OK;
+}
+int sskip_table_used(ctcd_decoder *d, hipStream_t stream) {
+  HIP_TRY(hipEventRecord(d->ev_sk_tab, stream));
+  d->sk_tab_busy = true;
+  return CTCD_OK;
+}
+int sskip_timing_events(ctcd_decoder *d) {
+  for (int i = 0; i < 4; ++i)
+    if (!d->ev_sk[i]) HIP_TRY(hipEventCreate(&d->ev_sk[i]));
+  return CTCD_OK;
+}
+// (d->mu_skip held) the row remap of a call's results, queued behind them: every stream's map and the frames it has decoded now
+int sskip_remap_rows(ctcd_decoder *d, ctcd_stream **states, int B, int32_t *ts, const int32_t *lens, const int32_t *since, int rows_per_item,
+                     long long row_stride, hipStream_t stream) {
+  ctcsskip::StreamRemapItem *h_tab = nullptr;
+  const ctcsskip::StreamRemapItem *d_tab = nullptr;
+  if (const int rc = sskip_remap_table(d, B, &h_tab, &d_tab)) return rc;
+  for (int b = 0; b < B; ++b) h_tab[b] = ctcsskip::StreamRemapItem{states[b]->map, nullptr, (int32_t)states[b]->frames, 0};
+  d->sk_remap_timed = false;
+  if (d->timing) {
+    if (const int rc = sskip_timing_events(d)) return rc;
+    HIP_TRY(hipEventRecord(d->ev_sk[2], stream));
+  }
+  const int e = ctcsskip::launch_remap_rows(ts, lens, since, d_tab, B, rows_per_item, row_stride, (void *)stream);
+  if (e != (int)hipSuccess) return fail(CTCD_EHIP, std::string("ctc_stream_remap_rows_kernel: ") + hipGetErrorString((hipError_t)e));
+  if (d->timing) {
+    HIP_TRY(hipEventRecord(d->ev_sk[3], stream));
+    d->sk_remap_timed = true;
+  }
+  return sskip_table_used(d, stream);
+}
+
+// what the filter hands a chunk call's decode: the kept rows, their counts as the chunk lengths, the log mode and element type to read them in
+struct SkChunk {
+  std::vector<int32_t> lens, kept;
+  const float *rows = nullptr;
+  int log_input = 0, dtype = CTCD_DTYPE_F32;
+  long long considered = 0;
+};
+
+// (d->mu_skip held, the decoder's device current) The filter of one chunk call: every argument is checked before the device is touched;
+// maps that lack room for the chunk grow; log-softmax (raw logits) -> scan -> gather are queued on `stream`, and the call waits for the
+// B kept counts: stream_prepare sizes the node pools from host lengths.  No stream's frames / seen / map length change here.
+int sskip_front(ctcd_decoder *d, ctcd_stream **states, const float *probs, const int32_t *seq_lens_host, int B, int T, int V, int blank_id,
+                int log_input, hipStream_t stream, SkChunk &ck) {
+  namespace ss = ctcsskip;
+  if (V <= 0 || blank_id < 0 || blank_id >= V) return fail(CTCD_EINVAL, "blank_id must index the vocabulary");
+  if (log_input < 0 || log_input > 2) return fail(CTCD_EINVAL, "log_input is 0, 1 or 2");
+  const unsigned long long call_id = ++g_stream_call_id;
+  ck.lens.assign((size_t)B, 0);
+  ck.kept.assign((size_t)B, 0);
+  ck.considered = 0;
+  for (int b = 0; b < B; ++b) {
+    ctcd_stream *st = states[b];
+    if (st->device != d->device || st->V != V) return fail(CTCD_EINVAL, "stream state does not match the decoder configuration");
+    if (st->seen_in_call == call_id) return fail(CTCD_EINVAL, "the same stream state appears twice in one batch");
+    st->seen_in_call = call_id;
+    if (st->seen + T > 0x7fffffffLL) return fail(CTCD_EUNSUPPORTED, "stream too long: the frame map holds 32-bit frame numbers");
+    const int len = seq_lens_host ? seq_lens_host[b] : T;
+    ck.lens[b] = len < 0 ? 0 : (len > T ? T : len);  // binding.cpp:171
+    ck.considered += ck.lens[b];
+  }
+  ck.rows = probs;
+  ck.log_input = log_input;
+  ck.dtype = d->in_dtype;
+  d->sk_timed = false;
+  d->sk_remap_timed = false;
+  d->sk_wait_ms = 0.f;
+  if (ck.considered == 0) return CTCD_OK;  // no frame to look at: the decode sees B empty chunks
+  if (!probs) return fail(CTCD_EINVAL, "null tensor");
+  for (int b = 0; b < B; ++b) {  // the maps: room for every frame of the chunk
+    ctcd_stream *st = states[b];
+    const long long need = ss::map_need(st->frames, ck.lens[b]);
+    if (need <= st->map_cap) continue;
+    const long long cap = ss::map_grown_cap(st->map_cap, need);
+    int32_t *nm = nullptr;
+    HIP_TRY(hipMalloc((void **)&nm, (size_t)cap * 4));
+    if (st->map && st->frames > 0) {
+      const hipError_t ce = hipMemcpyAsync(nm, st->map, (size_t)st->frames * 4, hipMemcpyDeviceToDevice, stream);
+      if (ce != hipSuccess) { (void)hipFree(nm); return fail(CTCD_EHIP, std::string("hipMemcpyAsync: ") + hipGetErrorString(ce)); }
+    }
+    if (st->map) {  // (a remap queued on another stream may still read the old map: hipFree waits for the device)
+      const hipError_t se = hipStreamSynchronize(stream);
+      if (se != hipSuccess) { (void)hipFree(nm); return fail(CTCD_EHIP, std::string("hipStreamSynchronize: ") + hipGetErrorString(se)); }
+      (void)hipFree(st->map);
+    }
+    st->map = nm;
+    st->map_cap = cap;
+  }
+  int rc;
+  char *hb = nullptr, *db = nullptr;
+  if ((rc = sskip_region(d, B, &hb, &db))) return rc;
+  const SkRegion r(d->h_sk_items);
+  ss::StreamSkipItem *h_tab = (ss::StreamSkipItem *)hb;
+  int32_t *h_len = (int32_t *)(hb + r.o_len);
+  volatile int32_t *h_cnt = (volatile int32_t *)(hb + r.o_cnt);
+  for (int b = 0; b < B; ++b) {
+    h_tab[b] = ss::StreamSkipItem{states[b]->map, (int32_t)states[b]->frames, (int32_t)states[b]->seen};
+    h_len[b] = ck.lens[b];
+    h_cnt[b] = -1;  // ("no result": a workgroup that never ran cannot read back as a count)
+  }
+  const int32_t *d_len = (const int32_t *)(db + r.o_len);
+  int32_t *d_cnt = (int32_t *)(db + r.o_cnt);
+  const size_t n = (size_t)B * T * V;
+  if (d->timing) {
+    if ((rc = sskip_timing_events(d))) return rc;
+    HIP_TRY(hipEventRecord(d->ev_sk[0], stream));
+  }
+  const void *rows_in = probs;
+  int dt = d->in_dtype;
+  float cmp = log_input == 0 ? d->sk_cmp_prob : d->sk_cmp_log;
+  if (log_input == 2) {  // raw logits: the float32 log-softmax rows are what the definition compares, and what the decode then reads
+    {
+      std::lock_guard<std::mutex> lock(d->mu);
+      if (!d->tables_ready) {
+        if ((rc = d->tables.ensure(sizeof(ctcmath::Tables)))) return rc;
+        HIP_TRY(hipMemcpy(d->tables.p, ctcmath::host_tables().w, sizeof(ctcmath::Tables), hipMemcpyHostToDevice));
+        d->tables_ready = true;
+      }
+    }
+    if ((rc = d->sk_lsm.ensure(n * 4))) return rc;
+    if ((rc = launch_log_softmax(d, probs, (float *)d->sk_lsm.p, (long long)B * T, d_len, T, V, stream, dt))) return rc;
+    rows_in = d->sk_lsm.p;
+    dt = CTCD_DTYPE_F32;
+    ck.log_input = 1;
+  }
+  if ((rc = d->sk_rows.ensure(n * in_elem_bytes(dt))) || (rc = d->sk_kept.ensure((size_t)B * T * 4))) return rc;
+  int e = ss::launch_chunk_scan(rows_in, d_len, (const ss::StreamSkipItem *)db, B, T, V, blank_id, cmp, dt, (int32_t *)d->sk_kept.p, d_cnt, (void *)stream);
+  if (e != (int)hipSuccess) return fail(CTCD_EHIP, std::string("ctc_stream_scan_kernel: ") + hipGetErrorString((hipError_t)e));
+  e = ctcskip::launch_blank_gather(rows_in, d->sk_rows.p, (const int32_t *)d->sk_kept.p, d_cnt, B, T, V, dt, (void *)stream);
+  if (e != (int)hipSuccess) {
+    (void)hipStreamSynchronize(stream);  // (the scan still writes the region)
+    return fail(CTCD_EHIP, std::string("ctc_blank_gather_kernel: ") + hipGetErrorString((hipError_t)e));
+  }
+  if (d->timing) {
+    HIP_TRY(hipEventRecord(d->ev_sk[1], stream));
+    d->sk_timed = true;
+  }
+  const auto t0 = std::chrono::steady_clock::now();
+  HIP_TRY(hipStreamSynchronize(stream));  // the wait for the kept counts
+  d->sk_wait_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  for (int b = 0; b < B; ++b) {
+    const int k = h_cnt[b];
+    if (k < 0 || k > ck.lens[b]) return fail(CTCD_EINTERNAL, "blank-frame filter: kept count " + std::to_string(k) + " for item " + std::to_string(b));
+    ck.kept[b] = k;
+  }
+  ck.rows = (const float *)d->sk_rows.p;
+  ck.dtype = dt;
+  return CTCD_OK;
+}
+
+// the decode launch was accepted: frames (advanced by the decode), frames seen and the map's used length move together
+void sskip_advance(ctcd_decoder *d, ctcd_stream **states, int B, const SkChunk &ck) {
+  long long kept = 0;
+  for (int b = 0; b < B; ++b) {
+    states[b]->seen += ck.lens[b];
+    states[b]->filtered = true;
+    kept += ck.kept[b];
+  }
+  d->sk_last[0] = ck.considered;
+  d->sk_last[1] = kept;
+}
+
+}  // namespace
 
 // Compacts the node pools of B parked streams of one beam width (stream_compact.h), behind whatever is queued on `stream`:
 // count -> the host sizes the scratch and decides which streams move to a smaller block -> gather -> store.  The caller has checked
@@ -2992,7 +3288,7 @@ int ctcd_stream_compact(ctcd_decoder *d, ctcd_stream **states, int B, int32_t *l
 // to a smaller block -> gather -> store -> the labels come over.  The caller has checked the states.  Synchronous; shares the
 // compaction's scratch and page-locked region.
 static int commit_streams(ctcd_decoder *d, ctcd_stream **sts, int B, ctcd_result_alloc_fn alloc, void *alloc_user, int32_t *counts_out,
-                          int32_t *live_out, int *out_L, hipStream_t stream) {
+                          int32_t *live_out, int *out_L, hipStream_t stream, bool filtered) {
   namespace cc = ctccompact;
   namespace cm = ctccommit;
   std::lock_guard<std::mutex> lock(d->mu);
@@ -3074,6 +3370,19 @@ static int commit_streams(ctcd_decoder *d, ctcd_stream **sts, int B, ctcd_result
     if (e == (int)hipSuccess) e = (int)hipStreamSynchronize(stream);
     if (e != (int)hipSuccess) { drop_moved(); return fail(CTCD_EHIP, std::string("ctc_stream_commit kernels: ") + hipGetErrorString((hipError_t)e)); }
     std::vector<int32_t> lab((size_t)labels);
+    if (labels > 0 && filtered) {
+      // filtered streams (stream_blank_skip.h; the caller holds d->mu_skip): the committed time steps, D words behind every stream's D
+      // tokens, go back through the maps on the device before they come over
+      ctcsskip::StreamRemapItem *h_tab = nullptr;
+      const ctcsskip::StreamRemapItem *d_tab = nullptr;
+      int rc = sskip_remap_table(d, B, &h_tab, &d_tab);
+      if (rc) { drop_moved(); return rc; }
+      for (int b = 0; b < B; ++b)
+        h_tab[b] = ctcsskip::StreamRemapItem{sts[b]->map, l.scratch + h_lab[b] + (h_drop[b] > 0 ? h_drop[b] : 0), (int32_t)sts[b]->frames, 0};
+      e = ctcsskip::launch_remap_rows(nullptr, (const int32_t *)(db + o_drop), nullptr, d_tab, B, 1, L, (void *)stream);
+      if (e == (int)hipSuccess) e = (int)hipStreamSynchronize(stream);
+      if (e != (int)hipSuccess) { drop_moved(); return fail(CTCD_EHIP, std::string("ctc_stream_remap_rows_kernel: ") + hipGetErrorString((hipError_t)e)); }
+    }
     if (labels > 0) {
       const hipError_t ce = hipMemcpy(lab.data(), l.scratch + total, (size_t)labels * 4, hipMemcpyDeviceToHost);
       if (ce != hipSuccess) { drop_moved(); return fail(CTCD_EHIP, std::string("hipMemcpy: ") + hipGetErrorString(ce)); }
@@ -3130,7 +3439,11 @@ int ctcd_stream_commit(ctcd_decoder *d, ctcd_stream **states, int B, ctcd_result
   }
   // (with a scorer the result scores use a prefix's absolute depth -- finish(), lm_final_scores: a re-rooted stream would need a base depth there)
   if (states[0]->scorer) return fail(CTCD_EUNSUPPORTED, "ctcd_stream_commit: streams with a scorer cannot drop their trunk");
-  return commit_streams(d, states, B, alloc, alloc_user, counts_host, live_nodes_host, out_L, (hipStream_t)stream_);
+  if (const int src = sskip_check_setting(d, states, B, "ctcd_stream_commit")) return src;
+  // (the blank-frame filter of live streams: its lock is taken before the decoder's, as a filtered chunk call takes them)
+  std::unique_lock<std::mutex> sk_lock(d->mu_skip, std::defer_lock);
+  if (d->sk_on) sk_lock.lock();
+  return commit_streams(d, states, B, alloc, alloc_user, counts_host, live_nodes_host, out_L, (hipStream_t)stream_, sk_lock.owns_lock());
 }
 
 long long ctcd_stream_committed(const ctcd_stream *st) { return st ? st->committed : -1; }
@@ -3179,6 +3492,9 @@ int ctcd_stream_save(ctcd_decoder *d, ctcd_stream **states, int B, ctcd_bytes_al
   }
   const ctcd_scorer *sc = states[0]->scorer;
   if (sc && sc->cbl) return fail(CTCD_EUNSUPPORTED, "ctcd_stream_save: the states of a stream behind a callback scorer index a per-process cache");
+  for (int b = 0; b < B; ++b)
+    if (states[b]->filtered && states[b]->seen > 0)
+      return fail(CTCD_EUNSUPPORTED, "ctcd_stream_save: item " + std::to_string(b) + " decodes behind the blank-frame filter (an image does not hold its frame map)");
   const int beam = states[0]->beam, lm = sc ? 1 : 0;
   // the image is the layout a compaction leaves
   std::vector<int32_t> live((size_t)B, 0);
@@ -3246,6 +3562,7 @@ int ctcd_stream_restore(ctcd_decoder *d, ctcd_scorer *scorer, const void *const 
     if (!blobs[b] || bytes[b] == 0) return fail(CTCD_EINVAL, "ctcd_stream_restore: item " + std::to_string(b) + " is empty");
   }
   if (scorer && scorer->cbl) return fail(CTCD_EUNSUPPORTED, "ctcd_stream_restore: no image is saved behind a callback scorer");
+  if (d->sk_on) return fail(CTCD_EUNSUPPORTED, "ctcd_stream_restore: this decoder has the blank-frame filter of live streams on (an image holds no frame map)");
   if (scorer && scorer->device != d->device) return fail(CTCD_EINVAL, "the scorer lives on another device than the decoder");
   // every image is checked before anything is allocated or uploaded
   sn::SnapInfo first;
@@ -3364,12 +3681,41 @@ int ctcd_set_stream_compaction(ctcd_decoder *d, long long min_nodes) {
   return CTCD_OK;
 }
 
+static int stream_decode_impl(ctcd_decoder *d, ctcd_stream **states, const unsigned char *is_eos, const float *probs, const int32_t *seq_lens_host, int B,
+                              int T, int V, int beam, double cutoff_prob, int cutoff_top_n, int blank_id, int log_input, int32_t *out_tok,
+                              int32_t *out_ts, float *out_sc, int32_t *out_len, int32_t *n_results, int out_T, void *stream_, int in_dtype = -1);
+
 int ctcd_stream_decode(ctcd_decoder *d, ctcd_stream **states, const unsigned char *is_eos, const float *probs,
                        const int32_t *seq_lens_host, int B, int T, int V, int beam, int /*num_processes*/, double cutoff_prob,
                        int cutoff_top_n, int blank_id, int log_input, int32_t *out_tok, int32_t *out_ts, float *out_sc,
                        int32_t *out_len, int32_t *n_results, int out_T, void *stream_) {
   if (!d || !states || !is_eos || B < 0 || T < 0 || out_T < 0) return fail(CTCD_EINVAL, "bad arguments");
   if (B == 0) return CTCD_OK;
+  int rc;
+  if ((rc = sskip_check_setting(d, states, B, "ctcd_stream_decode"))) return rc;
+  if (!d->sk_on)
+    return stream_decode_impl(d, states, is_eos, probs, seq_lens_host, B, T, V, beam, cutoff_prob, cutoff_top_n, blank_id, log_input, out_tok, out_ts, out_sc,
+                              out_len, n_results, out_T, stream_);
+  // the filter is on: scan and gather, the wait for the kept counts, the decode of the kept rows, the remap of what the call reports
+  CTC_ON_DEVICE(d->device);
+  hipStream_t stream = (hipStream_t)stream_;
+  std::lock_guard<std::mutex> sk_lock(d->mu_skip);
+  SkChunk ck;
+  if ((rc = sskip_front(d, states, probs, seq_lens_host, B, T, V, blank_id, log_input, stream, ck))) return rc;
+  // (the kept rows' element type travels with the call: raw logits are filtered, and decoded, as float32 rows)
+  rc = stream_decode_impl(d, states, is_eos, ck.rows, ck.kept.data(), B, T, V, beam, cutoff_prob, cutoff_top_n, blank_id, ck.log_input, out_tok, out_ts,
+                          out_sc, out_len, n_results, out_T, stream_, ck.dtype);
+  if (rc) return rc;
+  sskip_advance(d, states, B, ck);
+  bool any_eos = false;
+  for (int b = 0; b < B; ++b) any_eos |= is_eos[b] != 0;
+  if (any_eos && out_ts && out_len && out_T > 0) return sskip_remap_rows(d, states, B, out_ts, out_len, nullptr, beam, out_T, stream);
+  return CTCD_OK;
+}
+
+static int stream_decode_impl(ctcd_decoder *d, ctcd_stream **states, const unsigned char *is_eos, const float *probs, const int32_t *seq_lens_host, int B,
+                              int T, int V, int beam, double cutoff_prob, int cutoff_top_n, int blank_id, int log_input, int32_t *out_tok,
+                              int32_t *out_ts, float *out_sc, int32_t *out_len, int32_t *n_results, int out_T, void *stream_, int in_dtype) {
   CTC_ON_DEVICE(d->device);
   hipStream_t stream = (hipStream_t)stream_;
   std::vector<int32_t> lens(B);
@@ -3381,12 +3727,13 @@ int ctcd_stream_decode(ctcd_decoder *d, ctcd_stream **states, const unsigned cha
   // (the chunk lengths travel with the other per-item arguments: decode_common)
   if (states[0]->scorer && states[0]->scorer->cbl) {  // a callback scorer: as many launches as its cache needs
     const int rc = cb_rounds(d, states, is_eos, lens.data(), probs, B, T, V, beam, cutoff_prob, cutoff_top_n, blank_id, log_input, states[0]->scorer, out_tok,
-                             out_ts, out_sc, out_len, n_results, out_T, stream_);
+                             out_ts, out_sc, out_len, n_results, out_T, stream_, nullptr, false, in_dtype);
     if (rc) return rc;
     for (int b = 0; b < B; ++b) states[b]->frames += lens[b];
     return CTCD_OK;
   }
   StreamCall sc{states, is_eos, out_T, lens.data(), any_eos};
+  sc.in_dtype = in_dtype;
   int rc = decode_common(d, probs, nullptr, B, T, V, beam, cutoff_prob, cutoff_top_n, blank_id, log_input, out_tok,
                          out_ts, out_sc, out_len, n_results, stream_, &sc, states[0]->scorer);
   if (rc) return rc;
@@ -3402,6 +3749,10 @@ int ctcd_stream_peek(ctcd_decoder *d, ctcd_stream **states, int B, int n_best, c
   if (B == 0) return CTCD_OK;
   if (!out_sc || !out_len || !n_results || !stable_lens || (L_cap > 0 && (!out_tok || !out_ts))) return fail(CTCD_EINVAL, "null tensor");
   if (n_best < 1) return fail(CTCD_EINVAL, "n_best must be at least 1");
+  if (const int src = sskip_check_setting(d, states, B, "ctcd_stream_peek")) return src;
+  // (the blank-frame filter of live streams: its lock is taken before the decoder's, as a filtered chunk call takes them)
+  std::unique_lock<std::mutex> sk_lock(d->mu_skip, std::defer_lock);
+  if (d->sk_on) sk_lock.lock();
   std::lock_guard<std::mutex> lock(d->mu);
   CTC_ON_DEVICE(d->device);
   hipStream_t stream = (hipStream_t)stream_;
@@ -3467,6 +3818,8 @@ int ctcd_stream_peek(ctcd_decoder *d, ctcd_stream **states, int B, int n_best, c
   if (e != (int)hipSuccess) return fail(CTCD_EHIP, std::string("ctc_stream_peek_kernel: ") + hipGetErrorString((hipError_t)e));
   d->peek_items = B;
   d->peek_stream = stream;
+  // filtered streams report the kept frames' indices among the seen frames: the reported part of every row goes through the maps
+  if (sk_lock.owns_lock() && L_cap > 0) return sskip_remap_rows(d, states, B, out_ts, out_len, l.since, n_best, L_cap, stream);
   return CTCD_OK;
 }
 
@@ -3477,6 +3830,13 @@ int ctcd_stream_peek(ctcd_decoder *d, ctcd_stream **states, int B, int n_best, c
 // every finished stream's records into page-locked memory -- and host threads expand them into the caller's buffers: a tenth of the
 // padded [B, K, out_T] pair crosses PCIe.  out_scores / out_lens [B, beam] and n_results [B] are host pointers too.  Synchronous.
 // A callback scorer decodes launch after launch into padded device tensors (cb_rounds): not through this entry (CTCD_EUNSUPPORTED).
+// (remap_tab, device memory, non-null: the call's streams are filtered -- stream_blank_skip.h; launched(): the decode launch was accepted)
+static int stream_decode_to_host_impl(ctcd_decoder *d, ctcd_stream **states, const unsigned char *is_eos, const float *probs,
+                                      const int32_t *seq_lens_host, int B, int T, int V, int beam, int num_processes, double cutoff_prob,
+                                      int cutoff_top_n, int blank_id, int log_input, ctcd_result_alloc_fn alloc, void *alloc_user,
+                                      float *out_sc, int32_t *out_len, int32_t *n_results, int out_T, int *out_R, int *out_L, void *stream_,
+                                      const ctcsskip::StreamRemapItem *remap_tab, const std::function<void()> &launched = nullptr, int in_dtype = -1);
+
 int ctcd_stream_decode_to_host(ctcd_decoder *d, ctcd_stream **states, const unsigned char *is_eos, const float *probs,
                                const int32_t *seq_lens_host, int B, int T, int V, int beam, int num_processes, double cutoff_prob,
                                int cutoff_top_n, int blank_id, int log_input, ctcd_result_alloc_fn alloc, void *alloc_user,
@@ -3485,6 +3845,37 @@ int ctcd_stream_decode_to_host(ctcd_decoder *d, ctcd_stream **states, const unsi
   if (out_R) *out_R = 0;
   if (out_L) *out_L = 0;
   if (B == 0) return CTCD_OK;
+  int rc;
+  if ((rc = sskip_check_setting(d, states, B, "ctcd_stream_decode_to_host"))) return rc;
+  if (!d->sk_on)
+    return stream_decode_to_host_impl(d, states, is_eos, probs, seq_lens_host, B, T, V, beam, num_processes, cutoff_prob, cutoff_top_n, blank_id, log_input,
+                                      alloc, alloc_user, out_sc, out_len, n_results, out_T, out_R, out_L, stream_, nullptr);
+  // the filter is on.  Compact records hold 16-bit frame numbers, and a filtered stream reports indices among the frames it has SEEN:
+  // this route is taken only while they fit (stream_blank_skip.h compact_route_ok); beyond, the stream ends through ctcd_stream_decode
+  if (states[0]->scorer && states[0]->scorer->cbl) return fail(CTCD_EUNSUPPORTED, "a callback scorer's streams end through ctcd_stream_decode");
+  for (int b = 0; b < B; ++b)
+    if (!ctcsskip::compact_route_ok(states[b]->seen, T))
+      return fail(CTCD_EUNSUPPORTED, "compact results hold 16-bit frame numbers: a filtered stream that has seen more than 65536 frames ends through ctcd_stream_decode");
+  CTC_ON_DEVICE(d->device);
+  hipStream_t stream = (hipStream_t)stream_;
+  std::lock_guard<std::mutex> sk_lock(d->mu_skip);
+  SkChunk ck;
+  if ((rc = sskip_front(d, states, probs, seq_lens_host, B, T, V, blank_id, log_input, stream, ck))) return rc;
+  ctcsskip::StreamRemapItem *h_tab = nullptr;
+  const ctcsskip::StreamRemapItem *d_tab = nullptr;
+  if ((rc = sskip_remap_table(d, B, &h_tab, &d_tab))) return rc;
+  for (int b = 0; b < B; ++b)  // (the frames a stream will have decoded when the remap runs: the guard)
+    h_tab[b] = ctcsskip::StreamRemapItem{states[b]->map, nullptr, (int32_t)(states[b]->frames + ck.kept[b]), 0};
+  return stream_decode_to_host_impl(d, states, is_eos, ck.rows, ck.kept.data(), B, T, V, beam, num_processes, cutoff_prob, cutoff_top_n, blank_id, ck.log_input,
+                                    alloc, alloc_user, out_sc, out_len, n_results, out_T, out_R, out_L, stream_, d_tab, [&] { sskip_advance(d, states, B, ck); },
+                                    ck.dtype);
+}
+
+static int stream_decode_to_host_impl(ctcd_decoder *d, ctcd_stream **states, const unsigned char *is_eos, const float *probs,
+                                      const int32_t *seq_lens_host, int B, int T, int V, int beam, int num_processes, double cutoff_prob,
+                                      int cutoff_top_n, int blank_id, int log_input, ctcd_result_alloc_fn alloc, void *alloc_user,
+                                      float *out_sc, int32_t *out_len, int32_t *n_results, int out_T, int *out_R, int *out_L, void *stream_,
+                                      const ctcsskip::StreamRemapItem *remap_tab, const std::function<void()> &launched, int in_dtype) {
   CTC_ON_DEVICE(d->device);
   hipStream_t stream = (hipStream_t)stream_;
   if (states[0] && states[0]->scorer && states[0]->scorer->cbl) return fail(CTCD_EUNSUPPORTED, "a callback scorer's streams end through ctcd_stream_decode");
@@ -3523,13 +3914,30 @@ int ctcd_stream_decode_to_host(ctcd_decoder *d, ctcd_stream **states, const unsi
   for (int b = 0; b < B; ++b) done[b] = 0;
   std::memset(hs + o_hdr, 0, (size_t)B * 16);  // (streams that do not end write nothing)
   CompactOut co{(int32_t *)d->c_hdr.p, (int32_t *)d->c_ent.p, (uint32_t *)d->c_rag.p, (unsigned *)d->c_cnt.p, (unsigned)cap};
-  co.m_hdr = (int32_t *)(ds + o_hdr); co.m_ent = (int32_t *)(ds + o_ent); co.m_done = (int32_t *)(ds + o_done);
-  co.m_rag = (uint32_t *)(ds + o_lab); co.m_cap = (unsigned)std::min<size_t>(mcap, 0xFFFFFFFFu);
+  if (!remap_tab) {  // (filtered streams: the records are remapped on the device first, and fetched from its buffers below)
+    co.m_hdr = (int32_t *)(ds + o_hdr); co.m_ent = (int32_t *)(ds + o_ent); co.m_done = (int32_t *)(ds + o_done);
+    co.m_rag = (uint32_t *)(ds + o_lab); co.m_cap = (unsigned)std::min<size_t>(mcap, 0xFFFFFFFFu);
+  }
   StreamCall sc{states, is_eos, out_T, lens.data(), any_eos};
+  sc.in_dtype = in_dtype;
   rc = decode_common(d, probs, nullptr, B, T, V, beam, cutoff_prob, cutoff_top_n, blank_id, log_input, nullptr, nullptr, (float *)d->c_sc.p,
                      (int32_t *)d->c_ln.p, d_nres, stream, &sc, states[0]->scorer, &co);
   if (rc) return rc;
   for (int b = 0; b < B; ++b) states[b]->frames += lens[b];
+  if (launched) launched();
+  if (remap_tab && any_eos) {  // the frame half of every record goes back through the streams' maps (stream_blank_skip.h)
+    if (d->timing) {
+      if ((rc = sskip_timing_events(d))) return rc;
+      HIP_TRY(hipEventRecord(d->ev_sk[2], stream));
+    }
+    const int e = ctcsskip::launch_remap_compact((const int32_t *)d->c_hdr.p, (const int32_t *)d->c_ent.p, (uint32_t *)d->c_rag.p, remap_tab, B, beam, (void *)stream);
+    if (e != (int)hipSuccess) return fail(CTCD_EHIP, std::string("ctc_stream_remap_compact_kernel: ") + hipGetErrorString((hipError_t)e));
+    if (d->timing) {
+      HIP_TRY(hipEventRecord(d->ev_sk[3], stream));
+      d->sk_remap_timed = true;
+    }
+    if ((rc = sskip_table_used(d, stream))) return rc;
+  }
   struct Drain {
     hipStream_t a;
     ~Drain() { (void)hipStreamSynchronize(a); }

@@ -491,6 +491,52 @@ int ctcd_remap_compact(ctcd_decoder *dec, const int32_t *c_hdr, const int32_t *c
 int ctcd_remap_timesteps_host(int32_t *out_timesteps, const int32_t *out_lens, const int32_t *kept, const int32_t *kept_lens, int B,
                               int K, int T, int num_threads);
 
+/* ---- Blank-frame filter of live streams (no reference counterpart): the same filter in front of every chunk of the streams of a
+ * decoder.  ctcd_set_stream_blank_skip(dec, on, cmp_prob, cmp_log) is state of `dec` (off by default; off leaves every streaming
+ * call exactly as it is): cmp_prob is the float32 bound for log_input == 0, cmp_log the one for log_input == 1 and 2 (the threshold
+ * and its logarithm, rounded to float32 by the caller; NaN is CTCD_EINVAL).
+ *
+ * Definition.  A stream's SEEN frames are the valid frames of all chunks fed so far, probs[b, :clamp(seq_lens_host[b], 0, T)] of each
+ * call in order.  Seen frame s is skipped iff its blank value v > cmp (ctcd_blank_skip's compare: ordered, strict, NaN kept, equality
+ * kept, a half element widened exactly; log_input == 2: v is the blank entry of ctcd_log_softmax of the row).  The stream decodes the
+ * kept frames alone, and every time step it reports is the kept frame's index among the seen frames: the stream-ending call, and
+ * ctcd_stream_peek (results, `since`, stable_lens count labels as ever) and ctcd_stream_commit (the returned labels' time steps, and
+ * everything reported afterwards).  So, however the frames were cut into chunks, a stream returns what the one-shot decode of the
+ * concatenation behind ctcd_blank_skip returns -- tokens, scores, lengths, result counts and time steps, bit for bit.  A chunk whose
+ * frames are all skipped feeds nothing (also when it ends the stream); a stream whose frames were all skipped ends with the root alone.
+ *
+ * With the filter on, ctcd_stream_decode, ctcd_stream_decode_to_host, ctcd_stream_peek and ctcd_stream_commit do all of it inside the
+ * one call, on the caller's stream: log-softmax first for raw logits (float32; the rows are then filtered and decoded as
+ * log-probabilities), scan and gather into decoder-owned scratch, the decode of the kept rows with the kept counts as chunk lengths,
+ * the remap of whatever the call reports.  seq_lens_host is a host array and the node pools are sized from it on the host: A FILTERED
+ * CHUNK CALL WAITS FOR `stream` until the B kept counts have arrived, before it launches its decode -- one small read per call, which
+ * costs a stream synchronisation (ctcd_stream_decode is no longer asynchronous up to that point; what it queues behind is).
+ * Each stream owns a frame map in device memory, int32, 4 bytes per kept frame (map[i] = seen-index of the i-th kept frame): an
+ * allocation of its own beside the stream's block, made with the stream (room for the frames its pool starts with), grown by doubling
+ * on the stream the chunks are queued on, freed with the stream,
+ * never shrunk (ctcd_stream_compact and ctcd_stream_commit leave it alone); ctcd_stream_map_bytes reports it.
+ * ctcd_stream_frames keeps its meaning -- the frames the stream has DECODED, the kept ones: pool bounds, the 2^31 refusal, out_T
+ * (>= the kept frames of an ending stream) and ctcd_set_stream_compaction count those -- and ctcd_stream_frames_seen reports the seen
+ * frames (for a stream that never met the filter: the same number).  frames, frames seen and the map's used length advance together,
+ * and only when the decode launch was accepted: a refused call leaves the stream as it was (map entries written beyond `frames` are
+ * overwritten by the next call).  ctcd_last_stream_blank_skip: frames considered and kept by the last filtered chunk call.
+ * Compact delivery holds 16-bit frame numbers: with the filter on ctcd_stream_decode_to_host serves a call only while
+ * frames seen + T <= 65536 for every stream of it (the records are remapped on the device and fetched from there; no page-locked
+ * mirror); beyond that it returns CTCD_EUNSUPPORTED and the streams end through ctcd_stream_decode, whose padded tensors are remapped
+ * on the device.
+ * Restrictions.  A stream adopts the filter at its first chunk: a stream that has frames under the other setting is CTCD_EINVAL on
+ * ctcd_stream_decode / _to_host / _peek / _commit, and nothing changes.  ctcd_stream_save of a filtered stream and
+ * ctcd_stream_restore on a decoder with the filter on are CTCD_EUNSUPPORTED (the image format has no place for the map); the
+ * refused streams stay live and decode on.  Streams with the built-in scorer and behind a callback scorer take the filter like any
+ * other (ctcd_stream_peek behind a callback scorer stays refused).
+ * ctcd_last_stream_blank_skip_ms (with ctcd_set_timing): HIP-event time of the last filtered chunk call's filter (log-softmax, scan,
+ * gather), host time of its wait for the kept counts, HIP-event time of the remap behind it (0 where none ran). */
+int ctcd_set_stream_blank_skip(ctcd_decoder *dec, int on, float cmp_prob, float cmp_log);
+long long ctcd_stream_frames_seen(const ctcd_stream *st); /* -1: st == NULL */
+long long ctcd_stream_map_bytes(const ctcd_stream *st);   /* -1: st == NULL */
+int ctcd_last_stream_blank_skip(ctcd_decoder *dec, long long *considered, long long *kept);
+int ctcd_last_stream_blank_skip_ms(ctcd_decoder *dec, float *filter_ms, float *wait_ms, float *remap_ms);
+
 /* ---- n-best results (no reference counterpart): rows 0 .. n-1 of every item alone.  The one-shot entry points above return all
  * `beam` rows -- two padded [B, beam, T] tensors -- and almost every caller reads row 0 or a handful.  With 1 <= n_best <= beam:
  *   out_tokens, out_timesteps int32 [B][n_best][T]     out_scores float [B][n_best]     out_lens int32 [B][n_best]
