@@ -33,7 +33,8 @@ SYMBOLS = ["ctcd_log_softmax", "ctcd_compact_label_capacity", "ctcd_beam_decode_
            "ctcd_set_threads", "ctcd_set_cu_sharing", "ctcd_set_input_dtype", "ctcd_last_input_dtype", "ctcd_set_launch_order", "ctcd_debug_last_launch_order", "ctcd_set_subtree_search", "ctcd_last_subtree_search", "ctcd_debug_last_layout", "ctcd_debug_last_kernel", "ctcd_debug_last_prepass", "ctcd_debug_prepass_table", "ctcd_debug_set_host_path", "ctcd_set_timing", "ctcd_last_kernel_ms", "ctcd_last_prune_ms", "ctcd_last_resolve_ms", "ctcd_debug_math_check", "ctcd_debug_set_profile", "ctcd_debug_set_fixed_layout", "ctcd_debug_set_prune_resolve", "ctcd_debug_set_fused_logits", "ctcd_debug_set_prune_registers", "ctcd_debug_prune_rows", "ctcd_debug_timeline", "ctcd_debug_timeline_cap", "ctcd_debug_get_profile", "ctcd_debug_beam_dump", "ctcd_workgroup_lds_bytes", "ctcd_last_error", "ctcd_version",
            "ctcd_blank_skip", "ctcd_remap_timesteps", "ctcd_remap_compact", "ctcd_remap_timesteps_host",
            "ctcd_set_stream_blank_skip", "ctcd_stream_frames_seen", "ctcd_stream_map_bytes", "ctcd_last_stream_blank_skip", "ctcd_last_stream_blank_skip_ms",
-           "ctcd_expand_compact_nbest", "ctcd_beam_decode_nbest", "ctcd_beam_decode_to_host_nbest"]
+           "ctcd_expand_compact_nbest", "ctcd_beam_decode_nbest", "ctcd_beam_decode_to_host_nbest",
+           "ctcd_ctc_align", "ctcd_set_align_scratch", "ctcd_last_align_grid"]
 
 
 def _load():
@@ -174,6 +175,12 @@ def _load():
     # ... the decode entry points: `scorer`, then n_best, sit before the outputs
     lib.ctcd_beam_decode_nbest.argtypes = common[:12] + [ctypes.c_void_p, ctypes.c_int] + common[12:] + [ctypes.c_void_p]
     lib.ctcd_beam_decode_to_host_nbest.argtypes = common[:3] + [ctypes.c_int] + common[3:12] + [ctypes.c_void_p, ctypes.c_int] + common[12:] + [ctypes.c_void_p]
+    # forced alignment (align.hip): dec, probs, seq_lens, B, T, V, blank_id, log_input, tokens, lens, R, L_stride, out_start, out_end,
+    # out_scores, status, stream
+    lib.ctcd_ctc_align.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_int] * 5 + [ctypes.c_void_p] * 2 + [ctypes.c_int] * 2 + [ctypes.c_void_p] * 5
+    lib.ctcd_set_align_scratch.argtypes = [ctypes.c_void_p, ctypes.c_longlong]
+    lib.ctcd_last_align_grid.argtypes = [ctypes.c_void_p]
+    lib.ctcd_last_align_grid.restype = ctypes.c_longlong
     return lib
 
 

@@ -36,6 +36,7 @@
 #include "blank_skip.h"
 #include "stream_blank_skip.h"
 #include "nbest.h"
+#include "align.h"
 
 namespace {
 
@@ -1413,6 +1414,10 @@ struct ctcd_decoder {
   float sk_wait_ms = 0.f;
   long long sk_last[2] = {0, 0};      // frames considered | kept by the last filtered chunk call (ctcd_last_stream_blank_skip)
   std::mutex mu_skip;                 // a filtered streaming call holds it from its scan to its remap
+  // ctcd_ctc_align (align.h): the back-pointer slots of its persistent workgroups, the float32 log-softmax rows of raw logits, the
+  // budget of the former (ctcd_set_align_scratch; 0 = the default) and the grid of the last call (ctcd_last_align_grid)
+  Buf al_bp, al_lsm;
+  long long al_budget = 0, al_grid = 0;
   std::mutex mu;
   std::mutex mu_host;  // the host-tensor entry points: compact buffers, page-locked staging and the worker threads are per decoder
 };
@@ -1438,6 +1443,33 @@ int nbest_decoder_info(const ctcd_decoder *d, NbestDecoderInfo *out) {
 }
 int nbest_fail(int code, const char *msg) { return fail(code, msg ? msg : ""); }
 }  // namespace ctcnbest
+
+// ... and the forced alignment's (align.hip): device, input dtype and scratch budget; its two decoder-owned buffers
+namespace ctcalign {
+int align_decoder_info(const ctcd_decoder *d, AlignDecoderInfo *out) {
+  if (!d || !out) return fail(CTCD_EINVAL, "decoder == NULL");
+  out->device = d->device;
+  out->in_dtype = d->in_dtype;
+  out->budget = d->al_budget;
+  return CTCD_OK;
+}
+int align_fail(int code, const char *msg) { return fail(code, msg ? msg : ""); }
+int align_scratch(ctcd_decoder *d, size_t bytes, void **p) {
+  std::lock_guard<std::mutex> lock(d->mu);
+  if (const int rc = d->al_bp.ensure(bytes)) return rc;
+  *p = d->al_bp.p;
+  return CTCD_OK;
+}
+int align_lsm_rows(ctcd_decoder *d, const void *logits, const int32_t *seq_lens, int B, int T, int V, void *stream, const float **rows) {
+  {
+    std::lock_guard<std::mutex> lock(d->mu);
+    if (const int rc = d->al_lsm.ensure((size_t)B * T * V * sizeof(float))) return rc;
+  }
+  *rows = (const float *)d->al_lsm.p;
+  return ctcd_log_softmax(d, (const float *)logits, seq_lens, B, T, V, (float *)d->al_lsm.p, stream);
+}
+void align_note_grid(ctcd_decoder *d, long long grid) { d->al_grid = grid; }
+}  // namespace ctcalign
 
 // One audio stream's parked decoder state (ctcd_stream_*): a single HBM block [header | beam arrays | node pool].
 struct ctcd_stream {
@@ -1672,6 +1704,7 @@ void ctcd_destroy(ctcd_decoder *d) {
   d->cp_scratch.release();
   if (d->h_cp) (void)hipHostFree(d->h_cp);
   d->sk_rows.release(); d->sk_kept.release(); d->sk_lsm.release();
+  d->al_bp.release(); d->al_lsm.release();
   if (d->h_sk) (void)hipHostFree(d->h_sk);
   if (d->ev_sk_tab) (void)hipEventDestroy(d->ev_sk_tab);
   for (int i = 0; i < 4; ++i) if (d->ev_sk[i]) (void)hipEventDestroy(d->ev_sk[i]);
@@ -1697,6 +1730,14 @@ int ctcd_debug_set_host_path(ctcd_decoder *d, int input_streaming, long long mir
   if (mirror_cap_labels >= -1) d->mirror_cap_override = mirror_cap_labels;
   return CTCD_OK;
 }
+
+// Forced alignment (align.hip): the budget of its back-pointer scratch, and the workgroups its last call launched.
+int ctcd_set_align_scratch(ctcd_decoder *d, long long bytes) {
+  if (!d || bytes < 0) return fail(CTCD_EINVAL, "ctcd_set_align_scratch: a decoder and bytes >= 0 (0 = the default) required");
+  d->al_budget = bytes;
+  return CTCD_OK;
+}
+long long ctcd_last_align_grid(const ctcd_decoder *d) { return d ? d->al_grid : -1; }
 
 int ctcd_set_cu_sharing(ctcd_decoder *d, int mode) {
   if (!d || mode < -1 || mode > 1) return fail(CTCD_EINVAL, "cu sharing mode must be -1 (automatic), 0 or 1");

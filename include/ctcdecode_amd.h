@@ -569,6 +569,57 @@ int ctcd_beam_decode_to_host_nbest(ctcd_decoder *dec, const float *probs, const 
                                    ctcd_scorer *scorer, int n_best, int32_t *out_tokens, int32_t *out_timesteps, float *out_scores,
                                    int32_t *out_lens, int32_t *n_results, void *stream);
 
+/* ---- Forced alignment (no reference counterpart): for the rows a caller keeps, the frames each label occupies on the best CTC path
+ * of the row through the item's acoustic rows, and that path's score -- a Viterbi score that does not depend on what the beam search
+ * pruned.  (out_timesteps of a decode is something else: the frame at which the search first appended the label.)
+ *
+ * Definition.  For item b: n = clamp(seq_lens[b], 0, T) (T when seq_lens is NULL).  lp(t, c) is the float32 log-probability of
+ * label c at frame t, as the decoder's input mode defines it:
+ *   log_input == 1: the input value, a half value widened exactly.
+ *   log_input == 0: float(log(double(p) + FLT_MIN)), the value prob_to_log_kernel computes.
+ *   log_input == 2: the value ctcd_log_softmax writes.
+ * A hypothesis y[0..L) has the extended sequence z of S = 2L + 1 states: z[2i] = blank_id, z[2i+1] = y[i].  The recurrence:
+ *   d[0][0] = lp(0, blank).   d[0][1] = lp(0, y[0]) (if L >= 1).   d[0][s] = -inf otherwise.
+ *   d[t][s] = lp(t, z[s]) + max(d[t-1][s], d[t-1][s-1], d[t-1][s-2]).
+ *     The third predecessor is allowed only for odd s >= 3 with z[s] != z[s-2].  A predecessor index below 0 does not exist.
+ *   The addition is one float32 addition; the maximum is exact.
+ *   Back-pointer: the allowed predecessor with the greatest value; among equals the one with the largest state index (stay, before
+ *   s-1, before s-2).
+ *   End state: the greater of d[n-1][S-1] and d[n-1][S-2] (S-2 only if L >= 1).  On equality the end state is S-1.
+ * The result: `score` is that end value.  The path is traced back from there.  start[i] and end[i] are the first and last frame,
+ * inclusive, that the path spends in state 2i+1.
+ * The special cases:
+ *   A hypothesis with score == -inf or n == 0 with L > 0 is NOT ALIGNED.  This covers L > n, repeats that do not fit, and rows of
+ *   -inf.  Its score is -inf and its spans are 0.
+ *   L == 0 and n >= 1: the score is the sum of the blank's lp over the n frames in frame order, and there are no spans.
+ *   L == 0 and n == 0: score 0.
+ *   NaN inputs are undefined, as for the beam search.
+ * Every position of the outputs at or beyond a row's length is written as 0.
+ * The validity rules: a label outside [0, V), a label equal to blank_id, or a length outside [0, L_stride] makes the row INVALID.  An
+ * invalid row's outputs are zeroed and its score is 0.  The item's word of `status` is raised to CTCD_ALIGN_BAD_ROW.  Nothing is
+ * ever read through an unchecked index.
+ *
+ * ctcd_ctc_align: everything is device memory and asynchronous on `stream`.  probs [B][T][V] has the dtype ctcd_set_input_dtype set
+ * (f32 / f16 / bf16, widened exactly as everywhere else).  tokens int32 [B][R][L_stride], lens int32 [B][R]: with L_stride = T the
+ * call takes a device decode's out_tokens and out_lens as they are, R = beam or n_best.  out_start, out_end int32 [B][R][L_stride],
+ * out_scores float [B][R].  status: B device words the caller has zeroed, or NULL; words of items without an invalid row are not
+ * written.  log_input == 2 runs the log-softmax pass into decoder-owned float32 scratch first; log_input == 0 converts the values it
+ * gathers with the device's restated binary64 log and makes no converted copy of the input.  The back-pointers (2 bits per frame and
+ * state) live in decoder-owned scratch cut into slots of the worst-case size for (T, min(L_stride, T)); min(B x R, budget / slot
+ * bytes) persistent workgroups -- at least one -- take the rows in turn, so nothing of `lens` is read on the host and no
+ * allocation grows with B x R.  The scratch belongs to the decoder's next alignment: queue that call on the same stream, or wait.
+ * CTCD_EINVAL for bad shapes (negative sizes, V < 1, blank_id outside [0, V), log_input outside 0 .. 2, a NULL tensor), and nothing is
+ * launched.  CTCD_EUNSUPPORTED: min(L_stride, T) > 2047 (an extended sequence beyond the 4096 states one workgroup holds).
+ * ctcd_set_align_scratch: the budget of the back-pointer scratch in bytes; 0 = the default (256 MiB).
+ * ctcd_last_align_grid: the workgroups the last ctcd_ctc_align launched (0: none yet; -1: dec == NULL). */
+#define CTCD_ALIGN_BAD_ROW 8
+int ctcd_ctc_align(ctcd_decoder *dec, const void *probs, const int32_t *seq_lens, int B, int T, int V, int blank_id, int log_input,
+                   const int32_t *tokens /* [B][R][L_stride] */, const int32_t *lens /* [B][R] */, int R, int L_stride,
+                   int32_t *out_start, int32_t *out_end /* [B][R][L_stride] */, float *out_scores /* [B][R] */,
+                   int32_t *status /* [B] zeroed by the caller, or NULL */, void *stream);
+int ctcd_set_align_scratch(ctcd_decoder *dec, long long bytes);   /* budget of the back-pointer scratch; 0 = the default */
+long long ctcd_last_align_grid(const ctcd_decoder *dec);
+
 /* Tuning / introspection. */
 int ctcd_set_threads(ctcd_decoder *dec, int threads_per_workgroup); /* 0 = automatic (default); else a power of two in [64, 1024] */
 /* Two workgroups per CU.  The fixed-layout class (beam <= 128, <= 32 labels) has a second build of its kernel that fits
