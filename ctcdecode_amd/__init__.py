@@ -813,6 +813,62 @@ class CTCBeamDecoder(object):
         """Test hook: the workgroups the last ``align`` launched."""
         return int(_native.lib.ctcd_last_align_grid(self._handle))
 
+    def log_likelihood(self, probs, seq_lens, beam_results, out_lens):
+        """The CTC log-likelihood on the device (include/ctcdecode_amd.h "CTC log-likelihood"): for every row
+        ``beam_results[b, r, :out_lens[b, r]]``, ``log P(y | x)`` -- the sum over ALL alignments of its labels through the rows
+        ``probs[b, :seq_lens[b]]``, by the forward algorithm in float32, defined bit for bit.  Returns float32 [B, R]; ``-inf`` for a row
+        no alignment fits.  Unlike ``beam_scores`` it does not depend on ``beam_width``, ``cutoff_top_n`` or ``blank_skip``.
+
+        To re-rank an n-best list, sort each item's rows by this value (plus whatever a language model adds), greatest first: it is
+        comparable across beam widths and decoders, and ``exp`` of it is the model's posterior of the whole transcript.
+        ``log_likelihood - align(...)[2]`` is >= 0 and says how much of that mass lies outside the single best alignment (0: one
+        alignment holds all of it).
+
+        Tensor handling is that of ``align``: any label tensor and its lengths, CPU or device; the result is on the device when
+        ``beam_results`` is, otherwise CPU.  Follows the decoder's ``blank_id`` and input mode; half dtypes on the device are read as they
+        are.  Raises ``ValueError`` for a row with a label outside the vocabulary, a blank label or a length outside [0, L]."""
+        if probs.dim() != 3:
+            raise ValueError("probs must be [batch, time, labels]")
+        if beam_results.dim() != 3 or out_lens.dim() != 2 or tuple(out_lens.shape) != tuple(beam_results.shape[:2]):
+            raise ValueError("beam_results must be [batch, rows, labels] and out_lens [batch, rows]")
+        on_device = beam_results.is_cuda
+        probs = _input_rows(self, probs)
+        B, T, V = probs.shape
+        if beam_results.shape[0] != B:
+            raise ValueError("beam_results.shape[0] (%d) does not match the batch (%d)" % (beam_results.shape[0], B))
+        if V != self._num_labels:
+            raise ValueError("probs.shape[2] (%d) does not match the number of labels (%d)" % (V, self._num_labels))
+        if not 0 <= int(self._blank_id) < V:
+            raise ValueError("ctcdecode_amd: blank_id must index the vocabulary")
+        if seq_lens is not None:
+            seq_lens = seq_lens.to(device=self._device, dtype=torch.int32).contiguous()
+            if seq_lens.numel() != B:
+                raise ValueError("seq_lens must have one entry per batch item")
+        tokens = beam_results.to(device=self._device, dtype=torch.int32).contiguous()
+        lens = out_lens.to(device=self._device, dtype=torch.int32).contiguous()
+        R, L = int(tokens.shape[1]), int(tokens.shape[2])
+        with torch.cuda.device(self._device):
+            loglik = torch.empty((B, R), dtype=torch.float32, device=self._device)
+            status = torch.zeros((max(B, 1),), dtype=torch.int32, device=self._device)
+            stream = torch.cuda.current_stream(self._device).cuda_stream
+            _native.check(_native.lib.ctcd_ctc_loglik(
+                self._handle, probs.data_ptr(), seq_lens.data_ptr() if seq_lens is not None else None, B, T, V, int(self._blank_id), self._log_probs,
+                tokens.data_ptr(), lens.data_ptr(), R, L, loglik.data_ptr(), status.data_ptr(), stream))
+            bad = torch.nonzero(status[:B]).flatten().tolist() if B else []
+        if bad:
+            raise ValueError("ctcdecode_amd: log_likelihood: items %s have a row with a label outside the vocabulary, a blank label or a length "
+                             "outside [0, %d] (CTCD_ALIGN_BAD_ROW)" % (bad[:8], L))
+        return loglik if on_device else loglik.cpu()
+
+    def set_loglik_grid(self, n=0):
+        """The most workgroups a launch of ``log_likelihood`` uses (include/ctcdecode_amd.h ctcd_set_loglik_grid); 0 = the default, the
+        workgroups the device holds at once.  The results do not depend on it."""
+        _native.check(_native.lib.ctcd_set_loglik_grid(self._handle, int(n)))
+
+    def last_loglik_grid(self):
+        """Test hook: the workgroups of the widest launch of the last ``log_likelihood``."""
+        return int(_native.lib.ctcd_last_loglik_grid(self._handle))
+
     def decode_padded(self, probs, seq_lens=None, n_best=None):
         """The same call with the padded [B, K, T] tensors crossing PCIe (the delivery of round 1; kept for comparison); with ``n_best``
         the [B, n, T] ones."""

@@ -34,7 +34,8 @@ SYMBOLS = ["ctcd_log_softmax", "ctcd_compact_label_capacity", "ctcd_beam_decode_
            "ctcd_blank_skip", "ctcd_remap_timesteps", "ctcd_remap_compact", "ctcd_remap_timesteps_host",
            "ctcd_set_stream_blank_skip", "ctcd_stream_frames_seen", "ctcd_stream_map_bytes", "ctcd_last_stream_blank_skip", "ctcd_last_stream_blank_skip_ms",
            "ctcd_expand_compact_nbest", "ctcd_beam_decode_nbest", "ctcd_beam_decode_to_host_nbest",
-           "ctcd_ctc_align", "ctcd_set_align_scratch", "ctcd_last_align_grid"]
+           "ctcd_ctc_align", "ctcd_set_align_scratch", "ctcd_last_align_grid",
+           "ctcd_ctc_loglik", "ctcd_set_loglik_grid", "ctcd_last_loglik_grid"]
 
 
 def _load():
@@ -181,6 +182,11 @@ def _load():
     lib.ctcd_set_align_scratch.argtypes = [ctypes.c_void_p, ctypes.c_longlong]
     lib.ctcd_last_align_grid.argtypes = [ctypes.c_void_p]
     lib.ctcd_last_align_grid.restype = ctypes.c_longlong
+    # CTC log-likelihood (loglik.hip): dec, probs, seq_lens, B, T, V, blank_id, log_input, tokens, lens, R, L_stride, out_loglik, status, stream
+    lib.ctcd_ctc_loglik.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_int] * 5 + [ctypes.c_void_p] * 2 + [ctypes.c_int] * 2 + [ctypes.c_void_p] * 3
+    lib.ctcd_set_loglik_grid.argtypes = [ctypes.c_void_p, ctypes.c_longlong]
+    lib.ctcd_last_loglik_grid.argtypes = [ctypes.c_void_p]
+    lib.ctcd_last_loglik_grid.restype = ctypes.c_longlong
     return lib
 
 

@@ -37,6 +37,7 @@
 #include "stream_blank_skip.h"
 #include "nbest.h"
 #include "align.h"
+#include "loglik.h"
 
 namespace {
 
@@ -1418,6 +1419,8 @@ struct ctcd_decoder {
   // budget of the former (ctcd_set_align_scratch; 0 = the default) and the grid of the last call (ctcd_last_align_grid)
   Buf al_bp, al_lsm;
   long long al_budget = 0, al_grid = 0;
+  // ctcd_ctc_loglik (loglik.h): the cap of its grid (ctcd_set_loglik_grid; 0 = the default) and the widest grid of the last call
+  long long ll_cap = 0, ll_grid = 0;
   std::mutex mu;
   std::mutex mu_host;  // the host-tensor entry points: compact buffers, page-locked staging and the worker threads are per decoder
 };
@@ -1470,6 +1473,17 @@ int align_lsm_rows(ctcd_decoder *d, const void *logits, const int32_t *seq_lens,
 }
 void align_note_grid(ctcd_decoder *d, long long grid) { d->al_grid = grid; }
 }  // namespace ctcalign
+
+// ... and the log-likelihood's (loglik.hip), beyond the alignment's hooks: the cap of its grid and the device's compute units
+namespace ctcloglik {
+int loglik_decoder_info(const ctcd_decoder *d, LoglikDecoderInfo *out) {
+  if (!d || !out) return fail(CTCD_EINVAL, "decoder == NULL");
+  out->cap = d->ll_cap;
+  out->cus = d->cu_count;
+  return CTCD_OK;
+}
+void loglik_note_grid(ctcd_decoder *d, long long grid) { d->ll_grid = grid; }
+}  // namespace ctcloglik
 
 // One audio stream's parked decoder state (ctcd_stream_*): a single HBM block [header | beam arrays | node pool].
 struct ctcd_stream {
@@ -1738,6 +1752,14 @@ int ctcd_set_align_scratch(ctcd_decoder *d, long long bytes) {
   return CTCD_OK;
 }
 long long ctcd_last_align_grid(const ctcd_decoder *d) { return d ? d->al_grid : -1; }
+
+// CTC log-likelihood (loglik.hip): the cap of its grid, and the widest grid its last call launched.
+int ctcd_set_loglik_grid(ctcd_decoder *d, long long max_workgroups) {
+  if (!d || max_workgroups < 0) return fail(CTCD_EINVAL, "ctcd_set_loglik_grid: a decoder and max_workgroups >= 0 (0 = the default) required");
+  d->ll_cap = max_workgroups;
+  return CTCD_OK;
+}
+long long ctcd_last_loglik_grid(const ctcd_decoder *d) { return d ? d->ll_grid : -1; }
 
 int ctcd_set_cu_sharing(ctcd_decoder *d, int mode) {
   if (!d || mode < -1 || mode > 1) return fail(CTCD_EINVAL, "cu sharing mode must be -1 (automatic), 0 or 1");

@@ -620,6 +620,55 @@ int ctcd_ctc_align(ctcd_decoder *dec, const void *probs, const int32_t *seq_lens
 int ctcd_set_align_scratch(ctcd_decoder *dec, long long bytes);   /* budget of the back-pointer scratch; 0 = the default */
 long long ctcd_last_align_grid(const ctcd_decoder *dec);
 
+/* ---- CTC log-likelihood (no reference counterpart): for the rows a caller keeps, log P(y | x) -- the sum over ALL alignments of
+ * the row through the item's acoustic rows, by the forward algorithm.  It is the quantity CTC defines: it does not depend on what
+ * the beam search pruned (as the decode's scores do) and is not the single best alignment's share (as ctcd_ctc_align's score is),
+ * so it is what n-best rescoring, confidence estimates and comparisons between decoders are built on.  exp of it is the model's
+ * posterior of the transcript; log-likelihood - alignment score >= 0 is how much of that mass lies outside the best alignment.
+ *
+ * Definition.  n, lp(t, c) for the three log_input modes, the extended sequence z and S = 2L + 1 are exactly those of "Forced
+ * alignment"; so is the third predecessor: allowed only for odd s >= 3 with z[s] != z[s-2].
+ * lse3(v0, v1, v2), the three-way float32 log-sum-exp; an absent argument counts as -inf:
+ *   m = max(v0, v1, v2), exact.  If m == -inf the result is -inf.
+ *   Otherwise the result is logf((expf(v0 - m) + expf(v1 - m)) + expf(v2 - m)) + m.
+ *     Every operation is one float32 operation, and the sum is taken in that order.
+ *     expf and logf are glibc's (2.35, the FMA variants; csrc/exact_math.h expf_nonpos / logf_normal restate them on the domains
+ *     that occur: <= 0 for the exponential, [1, 3] for the logarithm).  expf(0) = 1 exactly and expf(-inf) = 0.
+ *     logf(..) + m is always evaluated: a cell with one finite predecessor m yields +0 + m, which for m = -0.0 is +0.0.
+ *     An implementation may replace the maximum's own term by 1.0f and skip -inf terms (bit-identical); it may not reorder the sum
+ *     or skip the logf.
+ * The recurrence:
+ *   a[0][0] = lp(0, blank).   a[0][1] = lp(0, y[0]) (if L >= 1).   a[0][s] = -inf otherwise.
+ *   a[t][s] = lp(t, z[s]) + lse3(a[t-1][s], a[t-1][s-1], a[t-1][s-2]), one float32 addition.  Predecessors that do not exist or
+ *   are not allowed count as -inf.
+ * The result: ll = lse3(a[n-1][S-1], a[n-1][S-2] (if L >= 1), -inf).
+ * The special cases:
+ *   n == 0: ll = 0 for L == 0, -inf otherwise.
+ *   L > n: -inf, and no recurrence runs.
+ *   NaN and +inf inputs are undefined.  -inf inputs and sums that overflow to -inf follow from the rules above.
+ * The validity rules are those of "Forced alignment": a label outside [0, V), a label equal to blank_id, or a length outside
+ * [0, L_stride] makes the row INVALID.  An invalid row's output is 0, and the item's word of `status` is raised to
+ * CTCD_ALIGN_BAD_ROW (the same value, the same meaning).  Nothing is ever read through an unchecked index.
+ *
+ * ctcd_ctc_loglik: everything is device memory and asynchronous on `stream`; nothing of `lens` is read on the host.  probs, tokens,
+ * lens and status are as for ctcd_ctc_align -- with L_stride = T the call takes a device decode's out_tokens and out_lens as they
+ * are -- and out_loglik is float [B][R].  log_input == 2 runs the log-softmax pass into the decoder-owned float32 rows that
+ * ctcd_ctc_align uses too: they belong to the decoder's next alignment or log-likelihood, so queue that call on the same stream, or
+ * wait.  log_input == 0 converts the values it gathers and makes no converted copy of the input.  There is no other scratch: a
+ * row's states live in registers.  Rows are classed as the alignment's (groups of four one-wave rows side by side; any other row on
+ * a workgroup with 1, 4 or 16 states per lane), one launch per class the shape allows; each takes min(units, cap) persistent
+ * workgroups, the cap being by default the workgroups the device holds at once (compute units x the occupancy the class's registers
+ * allow).  The error codes are ctcd_ctc_align's: CTCD_EINVAL for bad shapes (negative sizes, V < 1, blank_id outside [0, V),
+ * log_input outside 0 .. 2, a NULL tensor), and nothing is launched; CTCD_EUNSUPPORTED for min(L_stride, T) > 2047, V > 2^28 or more
+ * than 2^31 - 1 rows.  B x R == 0 is CTCD_OK and launches nothing.  Streams are out of scope: score the concatenated rows one-shot.
+ * ctcd_set_loglik_grid: the cap of every launch's grid; 0 = the default.  The results do not depend on it.
+ * ctcd_last_loglik_grid: the widest grid the last ctcd_ctc_loglik launched (0: none yet; -1: dec == NULL). */
+int ctcd_ctc_loglik(ctcd_decoder *dec, const void *probs, const int32_t *seq_lens, int B, int T, int V, int blank_id, int log_input,
+                    const int32_t *tokens /* [B][R][L_stride] */, const int32_t *lens /* [B][R] */, int R, int L_stride,
+                    float *out_loglik /* [B][R] */, int32_t *status /* [B] zeroed by the caller, or NULL */, void *stream);
+int ctcd_set_loglik_grid(ctcd_decoder *dec, long long max_workgroups);   /* 0 = the default */
+long long ctcd_last_loglik_grid(const ctcd_decoder *dec);
+
 /* Tuning / introspection. */
 int ctcd_set_threads(ctcd_decoder *dec, int threads_per_workgroup); /* 0 = automatic (default); else a power of two in [64, 1024] */
 /* Two workgroups per CU.  The fixed-layout class (beam <= 128, <= 32 labels) has a second build of its kernel that fits
