@@ -754,24 +754,14 @@ class CTCBeamDecoder(object):
                                                        B, T, V, out.data_ptr(), stream))
         return out
 
-    def align(self, probs, seq_lens, beam_results, out_lens):
-        """CTC forced alignment on the device (include/ctcdecode_amd.h "Forced alignment"): for every row ``beam_results[b, r, :out_lens[b, r]]``
-        the best path of its labels through the rows ``probs[b, :seq_lens[b]]``.  Returns ``(starts, ends, scores)``: ``starts`` / ``ends``
-        int32 [B, R, L], the first and last frame (inclusive) each label occupies, 0 at or beyond a row's length; ``scores`` float32
-        [B, R], the path's log-probability -- a Viterbi score that does not depend on what the beam search pruned (``timesteps`` of a
-        decode is something else: the frame at which the search first appended a label).  A row no path fits (more labels than frames,
-        repeats that need blanks there is no room for, labels the rows rule out) has score ``-inf`` and zero spans.
-
-        ``beam_results`` [B, R, L] / ``out_lens`` [B, R]: any label tensor and its lengths -- what ``decode``, ``decode_device`` and
-        ``decode_padded`` return, with or without ``n_best``.  CPU or device tensors; the results are on the device when ``beam_results``
-        is, otherwise CPU.  Follows the decoder's ``blank_id`` and input mode; half dtypes on the device are read as they are.
-        ``blank_skip`` plays no part: the labels of a filtered decode are aligned on the original frames.  Raises ``ValueError`` for a row
-        with a label outside the vocabulary, a blank label or a length outside [0, L]."""
+    def _score_rows(self, name, entry, probs, seq_lens, beam_results, out_lens, outputs):
+        """What ``align`` and ``log_likelihood`` (``name``, for the error text) share: the shape checks, the tensors moved to the device, the
+        call of ``entry`` (ctcd_ctc_align / ctcd_ctc_loglik) and the status read.  ``outputs``: (one value per label?, dtype) for each
+        output tensor of the entry point.  -> the output tensors, [B, R, L] or [B, R], on the device."""
         if probs.dim() != 3:
             raise ValueError("probs must be [batch, time, labels]")
         if beam_results.dim() != 3 or out_lens.dim() != 2 or tuple(out_lens.shape) != tuple(beam_results.shape[:2]):
             raise ValueError("beam_results must be [batch, rows, labels] and out_lens [batch, rows]")
-        on_device = beam_results.is_cuda
         probs = _input_rows(self, probs)
         B, T, V = probs.shape
         if beam_results.shape[0] != B:
@@ -788,19 +778,34 @@ class CTCBeamDecoder(object):
         lens = out_lens.to(device=self._device, dtype=torch.int32).contiguous()
         R, L = int(tokens.shape[1]), int(tokens.shape[2])
         with torch.cuda.device(self._device):
-            starts = torch.empty((B, R, L), dtype=torch.int32, device=self._device)
-            ends = torch.empty((B, R, L), dtype=torch.int32, device=self._device)
-            scores = torch.empty((B, R), dtype=torch.float32, device=self._device)
+            outs = [torch.empty((B, R, L) if per_label else (B, R), dtype=dtype, device=self._device) for per_label, dtype in outputs]
             status = torch.zeros((max(B, 1),), dtype=torch.int32, device=self._device)
             stream = torch.cuda.current_stream(self._device).cuda_stream
-            _native.check(_native.lib.ctcd_ctc_align(
-                self._handle, probs.data_ptr(), seq_lens.data_ptr() if seq_lens is not None else None, B, T, V, int(self._blank_id), self._log_probs,
-                tokens.data_ptr(), lens.data_ptr(), R, L, starts.data_ptr(), ends.data_ptr(), scores.data_ptr(), status.data_ptr(), stream))
+            _native.check(entry(self._handle, probs.data_ptr(), seq_lens.data_ptr() if seq_lens is not None else None, B, T, V, int(self._blank_id),
+                                self._log_probs, tokens.data_ptr(), lens.data_ptr(), R, L, *[o.data_ptr() for o in outs], status.data_ptr(), stream))
             bad = torch.nonzero(status[:B]).flatten().tolist() if B else []
         if bad:
-            raise ValueError("ctcdecode_amd: align: items %s have a row with a label outside the vocabulary, a blank label or a length outside "
-                             "[0, %d] (CTCD_ALIGN_BAD_ROW)" % (bad[:8], L))
-        if on_device or B * R == 0:
+            raise ValueError("ctcdecode_amd: %s: items %s have a row with a label outside the vocabulary, a blank label or a length outside "
+                             "[0, %d] (CTCD_ALIGN_BAD_ROW)" % (name, bad[:8], L))
+        return outs
+
+    def align(self, probs, seq_lens, beam_results, out_lens):
+        """CTC forced alignment on the device (include/ctcdecode_amd.h "Forced alignment"): for every row ``beam_results[b, r, :out_lens[b, r]]``
+        the best path of its labels through the rows ``probs[b, :seq_lens[b]]``.  Returns ``(starts, ends, scores)``: ``starts`` / ``ends``
+        int32 [B, R, L], the first and last frame (inclusive) each label occupies, 0 at or beyond a row's length; ``scores`` float32
+        [B, R], the path's log-probability -- a Viterbi score that does not depend on what the beam search pruned (``timesteps`` of a
+        decode is something else: the frame at which the search first appended a label).  A row no path fits (more labels than frames,
+        repeats that need blanks there is no room for, labels the rows rule out) has score ``-inf`` and zero spans.
+
+        ``beam_results`` [B, R, L] / ``out_lens`` [B, R]: any label tensor and its lengths -- what ``decode``, ``decode_device`` and
+        ``decode_padded`` return, with or without ``n_best``.  CPU or device tensors; the results are on the device when ``beam_results``
+        is, otherwise CPU.  Follows the decoder's ``blank_id`` and input mode; half dtypes on the device are read as they are.
+        ``blank_skip`` plays no part: the labels of a filtered decode are aligned on the original frames.  Raises ``ValueError`` for a row
+        with a label outside the vocabulary, a blank label or a length outside [0, L]."""
+        on_device = beam_results.is_cuda
+        starts, ends, scores = self._score_rows("align", _native.lib.ctcd_ctc_align, probs, seq_lens, beam_results, out_lens,
+                                                ((True, torch.int32), (True, torch.int32), (False, torch.float32)))
+        if on_device or scores.numel() == 0:
             return (starts, ends, scores) if on_device else (starts.cpu(), ends.cpu(), scores.cpu())
         return _to_host((starts, ends, scores))
 
@@ -827,37 +832,8 @@ class CTCBeamDecoder(object):
         Tensor handling is that of ``align``: any label tensor and its lengths, CPU or device; the result is on the device when
         ``beam_results`` is, otherwise CPU.  Follows the decoder's ``blank_id`` and input mode; half dtypes on the device are read as they
         are.  Raises ``ValueError`` for a row with a label outside the vocabulary, a blank label or a length outside [0, L]."""
-        if probs.dim() != 3:
-            raise ValueError("probs must be [batch, time, labels]")
-        if beam_results.dim() != 3 or out_lens.dim() != 2 or tuple(out_lens.shape) != tuple(beam_results.shape[:2]):
-            raise ValueError("beam_results must be [batch, rows, labels] and out_lens [batch, rows]")
         on_device = beam_results.is_cuda
-        probs = _input_rows(self, probs)
-        B, T, V = probs.shape
-        if beam_results.shape[0] != B:
-            raise ValueError("beam_results.shape[0] (%d) does not match the batch (%d)" % (beam_results.shape[0], B))
-        if V != self._num_labels:
-            raise ValueError("probs.shape[2] (%d) does not match the number of labels (%d)" % (V, self._num_labels))
-        if not 0 <= int(self._blank_id) < V:
-            raise ValueError("ctcdecode_amd: blank_id must index the vocabulary")
-        if seq_lens is not None:
-            seq_lens = seq_lens.to(device=self._device, dtype=torch.int32).contiguous()
-            if seq_lens.numel() != B:
-                raise ValueError("seq_lens must have one entry per batch item")
-        tokens = beam_results.to(device=self._device, dtype=torch.int32).contiguous()
-        lens = out_lens.to(device=self._device, dtype=torch.int32).contiguous()
-        R, L = int(tokens.shape[1]), int(tokens.shape[2])
-        with torch.cuda.device(self._device):
-            loglik = torch.empty((B, R), dtype=torch.float32, device=self._device)
-            status = torch.zeros((max(B, 1),), dtype=torch.int32, device=self._device)
-            stream = torch.cuda.current_stream(self._device).cuda_stream
-            _native.check(_native.lib.ctcd_ctc_loglik(
-                self._handle, probs.data_ptr(), seq_lens.data_ptr() if seq_lens is not None else None, B, T, V, int(self._blank_id), self._log_probs,
-                tokens.data_ptr(), lens.data_ptr(), R, L, loglik.data_ptr(), status.data_ptr(), stream))
-            bad = torch.nonzero(status[:B]).flatten().tolist() if B else []
-        if bad:
-            raise ValueError("ctcdecode_amd: log_likelihood: items %s have a row with a label outside the vocabulary, a blank label or a length "
-                             "outside [0, %d] (CTCD_ALIGN_BAD_ROW)" % (bad[:8], L))
+        loglik, = self._score_rows("log_likelihood", _native.lib.ctcd_ctc_loglik, probs, seq_lens, beam_results, out_lens, ((False, torch.float32),))
         return loglik if on_device else loglik.cpu()
 
     def set_loglik_grid(self, n=0):

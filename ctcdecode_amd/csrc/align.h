@@ -5,8 +5,10 @@
 //
 // Everything that defines the result is CTC_HD code here, compiled for both sides: the cell update with its tie rule, the end-state
 // rule, the back-pointer packing (2 bits per cell, 16 cells per word), the scratch-slot arithmetic, the back-trace step that turns a
-// path into spans, and the row validation.  The kernel of align.hip spreads a frame's cells over the lanes of a wave or a workgroup;
-// align_row_host below runs them sequentially (the host twin, tests/native/align_host.cpp).
+// path into spans, and the row validation with the code it gives a row before its first frame.  The kernel of align.hip spreads a
+// frame's cells over the lanes of a wave or a workgroup, by the walk of lattice_device.h that it shares with the log-likelihood
+// (loglik.h, loglik.hip); align_row_host below runs them sequentially (the host twin, tests/native/align_host.cpp).  The last part
+// declares what the two entry points share on the host: the decoder hooks and the entry prelude (align_entry).
 //
 // Every index is checked before it is followed: a length outside [0, L_stride], a label outside [0, V) or equal to the blank makes
 // the row invalid -- zero outputs, score 0, the item's status word raised to ALIGN_BAD_ROW -- and never an out-of-range read.
@@ -95,6 +97,18 @@ CTC_HD int align_npl(int S) { return S <= kAlignThreads ? 1 : (S <= kAlignThread
 // ---- row validation --------------------------------------------------------------------------------------------------------------
 CTC_HD bool len_ok(int L, int L_stride) { return L >= 0 && L <= L_stride; }
 CTC_HD bool label_ok(int c, int V, int blank) { return (unsigned)c < (unsigned)V && c != blank; }
+// what a row is before its first frame: one of these codes, or L -- a valid row that runs the recurrence (0 <= L <= n, n >= 1)
+enum : int { kRowNone = -1, kRowInvalid = -2, kRowNoPath = -3 };  // (no row; invalid; valid, but n == 0 or every label needs a frame of its own)
+CTC_HD int row_code(bool ok, int len, int n) { return !ok ? kRowInvalid : ((n == 0 || len > n) ? kRowNoPath : len); }
+// the score of a row that runs no recurrence (code < 0): 0 for an invalid row and for no labels in no frames, else -inf
+CTC_HD float no_row_score(int code, int len, int n) { return code == kRowInvalid || (n == 0 && len == 0) ? 0.0f : neg_inf(); }
+// the host twins' row, validated label by label; *n: the item's frames
+inline int row_code_host(const int32_t *seq_lens, int b, int T, int V, int blank, const int32_t *tok, int len, int L_stride, int *n) {
+  bool ok = len_ok(len, L_stride);
+  for (int i = 0; ok && i < len; ++i) ok = label_ok(tok[i], V, blank);
+  *n = ctcskip::clamped_len(seq_lens, b, T);
+  return row_code(ok, len, *n);
+}
 
 // ---- the back-trace --------------------------------------------------------------------------------------------------------------
 // The path is in state e at frame n - 1 ...
@@ -124,18 +138,11 @@ template <int DT, bool PROB>
 inline int align_row_host(const void *probs, const int32_t *seq_lens, int b, int T, int V, int blank, const int32_t *tok, int len, int L_stride, uint32_t *slot,
                           int32_t *st, int32_t *en, float *score) {
   for (int i = 0; i < L_stride; ++i) st[i] = en[i] = 0;
-  *score = 0.0f;
-  bool ok = len_ok(len, L_stride);
-  for (int i = 0; ok && i < len; ++i) ok = label_ok(tok[i], V, blank);
-  if (!ok) return ALIGN_BAD_ROW;
-  const int n = ctcskip::clamped_len(seq_lens, b, T), L = len, S = n_states(L);
-  if (n == 0) {
-    *score = L == 0 ? 0.0f : neg_inf();
-    return 0;
-  }
-  if (L > n) {  // (no path: every label needs a frame of its own)
-    *score = neg_inf();
-    return 0;
+  int n;
+  const int L = row_code_host(seq_lens, b, T, V, blank, tok, len, L_stride, &n), S = n_states(L);
+  if (L < 0) {
+    *score = no_row_score(L, len, n);
+    return L == kRowInvalid ? ALIGN_BAD_ROW : 0;
   }
   const int wpf = bp_row_words(S);
   const size_t row0 = (size_t)b * T;
@@ -172,7 +179,21 @@ struct AlignDecoderInfo {
 }  // namespace ctcalign
 
 struct ctcd_decoder;
+namespace ctcdev {
+struct DeviceGuard;  // device_guard.h
+}
 namespace ctcalign {
+// What ctcd_ctc_align and ctcd_ctc_loglik do alike before their launch (align.hip): the checks of the arguments they share -- `fn`, the
+// entry point's name, stands in the messages; `outputs`: its output tensors are there -- the decoder's info, its device entered
+// through `guard`, and for raw logits the log-softmax pass.  -> CTCD_OK with e filled in (rows == 0: nothing to do), or the failure.
+struct AlignEntry {
+  long long rows;     // B * R
+  const void *probs;  // the rows to read, of element type `dtype`, log-probabilities unless log_input == 0
+  int dtype;
+  AlignDecoderInfo inf;
+};
+int align_entry(const char *fn, ctcd_decoder *d, const void *probs, const int32_t *seq_lens, int B, int T, int V, int blank_id, int log_input, const int32_t *tokens,
+                const int32_t *lens, int R, int L_stride, bool outputs, void *stream, ctcdev::DeviceGuard *guard, AlignEntry *e);
 int align_decoder_info(const ctcd_decoder *d, AlignDecoderInfo *out);
 int align_fail(int code, const char *msg);
 // the decoder's back-pointer scratch, grown to `bytes`

@@ -13,6 +13,7 @@
 
 #include "../../include/ctcdecode_amd.h"
 #include "blank_skip.h"
+#include "device_guard.h"
 
 namespace ctcskip {
 
@@ -97,20 +98,6 @@ __global__ void __launch_bounds__(kRemapThreads) ctc_remap_compact_kernel(const 
 
 namespace {
 
-// the caller's current device is put back on exit (as every entry point of ctcdecode_amd.hip does)
-struct SkipDeviceGuard {
-  int prev = -1;
-  hipError_t err = hipSuccess;
-  explicit SkipDeviceGuard(int dev) {
-    int cur = -1;
-    if (hipGetDevice(&cur) == hipSuccess && cur != dev) prev = cur;
-    if (cur != dev) err = hipSetDevice(dev);
-  }
-  ~SkipDeviceGuard() {
-    if (prev >= 0) (void)hipSetDevice(prev);
-  }
-};
-
 int hip_fail(const char *what, hipError_t e) { return skip_fail(CTCD_EHIP, (std::string(what) + ": " + hipGetErrorString(e)).c_str()); }
 
 template <typename W>
@@ -146,7 +133,7 @@ int ctcd_blank_skip(ctcd_decoder *d, const void *x, const int32_t *seq_lens, int
   if (x == out_rows) return skip_fail(CTCD_EINVAL, "ctcd_blank_skip: the filter is not in place");
   SkipDecoderInfo inf;
   if (const int rc = skip_decoder_info(d, &inf)) return rc;
-  SkipDeviceGuard guard(inf.device);
+  ctcdev::DeviceGuard guard(inf.device);
   if (guard.err != hipSuccess) return hip_fail("hipSetDevice", guard.err);
   hipStream_t s = (hipStream_t)stream;
   switch (inf.in_dtype) {
@@ -175,7 +162,7 @@ int ctcd_remap_timesteps(ctcd_decoder *d, int32_t *timesteps, const int32_t *out
   if (B <= 0 || K <= 0 || T <= 0) return skip_fail(CTCD_EINVAL, "ctcd_remap_timesteps: B, K, T > 0 required");
   SkipDecoderInfo inf;
   if (const int rc = skip_decoder_info(d, &inf)) return rc;
-  SkipDeviceGuard guard(inf.device);
+  ctcdev::DeviceGuard guard(inf.device);
   if (guard.err != hipSuccess) return hip_fail("hipSetDevice", guard.err);
   const long long n_rows = (long long)B * K, per = kRemapThreads / 64;
   if ((n_rows + per - 1) / per > 0x7fffffffLL) return skip_fail(CTCD_EUNSUPPORTED, "ctcd_remap_timesteps: too many result rows for one launch");
@@ -192,7 +179,7 @@ int ctcd_remap_compact(ctcd_decoder *d, const int32_t *c_hdr, const int32_t *c_e
   if (T > 65536) return skip_fail(CTCD_EINVAL, "ctcd_remap_compact: compact results hold frame numbers below 65536");
   SkipDecoderInfo inf;
   if (const int rc = skip_decoder_info(d, &inf)) return rc;
-  SkipDeviceGuard guard(inf.device);
+  ctcdev::DeviceGuard guard(inf.device);
   if (guard.err != hipSuccess) return hip_fail("hipSetDevice", guard.err);
   hipLaunchKernelGGL(ctc_remap_compact_kernel, dim3((unsigned)B), dim3(kRemapThreads), 0, (hipStream_t)stream, c_hdr, c_ent, c_labels, kept, kept_lens, K, T);
   const hipError_t e = hipGetLastError();

@@ -29,6 +29,7 @@
 #include "lm_build.h"
 #include "lm_callback.h"
 #include "compact_results.h"
+#include "device_guard.h"
 #include "stream_peek.h"
 #include "stream_compact.h"
 #include "stream_commit.h"
@@ -1229,23 +1230,8 @@ int fail(int code, const std::string &msg) {
     if (e_ != hipSuccess) return fail(CTCD_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_));    \
   } while (0)
 
-// Every C ABI entry point works on the decoder's device and puts the caller's current device back on exit (a process
-// that uses several GPUs must not find PyTorch's current device switched by a decode -- or by a destructor that the
-// garbage collector runs at an arbitrary time).
-struct DeviceGuard {
-  int prev = -1;
-  hipError_t err = hipSuccess;
-  explicit DeviceGuard(int dev) {
-    int cur = -1;
-    if (hipGetDevice(&cur) == hipSuccess && cur != dev) prev = cur;
-    if (cur != dev) err = hipSetDevice(dev);
-  }
-  ~DeviceGuard() {
-    if (prev >= 0) (void)hipSetDevice(prev);
-  }
-  DeviceGuard(const DeviceGuard &) = delete;
-  DeviceGuard &operator=(const DeviceGuard &) = delete;
-};
+// Every C ABI entry point works on the decoder's device and puts the caller's current device back on exit (device_guard.h).
+using ctcdev::DeviceGuard;
 #define CTC_ON_DEVICE(dev)  \
   DeviceGuard guard_(dev);  \
   HIP_TRY(guard_.err)

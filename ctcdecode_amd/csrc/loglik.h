@@ -5,9 +5,10 @@
 // by exact_math.h, so the result is defined bit for bit.  No back-pointers, no scratch, no back-trace.
 //
 // Everything that defines the result is CTC_HD code here, compiled for both sides: lse3, the cell, the end rule, and the grid
-// arithmetic of loglik.hip.  The kernel of loglik.hip spreads a frame's cells over the lanes of a wave or a workgroup; loglik_row_host
-// below runs them sequentially (the host twin, tests/native/loglik_host.cpp).  The extended sequence, lp(t, c) for the three input
-// modes and the row validation are align.h's.
+// arithmetic of loglik.hip.  The kernel of loglik.hip spreads a frame's cells over the lanes of a wave or a workgroup, by the walk of
+// lattice_device.h that it shares with align.hip; loglik_row_host below runs them sequentially (the host twin,
+// tests/native/loglik_host.cpp).  The extended sequence, lp(t, c) for the three input modes, the row validation with its row codes and
+// the entry prelude are align.h's.
 #pragma once
 #include "align.h"
 
@@ -67,18 +68,11 @@ template <int DT, bool PROB>
 inline int loglik_row_host(const void *probs, const int32_t *seq_lens, int b, int T, int V, int blank, const int32_t *tok, int len, int L_stride,
                            const uint64_t *tbl, float *out) {
   using namespace ctcalign;
-  *out = 0.0f;
-  bool ok = len_ok(len, L_stride);
-  for (int i = 0; ok && i < len; ++i) ok = label_ok(tok[i], V, blank);
-  if (!ok) return ALIGN_BAD_ROW;
-  const int n = ctcskip::clamped_len(seq_lens, b, T), L = len, S = n_states(L);
-  if (n == 0) {
-    *out = L == 0 ? 0.0f : neg_inf();
-    return 0;
-  }
-  if (L > n) {  // (no alignment: every label needs a frame of its own)
-    *out = neg_inf();
-    return 0;
+  int n;
+  const int L = row_code_host(seq_lens, b, T, V, blank, tok, len, L_stride, &n), S = n_states(L);
+  if (L < 0) {
+    *out = no_row_score(L, len, n);
+    return L == kRowInvalid ? ALIGN_BAD_ROW : 0;
   }
   const size_t row0 = (size_t)b * T;
   std::vector<float> a((size_t)S), na((size_t)S);

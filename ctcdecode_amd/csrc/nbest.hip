@@ -6,6 +6,7 @@
 #include <string>
 
 #include "../../include/ctcdecode_amd.h"
+#include "device_guard.h"
 #include "nbest.h"
 
 namespace ctcnbest {
@@ -155,21 +156,6 @@ int launch_nbest_expand(const NbestDecoderInfo &inf, const int32_t *c_hdr, const
   }
   return e == hipSuccess ? CTCD_OK : nbest_fail(CTCD_EHIP, (std::string("n-best expansion: ") + hipGetErrorString(e)).c_str());
 }
-
-namespace {
-struct NbestDeviceGuard {  // the caller's current device is put back on exit (as every entry point of ctcdecode_amd.hip does)
-  int prev = -1;
-  hipError_t err = hipSuccess;
-  explicit NbestDeviceGuard(int dev) {
-    int cur = -1;
-    if (hipGetDevice(&cur) == hipSuccess && cur != dev) prev = cur;
-    if (cur != dev) err = hipSetDevice(dev);
-  }
-  ~NbestDeviceGuard() {
-    if (prev >= 0) (void)hipSetDevice(prev);
-  }
-};
-}  // namespace
 }  // namespace ctcnbest
 
 using namespace ctcnbest;
@@ -188,7 +174,7 @@ int ctcd_expand_compact_nbest(ctcd_decoder *d, const int32_t *c_hdr, const int32
   if (const int rc = nbest_decoder_info(d, &inf)) return rc;
   if (!nbest_expand_fits(inf, beam, n_best))
     return nbest_fail(CTCD_EUNSUPPORTED, "device expansion of compact results: the entry tables of this beam width exceed one workgroup's LDS");
-  NbestDeviceGuard guard(inf.device);
+  ctcdev::DeviceGuard guard(inf.device);
   if (guard.err != hipSuccess) return nbest_fail(CTCD_EHIP, (std::string("hipSetDevice: ") + hipGetErrorString(guard.err)).c_str());
   return launch_nbest_expand(inf, c_hdr, c_ent, c_labels, (unsigned long long)n_labels, nullptr, nullptr, B, beam, T, n_best, out_tok, out_ts, nullptr, nullptr,
                              status, stream);

@@ -236,12 +236,21 @@ def make_case(name):
         lp = log_softmax_rows(rng, 4, T, V)
         tok, lens = pack_rows(random_rows(rng, 4, 10, 40, V, repeat=0.1), R=10, Ls=T)
         seq = np.asarray([45, 44, 30, 45], np.int32)
+    elif name == "mixed_group":
+        # six rows, R = 3: the first group of four straddles the items and is long (S = 259: four states per lane; S = 7; S = 201: one
+        # state per lane; 64 labels in item 1's 40 frames: no path inside a long group), the last group is partial and long (S = 79; S = 1)
+        T, V = 130, 4
+        rows = [[cycle(129, V, first=1), [1, 2, 3], cycle(100, V)], [cycle(64, V), cycle(39, V), []]]
+        tok, lens = pack_rows(rows, R=3, Ls=T)
+        lp = log_softmax_rows(rng, 2, T, V, scale=1.0)
+        seq = np.asarray([130, 40], np.int32)
     else:
         raise KeyError(name)
     return dict(lp=np.ascontiguousarray(lp, np.float32), seq_lens=seq, tokens=tok, lens=lens, blank=blank)
 
 
-CASES = ["edges", "one_frame", "wave_edge", "workgroup_edge", "many_per_lane", "ties_half", "ties_constant", "neg_inf", "blank_last", "blank_mid", "forty_rows"]
+CASES = ["edges", "one_frame", "wave_edge", "workgroup_edge", "many_per_lane", "ties_half", "ties_constant", "neg_inf", "blank_last", "blank_mid", "forty_rows",
+         "mixed_group"]
 
 
 def hash_name(name):

@@ -43,6 +43,11 @@ def test_the_cases_cover_what_they_are_named_for():
     assert [2 * int(v) + 1 for v in c["lens"][0, :3]] == [255, 257, 259] and want["aligned"].all()
     c, want = au.case("many_per_lane")
     assert [au.host_npl(2 * int(v) + 1) for v in c["lens"][0]] == [16, 4, 1, 1] and want["aligned"].all()
+    c, want = au.case("mixed_group")
+    rows, n = c["lens"].reshape(-1), np.repeat(c["seq_lens"], c["lens"].shape[1])
+    assert [2 * int(v) + 1 for v in rows] == [259, 7, 201, 129, 79, 1], "a full group of four that straddles the items, then a partial one: both hold a row beyond a wave"
+    assert (rows > n).tolist() == [False, False, False, True, False, False] and np.isneginf(want["scores"][1, 0]), "the first group holds a row without a path"
+    assert want["aligned"].reshape(-1).tolist() == [True, True, True, False, True, True]
 
 
 @pytest.mark.parametrize("name", ["ties_half", "ties_constant"])

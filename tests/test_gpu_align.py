@@ -40,7 +40,8 @@ def test_device_equals_the_restatement(torch_mod, name):
     """edges: L = 0 at n = 0 and 1, L = 1 at n = 1, L = n distinct / with a repeat, "a a" at n = 3, ragged seq_lens with a 0, rows of length
     0; one_frame: T = 1; wave_edge: S = 63 / 65; workgroup_edge: S = 255 / 257 / 259; many_per_lane: S = 1023 / 1025, T no multiple of 16;
     ties_*: the tie rules alone decide; neg_inf: a label ruled out over a stretch, a whole frame of -inf; blank_*: blank_id != 0,
-    L_stride < T; forty_rows: rows of both kinds in every group."""
+    L_stride < T; forty_rows: rows of both kinds in every group; mixed_group: a group the workgroup runs row by row that also holds a row
+    without a path, and a partial last group of that kind."""
     torch = torch_mod
     c, want = au.case(name)
     dec = _dec(c["lp"].shape[2], c["blank"])
@@ -163,28 +164,37 @@ def test_raw_abi_refuses_bad_shapes(torch_mod):
     torch.cuda.synchronize()
 
 
+def _check_invalid_row(torch, dec, c, want, what, pos, val):
+    b1, r1 = pos[:2]
+    blank = c["blank"]
+    tok, lens = c["tokens"].copy(), c["lens"].copy()
+    (tok if len(pos) == 3 else lens)[pos] = val
+    got = _raw_align(torch, dec, c, tok, lens)
+    ref = au.reference(c["lp"], c["seq_lens"], tok, lens, blank)
+    assert ref["status"].tolist() == [au.BAD_ROW if b == b1 else 0 for b in range(2)]
+    au.assert_same(got, ref, what)
+    assert not got["start"][b1, r1].any() and not got["end"][b1, r1].any() and got["scores"][b1, r1] == 0, what
+    keep = np.ones(c["lens"].shape, bool)
+    keep[b1, r1] = False
+    assert np.array_equal(got["start"][keep], want["start"][keep]) and np.array_equal(got["end"][keep], want["end"][keep]), what
+    with pytest.raises(ValueError, match="CTCD_ALIGN_BAD_ROW"):
+        dec.align(torch.from_numpy(c["lp"]), None, torch.from_numpy(tok), torch.from_numpy(lens))
+    au.assert_same(_align(torch, dec, torch.from_numpy(c["lp"]).cuda(), c), want, "the decoder afterwards")
+
+
 def test_invalid_rows_raise_their_item_alone(torch_mod):
     """A label = V, a label = blank and a negative length each raise CTCD_ALIGN_BAD_ROW for that item only; the other rows are unchanged
-    and the decoder is usable afterwards."""
+    and the decoder is usable afterwards.  mixed_group: the invalid row lies in a group whose rows the workgroup runs one by one."""
     torch = torch_mod
     c, want = au.case("blank_mid")
     V, blank = c["lp"].shape[2], c["blank"]
     dec = _dec(V, blank)
     r0 = int(np.argmax(c["lens"][1] > 1))
     for what, pos, val in (("label = V", (1, r0, 1), V), ("label = blank", (1, r0, 0), blank), ("length < 0", (1, r0), -1), ("length > L_stride", (1, r0), 13)):
-        tok, lens = c["tokens"].copy(), c["lens"].copy()
-        (tok if len(pos) == 3 else lens)[pos] = val
-        got = _raw_align(torch, dec, c, tok, lens)
-        ref = au.reference(c["lp"], c["seq_lens"], tok, lens, blank)
-        assert ref["status"].tolist() == [0, au.BAD_ROW]
-        au.assert_same(got, ref, what)
-        assert not got["start"][1, r0].any() and not got["end"][1, r0].any() and got["scores"][1, r0] == 0, what
-        keep = np.ones(c["lens"].shape, bool)
-        keep[1, r0] = False
-        assert np.array_equal(got["start"][keep], want["start"][keep]) and np.array_equal(got["end"][keep], want["end"][keep]), what
-        with pytest.raises(ValueError, match="CTCD_ALIGN_BAD_ROW"):
-            dec.align(torch.from_numpy(c["lp"]), None, torch.from_numpy(tok), torch.from_numpy(lens))
-        au.assert_same(_align(torch, dec, torch.from_numpy(c["lp"]).cuda(), c), want, "the decoder afterwards")
+        _check_invalid_row(torch, dec, c, want, what, pos, val)
+    c, want = au.case("mixed_group")
+    V = c["lp"].shape[2]
+    _check_invalid_row(torch, _dec(V, c["blank"]), c, want, "label = V in a long group", (0, 1, 1), V)
 
 
 def test_decode_rows_fed_straight_back(torch_mod):

@@ -48,7 +48,8 @@ def _loglik(torch, dec, rows, c, device=True):
 @pytest.mark.parametrize("name", lu.CASES)
 def test_device_equals_the_restatement(torch_mod, name):
     """align_util's cases -- edges, one_frame, wave_edge (S = 63 / 65), workgroup_edge (S = 255 / 257 / 259), many_per_lane (S = 1023 /
-    1025, T = 514: no multiple of the prefetch depth), ties_*, neg_inf, blank_* (blank_id != 0, L_stride < T), forty_rows -- and zeros
+    1025, T = 514: no multiple of the prefetch depth), ties_*, neg_inf, blank_* (blank_id != 0, L_stride < T), forty_rows, mixed_group (a
+    group the workgroup runs row by row that also holds a row without a path, and a partial last group of that kind) -- and zeros
     (+0.0 / -0.0 values: the logf(1) + m rule), far_apart (differences around -88: an expf term vanishes or only just does not),
     positive (log_input == 1 rows with positive entries), overflow (finite values near -3e38 whose sums overflow to -inf)."""
     torch = torch_mod
@@ -174,28 +175,38 @@ def test_raw_abi_refuses_bad_shapes(torch_mod):
     assert (f[:2] != -123.0).all() and (f[2:] == -123.0).all()
 
 
+def _check_invalid_row(torch, dec, c, want, what, pos, val):
+    b1, r1 = pos[:2]
+    blank = c["blank"]
+    tok, lens = c["tokens"].copy(), c["lens"].copy()
+    (tok if len(pos) == 3 else lens)[pos] = val
+    got = _raw_loglik(torch, dec, c, tok, lens)
+    ref = lu.reference(c["lp"], c["seq_lens"], tok, lens, blank)
+    assert ref["status"].tolist() == [lu.BAD_ROW if b == b1 else 0 for b in range(2)]
+    lu.assert_same(got, ref, what)
+    assert got["loglik"][b1, r1] == 0, what
+    keep = np.ones(c["lens"].shape, bool)
+    keep[b1, r1] = False
+    assert np.array_equal(got["loglik"][keep].view(np.uint32), want["loglik"][keep].view(np.uint32)), what
+    with pytest.raises(ValueError, match=r"items \[%d\].*CTCD_ALIGN_BAD_ROW" % b1):
+        dec.log_likelihood(torch.from_numpy(c["lp"]), None, torch.from_numpy(tok), torch.from_numpy(lens))
+    lu.assert_same(_loglik(torch, dec, torch.from_numpy(c["lp"]).cuda(), c), want, "the decoder afterwards")
+
+
 def test_invalid_rows_raise_their_item_alone(torch_mod):
     """A label = V, a label = blank, a negative length and one beyond L_stride each raise CTCD_ALIGN_BAD_ROW for that item only; the other
-    rows are unchanged and the decoder is usable afterwards."""
+    rows are unchanged and the decoder is usable afterwards.  mixed_group: the invalid row lies in a group whose rows the workgroup
+    runs one by one."""
     torch = torch_mod
     c, want = lu.case("blank_mid")
     V, blank = c["lp"].shape[2], c["blank"]
     dec = _dec(V, blank)
     r0 = int(np.argmax(c["lens"][1] > 1))
     for what, pos, val in (("label = V", (1, r0, 1), V), ("label = blank", (1, r0, 0), blank), ("length < 0", (1, r0), -1), ("length > L_stride", (1, r0), 13)):
-        tok, lens = c["tokens"].copy(), c["lens"].copy()
-        (tok if len(pos) == 3 else lens)[pos] = val
-        got = _raw_loglik(torch, dec, c, tok, lens)
-        ref = lu.reference(c["lp"], c["seq_lens"], tok, lens, blank)
-        assert ref["status"].tolist() == [0, lu.BAD_ROW]
-        lu.assert_same(got, ref, what)
-        assert got["loglik"][1, r0] == 0, what
-        keep = np.ones(c["lens"].shape, bool)
-        keep[1, r0] = False
-        assert np.array_equal(got["loglik"][keep].view(np.uint32), want["loglik"][keep].view(np.uint32)), what
-        with pytest.raises(ValueError, match=r"items \[1\].*CTCD_ALIGN_BAD_ROW"):
-            dec.log_likelihood(torch.from_numpy(c["lp"]), None, torch.from_numpy(tok), torch.from_numpy(lens))
-        lu.assert_same(_loglik(torch, dec, torch.from_numpy(c["lp"]).cuda(), c), want, "the decoder afterwards")
+        _check_invalid_row(torch, dec, c, want, what, pos, val)
+    c, want = lu.case("mixed_group")
+    V = c["lp"].shape[2]
+    _check_invalid_row(torch, _dec(V, c["blank"]), c, want, "label = V in a long group", (0, 1, 1), V)
 
 
 @pytest.mark.parametrize("name", ["edges", "wave_edge", "workgroup_edge", "ties_half", "neg_inf", "blank_mid", "forty_rows", "far_apart", "positive"])
