@@ -755,8 +755,8 @@ class CTCBeamDecoder(object):
         return out
 
     def _score_rows(self, name, entry, probs, seq_lens, beam_results, out_lens, outputs):
-        """What ``align`` and ``log_likelihood`` (``name``, for the error text) share: the shape checks, the tensors moved to the device, the
-        call of ``entry`` (ctcd_ctc_align / ctcd_ctc_loglik) and the status read.  ``outputs``: (one value per label?, dtype) for each
+        """What ``align``, ``log_likelihood`` and ``label_posteriors`` (``name``, for the error text) share: the shape checks, the tensors
+        moved to the device, the call of ``entry`` (ctcd_ctc_align / ctcd_ctc_loglik / ctcd_ctc_posteriors) and the status read.  ``outputs``: (one value per label?, dtype) for each
         output tensor of the entry point.  -> the output tensors, [B, R, L] or [B, R], on the device."""
         if probs.dim() != 3:
             raise ValueError("probs must be [batch, time, labels]")
@@ -844,6 +844,37 @@ class CTCBeamDecoder(object):
     def last_loglik_grid(self):
         """Test hook: the workgroups of the widest launch of the last ``log_likelihood``."""
         return int(_native.lib.ctcd_last_loglik_grid(self._handle))
+
+    def label_posteriors(self, probs, seq_lens, beam_results, out_lens):
+        """CTC forward-backward per label on the device (include/ctcdecode_amd.h "Label posteriors"): for every label ``i`` of every row
+        ``beam_results[b, r, :out_lens[b, r]]``, what the model's posterior over ALL alignments of the row through ``probs[b, :seq_lens[b]]``
+        says about it.  Returns ``(peaks, occupancy, confidence, loglik)``:
+
+        * ``peaks`` int32 [B, R, L]: the frame at which the label's posterior is greatest (the first such frame);
+        * ``occupancy`` float32 [B, R, L]: the expected number of frames the label occupies;
+        * ``confidence`` float32 [B, R, L]: the posterior-weighted mean of the model's probability of the label over the frames it
+          occupies, in [0, 1] -- the soft form of averaging frame confidences over a hard alignment, low when the label is carried by
+          frames that do not vote for it;
+        * ``loglik`` float32 [B, R]: the row's log-likelihood, bit for bit what ``log_likelihood`` returns.
+
+        The per-label outputs are 0 at or beyond a row's length, and for a row no alignment fits (``loglik`` = ``-inf``).  All four are
+        defined bit for bit in float32.  Tensor handling is that of ``align`` and ``log_likelihood``: any label tensor and its lengths,
+        CPU or device; the results are on the device when ``beam_results`` is, otherwise CPU.  Follows the decoder's ``blank_id`` and
+        input mode; half dtypes on the device are read as they are.  Raises ``ValueError`` for a row with a label outside the
+        vocabulary, a blank label or a length outside [0, L]."""
+        on_device = beam_results.is_cuda
+        outs = self._score_rows("label_posteriors", _native.lib.ctcd_ctc_posteriors, probs, seq_lens, beam_results, out_lens,
+                                ((True, torch.int32), (True, torch.float32), (True, torch.float32), (False, torch.float32)))
+        return tuple(outs) if on_device else tuple(o.cpu() for o in outs)
+
+    def set_posterior_scratch(self, nbytes=0):
+        """The budget of ``label_posteriors``' scratch in bytes (include/ctcdecode_amd.h ctcd_set_posterior_scratch); 0 = the default.
+        The persistent workgroups of a call are as many as the budget has slots for, at least one; the results do not depend on it."""
+        _native.check(_native.lib.ctcd_set_posterior_scratch(self._handle, int(nbytes)))
+
+    def last_posterior_grid(self):
+        """Test hook: the workgroups the last ``label_posteriors`` launched."""
+        return int(_native.lib.ctcd_last_posterior_grid(self._handle))
 
     def decode_padded(self, probs, seq_lens=None, n_best=None):
         """The same call with the padded [B, K, T] tensors crossing PCIe (the delivery of round 1; kept for comparison); with ``n_best``

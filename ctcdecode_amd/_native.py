@@ -35,7 +35,8 @@ SYMBOLS = ["ctcd_log_softmax", "ctcd_compact_label_capacity", "ctcd_beam_decode_
            "ctcd_set_stream_blank_skip", "ctcd_stream_frames_seen", "ctcd_stream_map_bytes", "ctcd_last_stream_blank_skip", "ctcd_last_stream_blank_skip_ms",
            "ctcd_expand_compact_nbest", "ctcd_beam_decode_nbest", "ctcd_beam_decode_to_host_nbest",
            "ctcd_ctc_align", "ctcd_set_align_scratch", "ctcd_last_align_grid",
-           "ctcd_ctc_loglik", "ctcd_set_loglik_grid", "ctcd_last_loglik_grid"]
+           "ctcd_ctc_loglik", "ctcd_set_loglik_grid", "ctcd_last_loglik_grid",
+           "ctcd_ctc_posteriors", "ctcd_set_posterior_scratch", "ctcd_last_posterior_grid"]
 
 
 def _load():
@@ -187,6 +188,12 @@ def _load():
     lib.ctcd_set_loglik_grid.argtypes = [ctypes.c_void_p, ctypes.c_longlong]
     lib.ctcd_last_loglik_grid.argtypes = [ctypes.c_void_p]
     lib.ctcd_last_loglik_grid.restype = ctypes.c_longlong
+    # label posteriors (posterior.hip): dec, probs, seq_lens, B, T, V, blank_id, log_input, tokens, lens, R, L_stride, out_peaks,
+    # out_occupancy, out_confidence, out_loglik, status, stream
+    lib.ctcd_ctc_posteriors.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_int] * 5 + [ctypes.c_void_p] * 2 + [ctypes.c_int] * 2 + [ctypes.c_void_p] * 6
+    lib.ctcd_set_posterior_scratch.argtypes = [ctypes.c_void_p, ctypes.c_longlong]
+    lib.ctcd_last_posterior_grid.argtypes = [ctypes.c_void_p]
+    lib.ctcd_last_posterior_grid.restype = ctypes.c_longlong
     return lib
 
 

@@ -18,21 +18,7 @@
 namespace ctcalign {
 
 
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-
-// words [0, count) at p <- 0 by the unit's threads: single words up to the first 16-byte boundary, 16-byte stores, single words
-__device__ __forceinline__ void zero_words(int32_t *p, int count, int utid, int nt) {
-  if (count <= 0) return;
-  int head = (int)(((16u - (unsigned)((uintptr_t)p & 15u)) & 15u) >> 2);
-  if (head > count) head = count;
-  const int body = (count - head) >> 2, tail0 = head + body * 4;
-  if (utid < head) p[utid] = 0;
-  i32x4 z;
-  z.x = 0; z.y = 0; z.z = 0; z.w = 0;
-  i32x4 *q = reinterpret_cast<i32x4 *>(p + head);
-  for (int i = utid; i < body; i += nt) q[i] = z;
-  if (utid < count - tail0) p[tail0 + utid] = 0;
-}
+using ctclattice::zero_words;
 
 // a frame's back-pointers of NPL states per lane, whole words: the lanes that share a word OR their bits together
 template <int NPL> __device__ __forceinline__ uint32_t pack_word(uint32_t bits, int lane) {

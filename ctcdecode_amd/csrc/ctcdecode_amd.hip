@@ -39,6 +39,7 @@
 #include "nbest.h"
 #include "align.h"
 #include "loglik.h"
+#include "posterior.h"
 
 namespace {
 
@@ -1407,6 +1408,10 @@ struct ctcd_decoder {
   long long al_budget = 0, al_grid = 0;
   // ctcd_ctc_loglik (loglik.h): the cap of its grid (ctcd_set_loglik_grid; 0 = the default) and the widest grid of the last call
   long long ll_cap = 0, ll_grid = 0;
+  // ctcd_ctc_posteriors (posterior.h): the slots that keep the forward values between its two walks, their budget
+  // (ctcd_set_posterior_scratch; 0 = the default) and the grid of the last call (ctcd_last_posterior_grid)
+  Buf po_alpha;
+  long long po_budget = 0, po_grid = 0;
   std::mutex mu;
   std::mutex mu_host;  // the host-tensor entry points: compact buffers, page-locked staging and the worker threads are per decoder
 };
@@ -1470,6 +1475,18 @@ int loglik_decoder_info(const ctcd_decoder *d, LoglikDecoderInfo *out) {
 }
 void loglik_note_grid(ctcd_decoder *d, long long grid) { d->ll_grid = grid; }
 }  // namespace ctcloglik
+
+// ... and the label posteriors' (posterior.hip): the budget of their scratch, and the scratch
+namespace ctcpost {
+long long post_budget(const ctcd_decoder *d) { return d->po_budget; }
+int post_scratch(ctcd_decoder *d, size_t bytes, void **p) {
+  std::lock_guard<std::mutex> lock(d->mu);
+  if (const int rc = d->po_alpha.ensure(bytes)) return rc;
+  *p = d->po_alpha.p;
+  return CTCD_OK;
+}
+void post_note_grid(ctcd_decoder *d, long long grid) { d->po_grid = grid; }
+}  // namespace ctcpost
 
 // One audio stream's parked decoder state (ctcd_stream_*): a single HBM block [header | beam arrays | node pool].
 struct ctcd_stream {
@@ -1704,7 +1721,7 @@ void ctcd_destroy(ctcd_decoder *d) {
   d->cp_scratch.release();
   if (d->h_cp) (void)hipHostFree(d->h_cp);
   d->sk_rows.release(); d->sk_kept.release(); d->sk_lsm.release();
-  d->al_bp.release(); d->al_lsm.release();
+  d->al_bp.release(); d->al_lsm.release(); d->po_alpha.release();
   if (d->h_sk) (void)hipHostFree(d->h_sk);
   if (d->ev_sk_tab) (void)hipEventDestroy(d->ev_sk_tab);
   for (int i = 0; i < 4; ++i) if (d->ev_sk[i]) (void)hipEventDestroy(d->ev_sk[i]);
@@ -1746,6 +1763,14 @@ int ctcd_set_loglik_grid(ctcd_decoder *d, long long max_workgroups) {
   return CTCD_OK;
 }
 long long ctcd_last_loglik_grid(const ctcd_decoder *d) { return d ? d->ll_grid : -1; }
+
+// Label posteriors (posterior.hip): the budget of the scratch that keeps the forward values, and the workgroups its last call launched.
+int ctcd_set_posterior_scratch(ctcd_decoder *d, long long bytes) {
+  if (!d || bytes < 0) return fail(CTCD_EINVAL, "ctcd_set_posterior_scratch: a decoder and bytes >= 0 (0 = the default) required");
+  d->po_budget = bytes;
+  return CTCD_OK;
+}
+long long ctcd_last_posterior_grid(const ctcd_decoder *d) { return d ? d->po_grid : -1; }
 
 int ctcd_set_cu_sharing(ctcd_decoder *d, int mode) {
   if (!d || mode < -1 || mode > 1) return fail(CTCD_EINVAL, "cu sharing mode must be -1 (automatic), 0 or 1");

@@ -1,9 +1,11 @@
 // lattice_device.h -- the walk over a CTC lattice that the forced alignment (align.hip) and the log-likelihood (loglik.hip) share on
 // the device: how a hypothesis' extended sequence (align.h: S = 2L + 1 states) lies over the lanes of a wave or a workgroup and moves
 // from frame to frame (walk_row), how the rows of a launch are validated, classed in groups of four and handed out (walk_groups),
-// and which kernels a shape needs (launch_classes).  What a cell computes, what is kept of a frame and what follows the last one is
-// the user's: a policy type each.  Device code with wave intrinsics: only those two files include it; what defines a result stays
-// CTC_HD code in align.h / loglik.h, where the host twins compile it.
+// which kernels a shape needs (launch_classes), and how a unit zeroes the tail of an output row (zero_words).  The label posteriors
+// (posterior.hip) walk a row twice with it, forward and -- on the reversed labels, the frames in descending order -- backward.  What
+// a cell computes, what is kept of a frame and what follows the last one is the user's: a policy type each.  Device code with wave
+// intrinsics: only those three files include it; what defines a result stays CTC_HD code in align.h / loglik.h / posterior.h, where
+// the host twins compile it.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -15,6 +17,22 @@
 namespace ctclattice {
 
 using namespace ctcalign;
+
+typedef int i32x4 __attribute__((ext_vector_type(4)));
+
+// words [0, count) at p <- 0 by the unit's threads: single words up to the first 16-byte boundary, 16-byte stores, single words
+__device__ __forceinline__ void zero_words(int32_t *p, int count, int utid, int nt) {
+  if (count <= 0) return;
+  int head = (int)(((16u - (unsigned)((uintptr_t)p & 15u)) & 15u) >> 2);
+  if (head > count) head = count;
+  const int body = (count - head) >> 2, tail0 = head + body * 4;
+  if (utid < head) p[utid] = 0;
+  i32x4 z;
+  z.x = 0; z.y = 0; z.z = 0; z.w = 0;
+  i32x4 *q = reinterpret_cast<i32x4 *>(p + head);
+  for (int i = utid; i < body; i += nt) q[i] = z;
+  if (utid < count - tail0) p[tail0 + utid] = 0;
+}
 
 // One hypothesis on one unit: WAVES = 1 (a wave, utid = its lane) or kAlignWaves (the workgroup, utid = the thread), NPL states per
 // lane -- lane u holds states u * NPL .. u * NPL + NPL - 1 in registers, so that the neighbours s - 1 and s - 2 of all but a lane's
@@ -28,7 +46,13 @@ using namespace ctcalign;
 //   void frames_done()                                                        behind the last frame
 //   void finish(float last, float before, int L, int utid)                   with frame n - 1's states S - 1 and S - 2 (S - 2 is looked
 //                                                                            at only if L >= 1), on every thread of the unit
-template <int WAVES, int NPL, int DT, bool PROB, class P>
+// REV: the walk takes the item's frames in descending order, n - 1 first (`t` of the hooks is the frame itself; "frame t - 1" above is
+// then frame t + 1) -- on the reversed labels that is the backward recurrence (posterior.hip).  FIRST: the policy also sees the walk's
+// first frame, which no cell() computes:
+//   void first(int k, float lp, float v)                                     the lane's k-th state of the first frame: its lp, and its
+//                                                                            value v (-inf for all but the first two states)
+// followed by frame() for that frame.  Both default to what align.hip and loglik.hip were written for.
+template <int WAVES, int NPL, int DT, bool PROB, bool REV = false, bool FIRST = false, class P>
 __device__ __forceinline__ void walk_row(P &pol, const void *probs, size_t row0, int n, int V, int blank, const int32_t *tok, int L, int utid) {
   constexpr int CH = NPL == 1 ? 8 : (NPL == 4 ? 4 : 2);  // frames whose log-probabilities are in flight while a chunk is computed
   const int lane = utid & 63, wave = utid >> 6;
@@ -50,7 +74,8 @@ __device__ __forceinline__ void walk_row(P &pol, const void *probs, size_t row0,
     }
   }
   auto load = [&](float(&dst)[NPL], int t) {  // frame t's values as they lie in memory (a frame at or beyond n: frame n - 1's, unused)
-    const char *fr = (const char *)probs + (row0 + (size_t)(t < n ? t : n - 1)) * (size_t)V * kElem;
+    const int tt = t < n ? t : n - 1;
+    const char *fr = (const char *)probs + (row0 + (size_t)(REV ? n - 1 - tt : tt)) * (size_t)V * kElem;
 #pragma unroll
     for (int k = 0; k < NPL; ++k) dst[k] = ctcskip::widen_at<DT>(fr + (size_t)zo[k], 0);
   };
@@ -78,6 +103,11 @@ __device__ __forceinline__ void walk_row(P &pol, const void *probs, size_t row0,
   convert(cur[0]);
 #pragma unroll
   for (int k = 0; k < NPL; ++k) a[k] = (s0 + k < 2 && s0 + k < S) ? cur[0][k] : neg_inf();
+  if constexpr (FIRST) {
+#pragma unroll
+    for (int k = 0; k < NPL; ++k) pol.first(k, cur[0][k], a[k]);
+    pol.frame(REV ? n - 1 : 0, s0, lane);
+  }
   publish(0);
 #pragma unroll
   for (int c = 0; c < CH; ++c) load(cur[c], 1 + c);
@@ -114,7 +144,7 @@ __device__ __forceinline__ void walk_row(P &pol, const void *probs, size_t row0,
           const float p2 = k >= 2 ? a[k >= 2 ? k - 2 : 0] : (k == 1 ? a_in : b_in);
           a[k] = pol.cell(k, cur[c][k], a[k], p1, p2, (has2 >> k) & 1u);
         }
-        pol.frame(t, s0, lane);
+        pol.frame(REV ? n - 1 - t : t, s0, lane);
         publish(t & 1);
       }
     }

@@ -669,6 +669,55 @@ int ctcd_ctc_loglik(ctcd_decoder *dec, const void *probs, const int32_t *seq_len
 int ctcd_set_loglik_grid(ctcd_decoder *dec, long long max_workgroups);   /* 0 = the default */
 long long ctcd_last_loglik_grid(const ctcd_decoder *dec);
 
+/* ---- Label posteriors (no reference counterpart): CTC forward-backward for the rows a caller keeps, reduced to three numbers per
+ * label -- where the label's posterior peaks, how many frames it is expected to occupy, and how much the frames that carry it vote
+ * for it -- next to the row's log-likelihood.  One number per row cannot say which label of a transcript is shaky; these can.
+ *
+ * Definition.  n, lp(t, c), the extended sequence z, S = 2L + 1, the allowed skip, lse3 and a[t][s] are exactly those of "CTC
+ * log-likelihood".  Every operation below is one float32 operation, in the order written; all arithmetic is IEEE float32 with
+ * subnormals, and the division is correctly rounded.
+ *   ll: the result of "CTC log-likelihood".
+ *   beta:
+ *     b[n-1][S-1] = lp(n-1, blank).   b[n-1][S-2] = lp(n-1, y[L-1]) (if L >= 1).   b[n-1][s] = -inf otherwise.
+ *     b[t][s] = lp(t, z[s]) + lse3(b[t+1][s], b[t+1][s+1], b[t+1][s+2]).
+ *       The third argument is present only for odd s with s + 2 <= S - 1 and z[s+2] != z[s]; an index beyond S - 1 does not exist.
+ *     This is a of the reversed labels over the frames n-1 .. 0.
+ *   e80(x): if x > 0, x is taken as 0.  If x < -80 the value is 0.0f.  Otherwise the value is glibc's expf(x) (csrc/exact_math.h
+ *     expf_nonpos).  The cut at -80 keeps e80 itself out of the subnormal range; the clamp at 0 takes in the last-place excess that
+ *     rounding gives a + b - lp - ll.
+ *   g[t], for label i with s = 2i + 1:
+ *     g[t] = 0 if a[t][s] or b[t][s] is -inf, or their float sum is.
+ *     Otherwise g[t] = e80(((a[t][s] + b[t][s]) - lp(t, z[s])) - ll).
+ *   occupancy[i]: the float32 sum of g[t] taken in the order t = n-1, n-2, .., 0, starting from +0.0.
+ *   num[i]: the same sum of g[t] * e80(lp(t, z[s])); the product is one float32 multiplication and may be subnormal.
+ *   confidence[i] = num[i] / occupancy[i], one IEEE-rounded division; 0 if occupancy[i] == 0.  It lies in [0, 1].
+ *   peaks[i]: the smallest t whose g[t] equals the greatest.
+ * The special cases:
+ *   A row with ll == -inf, L > n or n == 0 has all per-label outputs 0; its loglik is as "CTC log-likelihood" defines it.
+ *   Every position of the per-label outputs at or beyond a row's length is written as 0.
+ *   NaN and +inf inputs are undefined.
+ * The validity rules are those of "Forced alignment": an INVALID row has all outputs 0, and the item's word of `status` is raised to
+ * CTCD_ALIGN_BAD_ROW.  Nothing is ever read through an unchecked index.
+ *
+ * ctcd_ctc_posteriors: everything is device memory and asynchronous on `stream`; nothing of `lens` is read on the host.  probs,
+ * tokens, lens and status are as for ctcd_ctc_align.  out_peaks int32, out_occupancy and out_confidence float, each
+ * [B][R][L_stride]; out_loglik float [B][R], bit for bit what ctcd_ctc_loglik writes.  log_input == 2 runs the log-softmax pass into
+ * the decoder-owned float32 rows the alignment uses too.  A row is walked twice, forward and backward; between the walks a lives in
+ * decoder-owned scratch cut into slots of max(T x (2 min(L_stride, T) + 1), T x 256) floats, rounded up to 256 bytes; min(B x R,
+ * budget / slot bytes) persistent workgroups -- at least one -- take the rows in turn, and only grid x slot bytes are allocated.
+ * The scratch belongs to the decoder's next call of this function: queue it on the same stream, or wait.  The error codes are
+ * ctcd_ctc_align's: CTCD_EINVAL for bad shapes, and nothing is launched; CTCD_EUNSUPPORTED for min(L_stride, T) > 2047, V > 2^28 or
+ * more than 2^31 - 1 rows.  B x R == 0 is CTCD_OK and launches nothing.  Streams are out of scope.
+ * ctcd_set_posterior_scratch: the budget of that scratch in bytes; 0 = the default (2 GiB: one workgroup per compute unit at
+ * T = L_stride = 1000).  The results do not depend on it.
+ * ctcd_last_posterior_grid: the workgroups the last ctcd_ctc_posteriors launched (0: none yet; -1: dec == NULL). */
+int ctcd_ctc_posteriors(ctcd_decoder *dec, const void *probs, const int32_t *seq_lens, int B, int T, int V, int blank_id, int log_input,
+                        const int32_t *tokens /* [B][R][L_stride] */, const int32_t *lens /* [B][R] */, int R, int L_stride,
+                        int32_t *out_peaks, float *out_occupancy, float *out_confidence /* [B][R][L_stride] */,
+                        float *out_loglik /* [B][R] */, int32_t *status /* [B] zeroed by the caller, or NULL */, void *stream);
+int ctcd_set_posterior_scratch(ctcd_decoder *dec, long long bytes);   /* budget of the scratch; 0 = the default */
+long long ctcd_last_posterior_grid(const ctcd_decoder *dec);
+
 /* Tuning / introspection. */
 int ctcd_set_threads(ctcd_decoder *dec, int threads_per_workgroup); /* 0 = automatic (default); else a power of two in [64, 1024] */
 /* Two workgroups per CU.  The fixed-layout class (beam <= 128, <= 32 labels) has a second build of its kernel that fits
