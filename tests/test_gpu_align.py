@@ -160,7 +160,14 @@ def test_raw_abi_refuses_bad_shapes(torch_mod):
     for kw in (dict(B=-1), dict(T=-1), dict(V=0), dict(blank=8), dict(blank=-1), dict(mode=3), dict(R=-1), dict(Ls=-1), dict(probs=None), dict(tok=None)):
         assert call(**kw) == -1, kw
     assert call(T=5000, Ls=5000, R=1) == -2, "rows beyond the states one workgroup holds are refused, not cut"
+    assert call(T=2048, Ls=2048, R=1) == -2, "min(L_stride, T) = 2048: one label more than a workgroup holds"
     assert call(B=0) == 0 and call(R=0) == 0
+    torch.cuda.synchronize()
+    # the limit itself is accepted: min(L_stride, T) = 2047 (tensors of that shape: the call launches, on one row without labels)
+    x2 = torch.zeros((1, 2048, 8), dtype=torch.float32, device="cuda")
+    t2, s2, e2 = (torch.zeros((2047,), dtype=torch.int32, device="cuda") for _ in range(3))
+    assert _native.lib.ctcd_ctc_align(dec._handle, x2.data_ptr(), None, 1, 2048, 8, 0, 1, t2.data_ptr(), lens.data_ptr(), 1, 2047, s2.data_ptr(), e2.data_ptr(),
+                                      f.data_ptr(), None, None) == 0
     torch.cuda.synchronize()
 
 

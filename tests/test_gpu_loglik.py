@@ -166,6 +166,7 @@ def test_raw_abi_refuses_bad_shapes(torch_mod):
                dict(out=None)):
         assert call(**kw) == -1, kw
     assert call(T=5000, Ls=5000, R=1) == -2, "rows beyond the states one workgroup holds are refused, not cut"
+    assert call(T=2048, Ls=2048, R=1) == -2, "min(L_stride, T) = 2048: one label more than a workgroup holds"
     assert call(V=(1 << 28) + 1) == -2
     assert call(B=0) == 0 and call(R=0) == 0
     torch.cuda.synchronize()
@@ -173,6 +174,11 @@ def test_raw_abi_refuses_bad_shapes(torch_mod):
     assert call() == 0
     torch.cuda.synchronize()
     assert (f[:2] != -123.0).all() and (f[2:] == -123.0).all()
+    # the limit itself is accepted: min(L_stride, T) = 2047 (tensors of that shape: the call launches, on one row without labels)
+    x2 = torch.zeros((1, 2048, 8), dtype=torch.float32, device="cuda")
+    t2 = torch.zeros((2047,), dtype=torch.int32, device="cuda")
+    assert call(T=2048, Ls=2047, R=1, probs=x2.data_ptr(), tok=t2.data_ptr()) == 0
+    torch.cuda.synchronize()
 
 
 def _check_invalid_row(torch, dec, c, want, what, pos, val):

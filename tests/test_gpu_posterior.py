@@ -175,6 +175,7 @@ def test_raw_abi_refuses_bad_shapes(torch_mod):
                dict(peaks=None), dict(occ=None), dict(conf=None), dict(out=None)):
         assert call(**kw) == -1, kw
     assert call(T=5000, Ls=5000, R=1) == -2, "rows beyond the states one workgroup holds are refused, not cut"
+    assert call(T=2048, Ls=2048, R=1) == -2, "min(L_stride, T) = 2048: one label more than a workgroup holds"
     assert call(V=(1 << 28) + 1) == -2
     assert call(B=0) == 0 and call(R=0) == 0
     torch.cuda.synchronize()
@@ -185,6 +186,12 @@ def test_raw_abi_refuses_bad_shapes(torch_mod):
     for o in (oc, cf):
         assert (o[:4] == 0).all() and (o[4:] == -123.0).all(), "two empty rows of stride 2: zero tails, and nothing beyond them"
     assert (pk[:4] == 0).all() and (pk[4:] == 0x5A5A5A5A).all()
+    # the limit itself is accepted: min(L_stride, T) = 2047 (tensors of that shape: the call launches, on one row without labels)
+    x2 = torch.zeros((1, 2048, 8), dtype=torch.float32, device="cuda")
+    t2, p2 = (torch.zeros((2047,), dtype=torch.int32, device="cuda") for _ in range(2))
+    o2, c2 = (torch.zeros((2047,), dtype=torch.float32, device="cuda") for _ in range(2))
+    assert call(T=2048, Ls=2047, R=1, probs=x2.data_ptr(), tok=t2.data_ptr(), peaks=p2.data_ptr(), occ=o2.data_ptr(), conf=c2.data_ptr()) == 0
+    torch.cuda.synchronize()
 
 
 def _check_invalid_row(torch, dec, c, want, what, pos, val):
