@@ -876,6 +876,51 @@ class CTCBeamDecoder(object):
         """Test hook: the workgroups the last ``label_posteriors`` launched."""
         return int(_native.lib.ctcd_last_posterior_grid(self._handle))
 
+    def greedy_decode_device(self, probs, seq_lens=None, details=False):
+        """Greedy (best-path) CTC decoding on the device (include/ctcdecode_amd.h "Greedy decode"): every frame's most probable label,
+        repeats collapsed, blanks dropped, in one read of ``probs``.  Returns ``(beam_results [B, 1, T] int32, scores [B, 1] float32,
+        timesteps [B, 1, T] int32, out_lens [B, 1] int32)`` in HBM on the decoder's device, asynchronous on the current stream -- the
+        order and dtypes of ``decode_device``, so the result goes straight into ``align``, ``log_likelihood`` and ``label_posteriors``.
+        ``timesteps[b, 0, i]`` is the frame that emits label ``i``; positions at or beyond ``out_lens`` are 0.  ``scores`` is the path's
+        log-probability, the float32 sum of the winners' values in frame order: the sign and the bits of ``align``'s score for that row,
+        not the sign convention of ``decode``'s ``beam_scores``.  With ``details=True`` two more tensors follow: ``ends`` int32
+        [B, 1, T], the last frame of each label's run, and ``label_scores`` float32 [B, 1, T], the greatest log-probability over it.
+
+        Follows the decoder's ``blank_id`` and input mode (raw logits are normalised per frame without a copy of the input); half
+        dtypes on the device are read as they are.  No language model, no ``cutoff_top_n`` / ``cutoff_prob`` and no ``blank_skip`` take
+        part."""
+        if probs.dim() != 3:
+            raise ValueError("probs must be [batch, time, labels]")
+        probs = _input_rows(self, probs)
+        B, T, V = probs.shape
+        if V != self._num_labels:
+            raise ValueError("probs.shape[2] (%d) does not match the number of labels (%d)" % (V, self._num_labels))
+        if not 0 <= int(self._blank_id) < V:
+            raise ValueError("ctcdecode_amd: blank_id must index the vocabulary")
+        if seq_lens is not None:
+            seq_lens = seq_lens.to(device=self._device, dtype=torch.int32).contiguous()
+            if seq_lens.numel() != B:
+                raise ValueError("seq_lens must have one entry per batch item")
+        with torch.cuda.device(self._device):
+            tokens = torch.empty((B, 1, T), dtype=torch.int32, device=self._device)
+            starts = torch.empty((B, 1, T), dtype=torch.int32, device=self._device)
+            ends = torch.empty((B, 1, T), dtype=torch.int32, device=self._device) if details else None
+            label_scores = torch.empty((B, 1, T), dtype=torch.float32, device=self._device) if details else None
+            scores = torch.empty((B, 1), dtype=torch.float32, device=self._device)
+            out_lens = torch.empty((B, 1), dtype=torch.int32, device=self._device)
+            stream = torch.cuda.current_stream(self._device).cuda_stream
+            _native.check(_native.lib.ctcd_greedy_decode(
+                self._handle, probs.data_ptr(), seq_lens.data_ptr() if seq_lens is not None else None, B, T, V, int(self._blank_id), self._log_probs,
+                tokens.data_ptr(), starts.data_ptr(), ends.data_ptr() if details else None, label_scores.data_ptr() if details else None,
+                scores.data_ptr(), out_lens.data_ptr(), stream))
+        return (tokens, scores, starts, out_lens, ends, label_scores) if details else (tokens, scores, starts, out_lens)
+
+    def greedy_decode(self, probs, seq_lens=None):
+        """``greedy_decode_device`` with the four tensors on the CPU: ``(beam_results [B, 1, T], scores [B, 1], timesteps [B, 1, T],
+        out_lens [B, 1])``, the order and dtypes of ``decode``."""
+        outs = self.greedy_decode_device(probs, seq_lens)
+        return tuple(o.cpu() for o in outs) if outs[0].numel() == 0 else tuple(_to_host(outs))
+
     def decode_padded(self, probs, seq_lens=None, n_best=None):
         """The same call with the padded [B, K, T] tensors crossing PCIe (the delivery of round 1; kept for comparison); with ``n_best``
         the [B, n, T] ones."""

@@ -36,7 +36,8 @@ SYMBOLS = ["ctcd_log_softmax", "ctcd_compact_label_capacity", "ctcd_beam_decode_
            "ctcd_expand_compact_nbest", "ctcd_beam_decode_nbest", "ctcd_beam_decode_to_host_nbest",
            "ctcd_ctc_align", "ctcd_set_align_scratch", "ctcd_last_align_grid",
            "ctcd_ctc_loglik", "ctcd_set_loglik_grid", "ctcd_last_loglik_grid",
-           "ctcd_ctc_posteriors", "ctcd_set_posterior_scratch", "ctcd_last_posterior_grid"]
+           "ctcd_ctc_posteriors", "ctcd_set_posterior_scratch", "ctcd_last_posterior_grid",
+           "ctcd_greedy_decode"]
 
 
 def _load():
@@ -194,6 +195,9 @@ def _load():
     lib.ctcd_set_posterior_scratch.argtypes = [ctypes.c_void_p, ctypes.c_longlong]
     lib.ctcd_last_posterior_grid.argtypes = [ctypes.c_void_p]
     lib.ctcd_last_posterior_grid.restype = ctypes.c_longlong
+    # greedy decode (greedy.hip): dec, probs, seq_lens, B, T, V, blank_id, log_input, out_tokens, out_starts, out_ends, out_label_scores,
+    # out_scores, out_lens, stream
+    lib.ctcd_greedy_decode.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_int] * 5 + [ctypes.c_void_p] * 7
     return lib
 
 

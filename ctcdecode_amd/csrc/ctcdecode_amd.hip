@@ -40,6 +40,8 @@
 #include "align.h"
 #include "loglik.h"
 #include "posterior.h"
+#include "greedy.h"
+#include "lsm_device.h"
 
 namespace {
 
@@ -178,56 +180,11 @@ __global__ void __launch_bounds__(256) log_softmax_rows_kernel(const float *in_,
 
 // The same normalisation for long rows, shaped for HBM bandwidth: one workgroup of four waves per frame, the row read ONCE
 // with 128-bit loads and held in registers (thread t: the float4s t, t + 256, ...), written once.  The sum keeps the order
-// the definition fixes -- 64 chains, chain l over the terms j = l, l + 64, ... in increasing j -- although no thread holds a
-// chain's terms: the exponentials of 1024 consecutive labels at a time go to LDS (every thread computes four), and one wave
-// per such chunk (the four take turns) extends the 64 chains by sixteen terms each, lane l reading its chain's terms at
-// l + 64 k.  Two chunk buffers, one barrier per chunk; the chains' running values pass from wave to wave through LDS.
-// Requires V % 4 == 0 and V <= 1024 * F4.
-constexpr int kLsmChunk = 1024;  // labels per chunk of exponentials (four per thread)
-struct LsmLds {
-  float terms[2][kLsmChunk];
-  float chain[64];
-  float wmax[4];
-};
-template <int F4>
-__device__ __forceinline__ float wg_exp_sum(const float4 (&v)[F4], int nv4, float m, LsmLds &s, const uint64_t *tbl, int tid) {
-  const int lane = tid & 63, wave = tid >> 6;
-#pragma unroll
-  for (int u = 0; u < F4; ++u) {
-    if (256 * u < nv4) {  // (uniform; chunks past the row's end would add zeros)
-      float4 e = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-      if (tid + 256 * u < nv4) {
-        // (two at a time: four interleaved binary64 evaluations on top of the row cost registers -- the other waves hide the latency)
-        e.x = ctcmath::expf_nonpos(v[u].x - m, tbl); e.y = ctcmath::expf_nonpos(v[u].y - m, tbl);
-        __builtin_amdgcn_sched_barrier(0);
-        e.z = ctcmath::expf_nonpos(v[u].z - m, tbl); e.w = ctcmath::expf_nonpos(v[u].w - m, tbl);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-      *reinterpret_cast<float4 *>(&s.terms[u & 1][4 * tid]) = e;
-      __syncthreads();
-      if (wave == (u & 3)) {
-        float p = u ? s.chain[lane] : 0.0f;
-        const float *c = &s.terms[u & 1][lane];
-#pragma unroll
-        for (int k = 0; k < kLsmChunk / 64; ++k) p += c[64 * k];
-        s.chain[lane] = p;
-      }
-    }
-  }
-  __syncthreads();
-  float part = s.chain[lane];
-  for (int off = 1; off < 64; off <<= 1) part += __shfl_xor(part, off, 64);
-  return part;
-}
-// the row's maximum (NaN-ignoring, as the one-wave kernel's), known to every thread; contains one barrier
-__device__ __forceinline__ float wg_row_max(float mine, LsmLds &s, int tid) {
-  for (int off = 1; off < 64; off <<= 1) { const float o = __shfl_xor(mine, off, 64); mine = o > mine ? o : mine; }
-  if ((tid & 63) == 0) s.wmax[tid >> 6] = mine;
-  __syncthreads();
-  float m = s.wmax[0];
-  m = s.wmax[1] > m ? s.wmax[1] : m; m = s.wmax[2] > m ? s.wmax[2] : m; m = s.wmax[3] > m ? s.wmax[3] : m;
-  return m + 0.0f;  // (a zero maximum is +0 whichever zero the reduction met first: part of the definition)
-}
+// the definition fixes; lsm_device.h has the helpers that see to it (wg_row_max, wg_exp_sum, LsmLds), shared with the greedy
+// decode's logit kernel (greedy.hip).  Requires V % 4 == 0 and V <= 1024 * F4.
+using ctclsm::LsmLds;
+using ctclsm::wg_exp_sum;
+using ctclsm::wg_row_max;
 template <int F4, int DT>
 __global__ void __launch_bounds__(256, F4 <= 10 ? 5 : 4) log_softmax_rows_wg_kernel(const float *in_, float *out, long long rows, const int32_t *seq_lens, int T,
                                                                                      int V, const uint64_t *tables) {
@@ -1412,6 +1369,8 @@ struct ctcd_decoder {
   // (ctcd_set_posterior_scratch; 0 = the default) and the grid of the last call (ctcd_last_posterior_grid)
   Buf po_alpha;
   long long po_budget = 0, po_grid = 0;
+  // ctcd_greedy_decode (greedy.h): the frame records its argmax pass leaves its collapse pass
+  Buf gr_frames;
   std::mutex mu;
   std::mutex mu_host;  // the host-tensor entry points: compact buffers, page-locked staging and the worker threads are per decoder
 };
@@ -1487,6 +1446,16 @@ int post_scratch(ctcd_decoder *d, size_t bytes, void **p) {
 }
 void post_note_grid(ctcd_decoder *d, long long grid) { d->po_grid = grid; }
 }  // namespace ctcpost
+
+// ... and the greedy decode's (greedy.hip), beyond the alignment's hooks: its frame records
+namespace ctcgreedy {
+int greedy_scratch(ctcd_decoder *d, size_t bytes, void **p) {
+  std::lock_guard<std::mutex> lock(d->mu);
+  if (const int rc = d->gr_frames.ensure(bytes)) return rc;
+  *p = d->gr_frames.p;
+  return CTCD_OK;
+}
+}  // namespace ctcgreedy
 
 // One audio stream's parked decoder state (ctcd_stream_*): a single HBM block [header | beam arrays | node pool].
 struct ctcd_stream {
@@ -1721,7 +1690,7 @@ void ctcd_destroy(ctcd_decoder *d) {
   d->cp_scratch.release();
   if (d->h_cp) (void)hipHostFree(d->h_cp);
   d->sk_rows.release(); d->sk_kept.release(); d->sk_lsm.release();
-  d->al_bp.release(); d->al_lsm.release(); d->po_alpha.release();
+  d->al_bp.release(); d->al_lsm.release(); d->po_alpha.release(); d->gr_frames.release();
   if (d->h_sk) (void)hipHostFree(d->h_sk);
   if (d->ev_sk_tab) (void)hipEventDestroy(d->ev_sk_tab);
   for (int i = 0; i < 4; ++i) if (d->ev_sk[i]) (void)hipEventDestroy(d->ev_sk[i]);

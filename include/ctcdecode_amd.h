@@ -718,6 +718,51 @@ int ctcd_ctc_posteriors(ctcd_decoder *dec, const void *probs, const int32_t *seq
 int ctcd_set_posterior_scratch(ctcd_decoder *dec, long long bytes);   /* budget of the scratch; 0 = the default */
 long long ctcd_last_posterior_grid(const ctcd_decoder *dec);
 
+/* ---- Greedy decode (no reference counterpart; the reference's test file defines a greedy_result it never uses): the best-path
+ * decode -- every frame's most probable label, repeats collapsed, blanks dropped -- in one read of the input.  No beam, no language
+ * model, no vocabulary prune and no blank-frame filter take part.
+ *
+ * Definition.  For item b: n = clamp(seq_lens[b], 0, T) (T when seq_lens is NULL).  x(t, c) is the input value of label c at frame
+ * t, a half value widened exactly.  lp(t, c) is exactly the lp of "Forced alignment" for log_input 0, 1 and 2.
+ * The frame label:
+ *   c*(t) is the index of the greatest x(t, .).  The compare is an ordered, strict `>` walked from c = 0: among equal values the
+ *   smallest index wins, -0.0 and +0.0 are equal, and a frame of all -inf gives 0.
+ *   This holds in all three input modes: the winner is chosen on the input values, not on lp.
+ *   NaN inputs are undefined, as elsewhere.  Nothing is read or written out of bounds because of one.
+ * The emission:
+ *   Frame t < n emits label c*(t) iff c*(t) != blank_id and (t == 0 or c*(t) != c*(t-1)).
+ *   The emitted labels in frame order are tokens[0..L).  starts[i] is the emitting frame.  ends[i] is the last frame of that run of
+ *   equal c*.
+ *   label_scores[i] is the greatest lp(t, c*(t)) over starts[i] .. ends[i].  The maximum is exact and involves no arithmetic; where
+ *   -0.0 and +0.0 are both the greatest, it is the one of the earlier frame.
+ * The score:
+ *   n == 0: score 0 and L = 0.
+ *   Otherwise score = lp(0, c*(0)), then score = score + lp(t, c*(t)) for t = 1 .. n-1 in that order.  Each step is one float32
+ *   addition.  The sign is that of ctcd_ctc_align's score (a log-probability), not the sign convention of a decode's out_scores.
+ * lp(t, c*(t)) by mode:
+ *   log_input == 1: x(t, c*(t)).
+ *   log_input == 0: float(log(double(p) + FLT_MIN)) of the winner only.
+ *   log_input == 2: the value ctcd_log_softmax would write there.  With the frame's NaN-skipping maximum m (a zero maximum taken as
+ *   +0) that is (x - m) - logf(s), the sum s taken in the order that function's definition fixes: 64 chains j mod 64 in increasing j,
+ *   then the butterfly.  For m = -inf it is -inf.  No [B][T][V] copy of the input is written.
+ * Every output position at or beyond L is written as 0.
+ * What follows: float32 addition is monotone in both arguments and c*(t) carries the greatest lp of its frame, so no path sums to
+ * more than the greedy one -- ctcd_ctc_align of the greedy row returns a score with equal bits (log_input 1 and 2; log_input 0 as far
+ * as the restated binary64 log is monotone).
+ *
+ * ctcd_greedy_decode: everything is device memory and asynchronous on `stream`; nothing is read on the host.  probs [B][T][V] has the
+ * dtype ctcd_set_input_dtype set.  out_tokens, out_starts int32 [B][T]; out_ends int32 [B][T] and out_label_scores float [B][T], or
+ * NULL each; out_scores float [B], out_lens int32 [B].  out_tokens / out_lens are rows ctcd_ctc_align, ctcd_ctc_loglik and
+ * ctcd_ctc_posteriors take with R = 1, L_stride = T.  Two kernels run behind each other: an argmax pass that leaves c*(t) and
+ * lp(t, c*(t)) of every frame below n in decoder-owned scratch (8 bytes per frame), and a collapse pass, one workgroup per item.  The
+ * scratch belongs to the decoder's next greedy decode: queue that call on the same stream, or wait.  A decoder built with a scorer
+ * ignores it.  CTCD_EINVAL for bad shapes (negative sizes, V < 1, blank_id outside [0, V), log_input outside 0 .. 2, a NULL tensor),
+ * and nothing is launched.  CTCD_EUNSUPPORTED for V > 2^28.  B == 0 is CTCD_OK and launches nothing; T == 0 with B > 0 writes
+ * out_lens and out_scores as zeros.  Streams, more than one row per item and host pointers are out of scope. */
+int ctcd_greedy_decode(ctcd_decoder *dec, const void *probs, const int32_t *seq_lens, int B, int T, int V, int blank_id, int log_input,
+                       int32_t *out_tokens, int32_t *out_starts /* [B][T] */, int32_t *out_ends, float *out_label_scores /* [B][T] or NULL */,
+                       float *out_scores, int32_t *out_lens /* [B] */, void *stream);
+
 /* Tuning / introspection. */
 int ctcd_set_threads(ctcd_decoder *dec, int threads_per_workgroup); /* 0 = automatic (default); else a power of two in [64, 1024] */
 /* Two workgroups per CU.  The fixed-layout class (beam <= 128, <= 32 labels) has a second build of its kernel that fits
