@@ -1,7 +1,7 @@
 // lsm_device.h -- the workgroup helpers that give a long row's log-softmax the summation order ctcd_log_softmax defines
 // (include/ctcdecode_amd.h): the row's maximum and the sum of its exponentials over 64 chains, for a row that a workgroup of four waves
 // holds in registers (thread t: the float4s t, t + 256, ...).  Device code with barriers and wave intrinsics, shared by the kernels that
-// hold a row that way: log_softmax_rows_wg_kernel and prune_logits_wg_kernel (ctcdecode_amd.hip) and the greedy decode's logit kernel
+// hold a row that way: log_softmax_rows_wg_kernel and prune_logits_wg_kernel (prepass.hip) and the greedy decode's logit kernel
 // (greedy.hip).
 #pragma once
 #include <hip/hip_runtime.h>

@@ -258,7 +258,7 @@ static int decode_impl(const float *probs, const int32_t *seq_lens, int B, int T
                        int32_t *out_timesteps, float *out_scores, int32_t *out_lens, int32_t *n_results,
                        const ctclm::LmView *lm, const float *raw, int raw_log);
 
-// Host twin of the product's log_softmax pre-pass (ctcdecode_amd.hip log_softmax_rows_kernel; input mode 2 / ctcd_log_softmax):
+// Host twin of the product's log_softmax pre-pass (prepass.hip log_softmax_rows_kernel; input mode 2 / ctcd_log_softmax):
 // the same float32 operations in the same order, with the C library's expf / logf.
 // event statistics since the process started (or since the last call with reset != 0): out[ctcbeam::EV_COUNT].  Decodes that run on
 // several host threads add up racily -- use num_threads = 1 for exact counts.

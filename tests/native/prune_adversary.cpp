@@ -1,4 +1,4 @@
-// Adversarial rows for the vocabulary prune's std::sort replay (ctcdecode_amd.hip prune_resolve_kernel ->
+// Adversarial rows for the vocabulary prune's std::sort replay (prepass.hip prune_resolve_kernel ->
 // stl_emul.h sort_prefix_parallel), and a certificate of what such a row makes the replay do.  TEST INFRASTRUCTURE ONLY.
 //
 //   * Generator: McIlroy's "A Killer Adversary for Quicksort" (1999), played against the live std::sort under the descending
@@ -31,7 +31,7 @@ struct Adversary {
   }
 };
 
-// the order of the doubles the reference compares (ctcdecode_amd.hip prune_key): -0 == +0, NaN below every number
+// the order of the doubles the reference compares (prepass.hip prune_key): -0 == +0, NaN below every number
 uint32_t key_of_float(float f) {
   uint32_t u;
   std::memcpy(&u, &f, 4);

@@ -1,4 +1,4 @@
-"""One case per pre-pass kernel instantiation of ctcdecode_amd/csrc/ctcdecode_amd.hip (the table ctcd_debug_prepass_table reports), plus
+"""One case per pre-pass kernel instantiation of ctcdecode_amd/csrc/prepass.hip (the table ctcd_debug_prepass_table reports), plus
 the global-memory route of prune_resolve_kernel for each input dtype: 89 cases.  Each names the instantiation it is for (``target``),
 the decoder arguments and switches that select it, and an input recipe.  Shared by the CPU coverage check (test_abi.py: the targets
 equal the build's table exactly) and the GPU tests (test_gpu_prepass_matrix.py).  No torch here: the CPU suite imports this module.
@@ -93,7 +93,7 @@ def pruned(c):
 
 
 def resolve_lds_bytes(V, n):
-    """ctcdecode_amd.hip prune_resolve_lds_bytes."""
+    """prepass.h prune_resolve_lds_bytes."""
     cap = V // 17 + 2
     return V * 8 + 2 * (V + 2) * 2 + 6 * cap * 2 + 2 * (V // 2 + 1) * 2 + 3 * 64 * 4 + 64 + n * 4 + 64
 

@@ -19,7 +19,7 @@ import numpy as np
 import oracle_util as ou
 
 B, T, K = 2, 6, 8
-BIG_CUT = 256       # ctcdecode_amd.hip kResolveBigCut
+BIG_CUT = 256       # prepass.hip kResolveBigCut
 BSTACK_SLOTS = 64   # stl_emul.h sort_prefix_parallel: bstack holds 3 * 64 ints
 SEQ_LENS = np.array([T, T - 1], np.int32)
 LOGIT_SHIFTS = (4, 5, 6, 7, 8)

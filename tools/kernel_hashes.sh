@@ -1,7 +1,7 @@
 #!/bin/bash
 # A hash of the machine code of every kernel in the built library (or in the library given as $1): "this change leaves the north-star
 # kernel as it was" is checked, not assumed.   usage: bash tools/kernel_hashes.sh [lib.so] | grep "1024, 0, false"
-# KERNELS=all: every kernel of the library (the pre-pass kernels of ctcdecode_amd.hip too), the "..." lines of zero padding between
+# KERNELS=all: every kernel of the library (the pre-pass kernels of prepass.hip and the kernels of every feature's unit too), the "..." lines of zero padding between
 # functions, the "// address: encoding" comments and the s_nop padding at the end of the code object left out (they follow the layout
 # of the code object, not a kernel's code); full names.
 set -e
