@@ -15,7 +15,7 @@ import torch
 from . import _native
 from ._native import NativeError  # noqa: F401
 
-__all__ = ["CTCBeamDecoder", "OnlineCTCBeamDecoder", "DecoderState", "NativeError", "CallbackScorer", "KenlmScorer", "DecodePipeline", "snapshot_info"]
+__all__ = ["CTCBeamDecoder", "OnlineCTCBeamDecoder", "DecoderState", "GreedyState", "NativeError", "CallbackScorer", "KenlmScorer", "DecodePipeline", "snapshot_info"]
 HAVE_LM = True  # the external-scorer tier (model_path / alpha / beta) is part of this build
 
 
@@ -1391,6 +1391,80 @@ class OnlineCTCBeamDecoder(object):
         L = int(out_len_c.max()) if B and R else 0
         return _to_host((output[:, :R, :L].contiguous(), scores, timesteps[:, :R, :L].contiguous(), out_len))
 
+    def greedy_decode_device(self, probs, states, is_eos_s, seq_lens=None, details=False):
+        """Greedy (best-path) decoding of live streams on the device (extension; include/ctcdecode_amd.h "Greedy decode of live streams"):
+        feeds the chunk ``probs[b, :seq_lens[b]]`` to the ``GreedyState`` ``states[b]`` and returns the labels whose emitting frame lies in
+        the chunk -- final labels: best-path decoding never revises one.  However a stream's frames are cut into chunks, its calls return,
+        concatenated, what ``CTCBeamDecoder.greedy_decode_device`` returns for all its frames together, bit for bit.
+
+        Returns ``(tokens [B, 1, Tc] int32, scores [B, 1] float32, timesteps [B, 1, Tc] int32, out_lens [B, 1] int32)`` in HBM on the
+        decoder's device, asynchronous on the current stream; nothing is read on the host.  ``timesteps`` count frames from the stream's
+        ``first_frame``; ``scores`` is the score of all frames so far, this chunk included (0 for a stream that never had a frame).  With
+        ``details=True`` three more tensors follow: ``ends`` int32 [B, 1, Tc + 1] and ``label_scores`` float32 [B, 1, Tc + 1] of the runs
+        whose last frame became known in this call -- a run that reaches the chunk's last frame of a stream that goes on is reported by
+        a later call -- and ``closed_lens`` int32 [B, 1], their count; over a stream's life the i-th closed run is the i-th label's.
+        Positions at or beyond a count are 0.
+
+        ``is_eos_s[b]`` ends stream ``b`` with this chunk (an empty chunk too); an ended state raises ``ValueError`` until it is
+        ``reset()``.  Follows the decoder's ``blank_id`` and input mode; half dtypes on the device are read as they are.  No language
+        model, no ``cutoff_top_n`` / ``cutoff_prob`` and no blank filter take part; the beam streams (``DecoderState``) are untouched."""
+        if probs.dim() != 3:
+            raise ValueError("probs must be [batch, time, labels]")
+        probs = _input_rows(self, probs)
+        B, T, V = probs.shape
+        if V != self._num_labels:
+            raise ValueError("probs.shape[2] (%d) does not match the number of labels (%d)" % (V, self._num_labels))
+        if not 0 <= int(self._blank_id) < V:
+            raise ValueError("ctcdecode_amd: blank_id must index the vocabulary")
+        if len(states) != B or len(is_eos_s) != B:
+            raise ValueError("states and is_eos_s need one entry per batch item")
+        # (a serving loop calls this once per chunk with the same states: the list is looked at, and the array of handles rebuilt, only
+        #  when it changes -- weak references, as in ``decode``; an ended or a duplicate state is refused by the library itself)
+        cache = getattr(self, "_greedy_ptr_cache", None)
+        if cache is None or len(cache[0]) != B or any(r() is not st for r, st in zip(cache[0], states)):
+            if len(set(id(st) for st in states)) != B:
+                raise ValueError("the same GreedyState twice in one call")
+            for st in states:
+                if not isinstance(st, GreedyState):
+                    raise ValueError("greedy_decode takes GreedyState objects (DecoderState belongs to decode)")
+                if st._device != self._device:
+                    raise ValueError("GreedyState of device %s used with a decoder of device %s" % (st._device, self._device))
+                if st.ended:
+                    raise ValueError("GreedyState has ended: reset() it before it is fed again")
+            cache = ([weakref.ref(st) for st in states], (ctypes.c_void_p * max(B, 1))(*[st._handle.value for st in states]))
+            self._greedy_ptr_cache = cache
+        ptrs = cache[1]
+        if seq_lens is not None:
+            seq_lens = seq_lens.to(device=self._device, dtype=torch.int32).contiguous()
+            if seq_lens.numel() != B:
+                raise ValueError("seq_lens must have one entry per batch item")
+        any_eos = any(is_eos_s)
+        eos = (ctypes.c_ubyte * max(B, 1)).from_buffer_copy(bytes(bytearray(1 if e else 0 for e in is_eos_s)) or b"\0")
+        with torch.cuda.device(self._device):
+            tokens = torch.empty((B, 1, T), dtype=torch.int32, device=self._device)
+            starts = torch.empty((B, 1, T), dtype=torch.int32, device=self._device)
+            ends = torch.empty((B, 1, T + 1), dtype=torch.int32, device=self._device) if details else None
+            label_scores = torch.empty((B, 1, T + 1), dtype=torch.float32, device=self._device) if details else None
+            closed_lens = torch.empty((B, 1), dtype=torch.int32, device=self._device) if details else None
+            scores = torch.empty((B, 1), dtype=torch.float32, device=self._device)
+            out_lens = torch.empty((B, 1), dtype=torch.int32, device=self._device)
+            stream = torch.cuda.current_stream(self._device).cuda_stream
+            _native.check(_native.lib.ctcd_greedy_stream_decode(
+                self._handle, ptrs, eos, probs.data_ptr(), seq_lens.data_ptr() if seq_lens is not None else None, B, T, V, int(self._blank_id),
+                self._log_probs, tokens.data_ptr(), starts.data_ptr(), ends.data_ptr() if details else None,
+                label_scores.data_ptr() if details else None, closed_lens.data_ptr() if details else None, scores.data_ptr(), out_lens.data_ptr(), stream))
+        if any_eos:
+            for st, e in zip(states, is_eos_s):
+                if e:
+                    st._ended = True
+            self._greedy_ptr_cache = None  # (ended streams are not fed again: the next call brings other states)
+        return (tokens, scores, starts, out_lens, ends, label_scores, closed_lens) if details else (tokens, scores, starts, out_lens)
+
+    def greedy_decode(self, probs, states, is_eos_s, seq_lens=None, details=False):
+        """``greedy_decode_device`` with its tensors on the CPU."""
+        outs = self.greedy_decode_device(probs, states, is_eos_s, seq_lens, details)
+        return tuple(o.cpu() for o in outs) if any(o.numel() == 0 for o in outs) else tuple(_to_host(outs))
+
     def peek(self, states, n_best=1, since=None):
         """Interim results of live streams (extension; the reference reports nothing before ``is_eos``): what the streams' one-shot
         decode of the frames fed so far returns, without feeding a frame and without disturbing the streams.
@@ -1682,3 +1756,48 @@ class DecoderState(object):
             except Exception:
                 pass
             self.state = None
+
+
+class GreedyState(object):
+    """State of one audio stream under greedy (best-path) decoding (extension; ``OnlineCTCBeamDecoder.greedy_decode`` /
+    ``greedy_decode_device``): 32 bytes on the decoder's device -- the frames fed, the last frame's label, the open run's maximum, the
+    running score, the counts.  ``first_frame``: the number reported for the stream's first frame (``timesteps`` and ``ends`` count from
+    it); a stream's frame numbers stay below 2**31 - 1 (``NotImplementedError`` from the call that would pass it).  Not reusable after
+    its stream ended, until ``reset()``."""
+
+    def __init__(self, decoder, first_frame=0):
+        self._decoder = decoder
+        self._device = decoder._device
+        self._ended = False
+        h = ctypes.c_void_p()
+        _native.check(_native.lib.ctcd_greedy_stream_create(decoder._handle, ctypes.byref(h), int(first_frame)))
+        self._handle = h
+
+    def reset(self, first_frame=0):
+        """A fresh stream again (queued on the current stream of the state's device)."""
+        with torch.cuda.device(self._device):
+            stream = torch.cuda.current_stream(self._device).cuda_stream
+            _native.check(_native.lib.ctcd_greedy_stream_reset(self._decoder._handle, self._handle, int(first_frame), stream))
+        self._ended = False
+
+    @property
+    def ended(self):
+        """True once a call has fed the stream with ``is_eos`` set."""
+        return self._ended
+
+    def info(self):
+        """Waits for the device: ``dict(frames, emitted, closed, open_run)`` -- frames fed, labels emitted, runs closed so far, and
+        whether a run is open (its label emitted, its last frame not yet known)."""
+        out = (ctypes.c_longlong * 4)()
+        _native.check(_native.lib.ctcd_greedy_stream_info(self._decoder._handle, self._handle, out))
+        return dict(frames=int(out[0]), emitted=int(out[1]), closed=int(out[2]), open_run=bool(out[3]))
+
+    def __del__(self):
+        h = getattr(self, "_handle", None)
+        d = getattr(self, "_decoder", None)
+        if h is not None and h.value and d is not None and getattr(d, "_handle", None) is not None:
+            try:
+                _native.destroy(_native.lib.ctcd_greedy_stream_destroy, d._handle, h)
+            except Exception:
+                pass
+            self._handle = None

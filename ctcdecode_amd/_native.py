@@ -37,7 +37,8 @@ SYMBOLS = ["ctcd_log_softmax", "ctcd_compact_label_capacity", "ctcd_beam_decode_
            "ctcd_ctc_align", "ctcd_set_align_scratch", "ctcd_last_align_grid",
            "ctcd_ctc_loglik", "ctcd_set_loglik_grid", "ctcd_last_loglik_grid",
            "ctcd_ctc_posteriors", "ctcd_set_posterior_scratch", "ctcd_last_posterior_grid",
-           "ctcd_greedy_decode"]
+           "ctcd_greedy_decode",
+           "ctcd_greedy_stream_create", "ctcd_greedy_stream_destroy", "ctcd_greedy_stream_reset", "ctcd_greedy_stream_decode", "ctcd_greedy_stream_info"]
 
 
 def _load():
@@ -198,6 +199,14 @@ def _load():
     # greedy decode (greedy.hip): dec, probs, seq_lens, B, T, V, blank_id, log_input, out_tokens, out_starts, out_ends, out_label_scores,
     # out_scores, out_lens, stream
     lib.ctcd_greedy_decode.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_int] * 5 + [ctypes.c_void_p] * 7
+    # greedy decode of live streams (greedy_stream.hip).  decode: dec, states, is_eos, probs, seq_lens, B, Tc, V, blank_id, log_input,
+    # out_tokens, out_starts, out_ends, out_label_scores, out_closed_lens, out_scores, out_lens, stream
+    lib.ctcd_greedy_stream_create.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.c_longlong]
+    lib.ctcd_greedy_stream_destroy.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+    lib.ctcd_greedy_stream_destroy.restype = None
+    lib.ctcd_greedy_stream_reset.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p]
+    lib.ctcd_greedy_stream_decode.argtypes = [ctypes.c_void_p] * 5 + [ctypes.c_int] * 5 + [ctypes.c_void_p] * 8
+    lib.ctcd_greedy_stream_info.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_longlong)]
     return lib
 
 

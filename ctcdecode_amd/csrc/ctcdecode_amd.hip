@@ -351,6 +351,13 @@ struct ctcd_decoder {
   long long po_budget = 0, po_grid = 0;
   // ctcd_greedy_decode (greedy.h): the frame records its argmax pass leaves its collapse pass
   Buf gr_frames;
+  // ctcd_greedy_stream_decode (greedy.h "live streams"): a chunk call's per-stream arguments travel like ctcd_stream_decode's (two
+  // page-locked slots, an event each, one copy per call)
+  Buf gs_args;
+  char *h_gsargs[2] = {nullptr, nullptr};
+  size_t h_gsargs_cap = 0;
+  hipEvent_t ev_gsargs[2] = {nullptr, nullptr};
+  unsigned long long gs_calls = 0;
   std::mutex mu;
   std::mutex mu_host;  // the host-tensor entry points: compact buffers, page-locked staging and the worker threads are per decoder
 };
@@ -433,6 +440,33 @@ int greedy_scratch(ctcd_decoder *d, size_t bytes, void **p) {
   std::lock_guard<std::mutex> lock(d->mu);
   if (const int rc = d->gr_frames.ensure(bytes)) return rc;
   *p = d->gr_frames.p;
+  return CTCD_OK;
+}
+// ... and its streams' (greedy_stream.hip): a chunk call's per-stream arguments, staged in page-locked memory and sent with ONE
+// asynchronous copy, as ctcd_stream_decode sends its own
+int greedy_stream_upload(ctcd_decoder *d, const void *src, size_t bytes, void *stream, void **dev) {
+  std::lock_guard<std::mutex> lock(d->mu);
+  const size_t need = (bytes + 255) & ~(size_t)255;
+  if (const int rc = d->gs_args.ensure(2 * need)) return rc;
+  if (d->h_gsargs_cap < need) {
+    for (int i = 0; i < 2; ++i) {
+      if (d->ev_gsargs[i]) HIP_TRY(hipEventSynchronize(d->ev_gsargs[i]));
+      if (d->h_gsargs[i]) (void)hipHostFree(d->h_gsargs[i]);
+      d->h_gsargs[i] = nullptr;
+      d->h_gsargs_cap = 0;
+      HIP_TRY(hipHostMalloc((void **)&d->h_gsargs[i], need, hipHostMallocDefault));
+      if (!d->ev_gsargs[i]) HIP_TRY(hipEventCreateWithFlags(&d->ev_gsargs[i], hipEventDisableTiming));
+    }
+    d->h_gsargs_cap = need;
+  }
+  const int slot = (int)(d->gs_calls++ & 1);
+  HIP_TRY(hipEventSynchronize(d->ev_gsargs[slot]));  // (the copy of two calls ago: long done)
+  memcpy(d->h_gsargs[slot], src, bytes);
+  // (the slots' offsets follow the capacity of the page-locked end, which only grows with the device end)
+  char *db = (char *)d->gs_args.p + (size_t)slot * d->h_gsargs_cap;
+  HIP_TRY(hipMemcpyAsync(db, d->h_gsargs[slot], bytes, hipMemcpyHostToDevice, (hipStream_t)stream));
+  HIP_TRY(hipEventRecord(d->ev_gsargs[slot], (hipStream_t)stream));
+  *dev = db;
   return CTCD_OK;
 }
 }  // namespace ctcgreedy
@@ -670,7 +704,11 @@ void ctcd_destroy(ctcd_decoder *d) {
   d->cp_scratch.release();
   if (d->h_cp) (void)hipHostFree(d->h_cp);
   d->sk_rows.release(); d->sk_kept.release(); d->sk_lsm.release();
-  d->al_bp.release(); d->al_lsm.release(); d->po_alpha.release(); d->gr_frames.release();
+  d->al_bp.release(); d->al_lsm.release(); d->po_alpha.release(); d->gr_frames.release(); d->gs_args.release();
+  for (int i = 0; i < 2; ++i) {
+    if (d->h_gsargs[i]) (void)hipHostFree(d->h_gsargs[i]);
+    if (d->ev_gsargs[i]) (void)hipEventDestroy(d->ev_gsargs[i]);
+  }
   if (d->h_sk) (void)hipHostFree(d->h_sk);
   if (d->ev_sk_tab) (void)hipEventDestroy(d->ev_sk_tab);
   for (int i = 0; i < 4; ++i) if (d->ev_sk[i]) (void)hipEventDestroy(d->ev_sk[i]);

@@ -6,7 +6,9 @@
 // Everything that defines the result is CTC_HD code here, compiled for both sides: the argmax step and the rule that combines two
 // partial winners, a winner's log-probability in the three input modes, the emit and run-end rules, the run and score bookkeeping,
 // and the scratch arithmetic.  The kernels of greedy.hip spread a frame's labels over lanes and an item's frames over a workgroup;
-// greedy_item_host below runs the same routines sequentially (the host twin, tests/native/greedy_host.cpp).
+// greedy_item_host below runs the same routines sequentially (the host twin, tests/native/greedy_host.cpp).  Live streams ("live
+// streams" below; greedy_stream.hip, greedy_stream_item_host, tests/native/greedy_stream_host.cpp) add the record a stream keeps
+// between chunk calls and the rules of what a call closes and leaves open.
 #pragma once
 #include <float.h>
 #include <stddef.h>
@@ -69,6 +71,59 @@ CTC_HD float run_max_back(float acc, float earlier) { return earlier >= acc ? ea
 // the score: lp of frame 0, then one float32 addition per frame, in frame order
 CTC_HD float score_step(float score, float lp, bool first) { return first ? lp : score + lp; }
 
+// ---- live streams ------------------------------------------------------------------------------------------------------------------
+// include/ctcdecode_amd.h "Greedy decode of live streams": what a stream carries from one chunk call to the next, so that its calls
+// return, piece by piece, the decode of all frames it was ever fed.  One record of 32 bytes in device memory per stream; the kernel
+// reads it at the start of a call and one thread writes it back at the end.
+struct StreamRec {
+  int32_t frames;    // frames fed so far (N)
+  int32_t prev;      // c*(N - 1); meaningless while frames == 0
+  int32_t emitted;   // labels emitted so far
+  int32_t closed;    // runs closed so far (= emitted, less the open one)
+  float score;       // the score of the frames so far; 0.0f while frames == 0
+  float open_max;    // the greatest lp so far of the open run; 0.0f without one
+  int32_t flags;     // kRecOpen | kRecEnded
+  int32_t first;     // F0: added to every frame number reported
+};
+static_assert(sizeof(StreamRec) == 32, "the record of a greedy stream is 32 bytes");
+enum : int { kRecOpen = 1, kRecEnded = 2 };
+constexpr long long kStreamMaxFrame = 0x7fffffffLL;  // F0 + the frames fed stays at or below it
+CTC_HD StreamRec stream_rec_init(int first_frame) {
+  StreamRec r;
+  r.frames = r.prev = r.emitted = r.closed = r.flags = 0;
+  r.score = r.open_max = 0.0f;
+  r.first = first_frame;
+  return r;
+}
+CTC_HD bool rec_open(const StreamRec &r) { return (r.flags & kRecOpen) != 0; }
+// the label in front of the chunk's frame 0 (emits does not look at it for the stream's first frame)
+CTC_HD int rec_prev(const StreamRec &r, int blank) { return r.frames > 0 ? r.prev : blank; }
+// chunk frame t is the first frame the stream ever had
+CTC_HD bool stream_first(const StreamRec &r, int t) { return r.frames == 0 && t == 0; }
+// the number reported for chunk frame t
+CTC_HD int stream_frame_no(const StreamRec &r, int t) { return r.first + r.frames + t; }
+// the run that came in open ends at the frame before this chunk: the chunk of n frames begins with another label (label0), or is empty and
+// ends the stream.  It is closed entry 0 of the call: end stream_frame_no(r, -1), maximum r.open_max.
+CTC_HD bool carried_closes(const StreamRec &r, int n, int label0, bool eos) { return rec_open(r) && (n > 0 ? label0 != r.prev : eos); }
+// chunk frame t of n is known to be the last of its run: its successor is in the chunk, or the stream ends with the chunk
+CTC_HD bool stream_run_ends(int c, int next, int t, int n, bool eos, int blank) { return (t + 1 < n || eos) && run_ends(c, next, t == n - 1, blank); }
+// ... or its run stays open: the chunk's last frame of a stream that goes on
+CTC_HD bool stream_run_open(int c, int t, int n, bool eos, int blank) { return c != blank && t == n - 1 && !eos; }
+// the record behind a chunk of n frames whose last label is last_label (n > 0), in which `emitted` labels were emitted and `closed` runs
+// closed; score: the score including the chunk; open_max: the maximum of the run stream_run_open found (n > 0)
+CTC_HD StreamRec stream_rec_after(const StreamRec &r, int n, int last_label, int emitted, int closed, float score, float open_max, bool eos, int blank) {
+  StreamRec a = r;
+  a.frames = r.frames + n;
+  a.emitted = r.emitted + emitted;
+  a.closed = r.closed + closed;
+  a.score = score;
+  if (n > 0) a.prev = last_label;
+  const bool open = !eos && (n > 0 ? last_label != blank : rec_open(r));
+  a.open_max = open ? (n > 0 ? open_max : r.open_max) : 0.0f;
+  a.flags = (open ? kRecOpen : 0) | (eos ? kRecEnded : 0);
+  return a;
+}
+
 // ---- scratch -----------------------------------------------------------------------------------------------------------------------
 // what the argmax pass leaves the collapse pass: 8 bytes per frame, frame t of item b at b * T + t
 struct FrameRec {
@@ -112,10 +167,8 @@ template <int DT> inline float lsm_sum_host(const void *rows, size_t row0, int V
 
 // Item b.  rec: the item's T frame records (scratch); tok / st / en / ls: T words each (en, ls may be NULL), all written; tbl:
 // exact_math.h's 64 table words (MODE 2).
-template <int DT, int MODE>
-inline void greedy_item_host(const void *probs, const int32_t *seq_lens, int b, int T, int V, int blank, const uint64_t *tbl, FrameRec *rec, int32_t *tok,
-                             int32_t *st, int32_t *en, float *ls, float *score, int32_t *len) {
-  const int n = ctcskip::clamped_len(seq_lens, b, T);
+// the argmax pass: the records of item b's first n frames
+template <int DT, int MODE> inline void frame_recs_host(const void *probs, int b, int T, int V, int n, const uint64_t *tbl, FrameRec *rec) {
   for (int t = 0; t < n; ++t) {
     const size_t row0 = ((size_t)b * T + (size_t)t) * V;
     Winner w = no_winner();
@@ -128,6 +181,13 @@ inline void greedy_item_host(const void *probs, const int32_t *seq_lens, int b, 
       rec[t].lp = winner_lp<MODE>(w.v);
     }
   }
+}
+
+template <int DT, int MODE>
+inline void greedy_item_host(const void *probs, const int32_t *seq_lens, int b, int T, int V, int blank, const uint64_t *tbl, FrameRec *rec, int32_t *tok,
+                             int32_t *st, int32_t *en, float *ls, float *score, int32_t *len) {
+  const int n = ctcskip::clamped_len(seq_lens, b, T);
+  frame_recs_host<DT, MODE>(probs, b, T, V, n, tbl, rec);
   int L = 0;
   float sc = 0.0f, rm = 0.0f;
   for (int t = 0; t < n; ++t) {
@@ -155,10 +215,59 @@ inline void greedy_item_host(const void *probs, const int32_t *seq_lens, int b, 
   }
 }
 
+// One chunk call for the stream whose record is *state, item b of the call's [B, Tc, V] rows.  rec: Tc frame records (scratch); tok / st:
+// Tc words each; en / ls: Tc + 1 words each and closed_len, or NULL all three; everything is written, *state included.
+template <int DT, int MODE>
+inline void greedy_stream_item_host(const void *probs, const int32_t *seq_lens, int b, int Tc, int V, int blank, const uint64_t *tbl, FrameRec *rec,
+                                    StreamRec *state, bool eos, int32_t *tok, int32_t *st, int32_t *en, float *ls, float *score, int32_t *len,
+                                    int32_t *closed_len) {
+  const int n = ctcskip::clamped_len(seq_lens, b, Tc);
+  frame_recs_host<DT, MODE>(probs, b, Tc, V, n, tbl, rec);
+  const StreamRec r = *state;
+  int E = 0, C = 0;
+  float sc = r.score, rm = r.open_max;
+  if (carried_closes(r, n, n > 0 ? rec[0].c : blank, eos)) {
+    if (en) en[C] = stream_frame_no(r, -1);
+    if (ls) ls[C] = r.open_max;
+    ++C;
+  }
+  for (int t = 0; t < n; ++t) {
+    const int c = rec[t].c;
+    sc = score_step(sc, rec[t].lp, stream_first(r, t));
+    if (emits(c, t > 0 ? rec[t - 1].c : rec_prev(r, blank), stream_first(r, t), blank)) {
+      tok[E] = c;
+      st[E] = stream_frame_no(r, t);
+      ++E;
+      rm = rec[t].lp;
+    } else if (c != blank) {
+      rm = run_max_fwd(rm, rec[t].lp);
+    }
+    if (stream_run_ends(c, t + 1 < n ? rec[t + 1].c : blank, t, n, eos, blank)) {
+      if (en) en[C] = stream_frame_no(r, t);
+      if (ls) ls[C] = rm;
+      ++C;
+    }
+  }
+  *state = stream_rec_after(r, n, n > 0 ? rec[n - 1].c : blank, E, C, sc, rm, eos, blank);
+  *score = sc;
+  *len = E;
+  if (closed_len) *closed_len = C;
+  for (int i = E; i < Tc; ++i) tok[i] = st[i] = 0;
+  for (int i = C; i <= Tc; ++i) {
+    if (en) en[i] = 0;
+    if (ls) ls[i] = 0.0f;
+  }
+}
+
 }  // namespace ctcgreedy
 
 struct ctcd_decoder;
 namespace ctcgreedy {
 // what greedy.hip needs of the library's host file (ctcdecode_amd.hip) beyond align.h's hooks: the decoder's frame records, grown to `bytes`
 int greedy_scratch(ctcd_decoder *d, size_t bytes, void **p);
+// ... and what greedy_stream.hip needs: `bytes` of per-stream arguments of a chunk call sent to the device in one copy queued on `stream`, through
+// page-locked staging the decoder owns (two slots, an event each: the call waits for nothing that is not long done); *dev: where they are
+int greedy_stream_upload(ctcd_decoder *d, const void *src, size_t bytes, void *stream, void **dev);
+// greedy.hip's argmax pass (in_dtype: CTCD_DTYPE_*; mode: log_input)
+void launch_argmax_pass(int in_dtype, int mode, const void *probs, const int32_t *seq_lens, long long frames, int T, int V, FrameRec *rec, void *stream);
 }  // namespace ctcgreedy

@@ -347,6 +347,13 @@ void launch_argmax_mode(int mode, const void *probs, const int32_t *seq_lens, lo
   else if (mode == kModeLog) launch_argmax<DT, kModeLog>(probs, seq_lens, frames, T, V, rec, stream);
   else launch_argmax<DT, kModeLogits>(probs, seq_lens, frames, T, V, rec, stream);
 }
+// the argmax pass over [frames / T, T, V] rows of the element type in_dtype (CTCD_DTYPE_*): greedy_stream.hip launches it too
+void launch_argmax_pass(int in_dtype, int mode, const void *probs, const int32_t *seq_lens, long long frames, int T, int V, FrameRec *rec, void *stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (in_dtype == CTCD_DTYPE_F16) launch_argmax_mode<kSkipF16>(mode, probs, seq_lens, frames, T, V, rec, s);
+  else if (in_dtype == CTCD_DTYPE_BF16) launch_argmax_mode<kSkipBF16>(mode, probs, seq_lens, frames, T, V, rec, s);
+  else launch_argmax_mode<kSkipF32>(mode, probs, seq_lens, frames, T, V, rec, s);
+}
 
 }  // namespace ctcgreedy
 
@@ -373,10 +380,7 @@ int ctcd_greedy_decode(ctcd_decoder *d, const void *probs, const int32_t *seq_le
   void *rec = nullptr;
   if (T > 0) {
     if (const int rc = greedy_scratch(d, greedy_scratch_bytes(B, T), &rec)) return rc;
-    const long long frames = (long long)B * T;
-    if (inf.in_dtype == CTCD_DTYPE_F16) launch_argmax_mode<kSkipF16>(log_input, probs, seq_lens, frames, T, V, (FrameRec *)rec, s);
-    else if (inf.in_dtype == CTCD_DTYPE_BF16) launch_argmax_mode<kSkipBF16>(log_input, probs, seq_lens, frames, T, V, (FrameRec *)rec, s);
-    else launch_argmax_mode<kSkipF32>(log_input, probs, seq_lens, frames, T, V, (FrameRec *)rec, s);
+    launch_argmax_pass(inf.in_dtype, log_input, probs, seq_lens, (long long)B * T, T, V, (FrameRec *)rec, s);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return align_fail(CTCD_EHIP, (std::string("greedy argmax: ") + hipGetErrorString(e)).c_str());
   }

@@ -758,10 +758,65 @@ long long ctcd_last_posterior_grid(const ctcd_decoder *dec);
  * scratch belongs to the decoder's next greedy decode: queue that call on the same stream, or wait.  A decoder built with a scorer
  * ignores it.  CTCD_EINVAL for bad shapes (negative sizes, V < 1, blank_id outside [0, V), log_input outside 0 .. 2, a NULL tensor),
  * and nothing is launched.  CTCD_EUNSUPPORTED for V > 2^28.  B == 0 is CTCD_OK and launches nothing; T == 0 with B > 0 writes
- * out_lens and out_scores as zeros.  Streams, more than one row per item and host pointers are out of scope. */
+ * out_lens and out_scores as zeros.  More than one row per item and host pointers are out of scope; streams: the next section. */
 int ctcd_greedy_decode(ctcd_decoder *dec, const void *probs, const int32_t *seq_lens, int B, int T, int V, int blank_id, int log_input,
                        int32_t *out_tokens, int32_t *out_starts /* [B][T] */, int32_t *out_ends, float *out_label_scores /* [B][T] or NULL */,
                        float *out_scores, int32_t *out_lens /* [B] */, void *stream);
+
+/* ---- Greedy decode of live streams: "Greedy decode" of a stream whose frames arrive chunk by chunk.  Under best-path decoding a
+ * label is final the moment its frame has been seen, so a call returns final labels, nothing is revised, and what a stream keeps
+ * between calls is a record of 32 bytes.
+ *
+ * Definition.  A greedy stream is created with a first frame number F0 >= 0.  A call feeds stream b the chunk probs[b, :n_b],
+ * n_b = clamp(seq_lens[b], 0, Tc) (Tc when seq_lens is NULL), and carries a host flag is_eos[b].
+ * The concatenation:
+ *   X is all frames fed to the stream so far, this chunk included; N is their count before this call.
+ *   tokens, starts, ends, label_scores, score, L are what "Greedy decode" defines for X (one item, n = its frame count).
+ *   Every frame number is reported shifted by F0.
+ * What a call returns for stream b:
+ *   out_tokens[b][0..E) and out_starts[b][0..E) are the labels of X whose emitting frame lies in this chunk, in order;
+ *   E = out_lens[b] <= n_b.
+ *   out_scores[b] is the score of X.  A stream that has never had a frame has score 0.0f.  The first frame ever seen sets the
+ *   score to its lp (a first lp of -0.0 stays -0.0); every later frame is one float32 addition, across calls as within them.
+ *   out_ends[b][0..C) and out_label_scores[b][0..C), C = out_closed_lens[b], are the ends / label_scores of the runs of X whose last
+ *   frame became known in this call, in order: the run with last frame e (unshifted) is reported by the first call for which
+ *   N + n_b > e + 1, or is_eos[b] and N + n_b == e + 1.  A run that reaches the chunk's last frame of a stream that goes on stays
+ *   open: its maximum so far travels in the record and a later call closes it -- a call with n_b == 0 and is_eos too.  Over a
+ *   stream's life the i-th closed run belongs to the i-th emitted label.  Up to n_b + 1 runs close in one call (the carried one and
+ *   n_b new ones): these two outputs have Tc + 1 columns.
+ *   The tie rule of the run maximum holds across calls: among equal values (-0.0, +0.0) the earlier frame's wins, also when that
+ *   frame was in an earlier call.
+ *   Every output position at or beyond its count is written as 0.
+ * What follows: however a row is cut into chunks, the calls' outputs concatenated are the row's ctcd_greedy_decode outputs, and the
+ * last call's score is its score, with equal bits.
+ *
+ * ctcd_greedy_stream_create / _destroy: a stream and its record on the decoder's device.  ctcd_greedy_stream_reset: a fresh stream
+ * with a first frame number again, the record written by a kernel queued on `stream`.  first_frame outside [0, 2^31 - 1] is
+ * CTCD_EINVAL.
+ * ctcd_greedy_stream_decode: states and is_eos are host arrays [B]; everything else is device memory and asynchronous on `stream`;
+ * nothing is read on the host.  probs [B][Tc][V] has the dtype ctcd_set_input_dtype set; the three input modes are those of
+ * ctcd_greedy_decode, whose argmax pass runs on the chunk as it stands, with the same decoder-owned frame records (they, and the
+ * staged per-stream arguments, belong to the decoder's next greedy call: queue it on the same stream, or wait).  out_tokens,
+ * out_starts int32 [B][Tc]; out_ends int32 [B][Tc + 1], out_label_scores float [B][Tc + 1] and out_closed_lens int32 [B], or NULL
+ * each; out_scores float [B], out_lens int32 [B].  Tc == 0 is legal: it writes the counts and the running score, and closes the open
+ * run of a stream whose is_eos is set.  No scorer, prune or blank filter takes part.
+ * CTCD_EINVAL, and nothing is launched: bad shapes, blank_id, log_input and NULL tensors as for ctcd_greedy_decode; a stream that has
+ * ended (is_eos in an earlier call) and was not reset; the same stream twice in one call; a stream of another device.
+ * CTCD_EUNSUPPORTED, and nothing is launched: the host keeps an upper bound of a stream's frame numbers, F0 + the Tc of every call,
+ * and a call that would take it beyond 2^31 - 1 is refused; the stream is intact.  V > 2^28.  B == 0 is CTCD_OK and launches nothing.
+ * ctcd_greedy_stream_info: waits for the device, then out = {frames fed (exact, unshifted), labels emitted, runs closed, 1 if a run
+ * is open else 0}.
+ * More than one row per item, host-pointer entry points and save / restore of a greedy stream are out of scope. */
+typedef struct ctcd_greedy_stream ctcd_greedy_stream;
+int ctcd_greedy_stream_create(ctcd_decoder *dec, ctcd_greedy_stream **out, long long first_frame);
+void ctcd_greedy_stream_destroy(ctcd_decoder *dec, ctcd_greedy_stream *st);
+int ctcd_greedy_stream_reset(ctcd_decoder *dec, ctcd_greedy_stream *st, long long first_frame, void *stream);
+int ctcd_greedy_stream_decode(ctcd_decoder *dec, ctcd_greedy_stream **states, const unsigned char *is_eos /* HOST [B] */,
+                              const void *probs, const int32_t *seq_lens, int B, int Tc, int V, int blank_id, int log_input,
+                              int32_t *out_tokens, int32_t *out_starts /* [B][Tc] */, int32_t *out_ends,
+                              float *out_label_scores /* [B][Tc + 1] or NULL */, int32_t *out_closed_lens /* [B] or NULL */,
+                              float *out_scores, int32_t *out_lens /* [B] */, void *stream);
+int ctcd_greedy_stream_info(ctcd_decoder *dec, const ctcd_greedy_stream *st, long long out[4]); /* waits */
 
 /* Tuning / introspection. */
 int ctcd_set_threads(ctcd_decoder *dec, int threads_per_workgroup); /* 0 = automatic (default); else a power of two in [64, 1024] */
