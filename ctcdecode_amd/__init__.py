@@ -921,6 +921,107 @@ class CTCBeamDecoder(object):
         outs = self.greedy_decode_device(probs, seq_lens)
         return tuple(o.cpu() for o in outs) if outs[0].numel() == 0 else tuple(_to_host(outs))
 
+    def edit_distance(self, beam_results, out_lens, references=None, ref_lens=None):
+        """Levenshtein distances on the device (include/ctcdecode_amd.h "Edit distance"): ``D[b, i, j]``, int32 [B, R, Q], is the least
+        number of insertions, deletions and substitutions that turn ``beam_results[b, i, :out_lens[b, i]]`` into
+        ``references[b, j, :ref_lens[b, j]]``.  Tokens are compared as int32 values and nothing else: no vocabulary and no ``blank_id``
+        take part, so word ids give word-level distances.  The arithmetic is integer and the result exact.
+
+        ``references`` [B, Q, Lq] with ``ref_lens`` [B, Q], or [B, Lq] with ``ref_lens`` [B], which is read as Q = 1.
+        ``references=None`` selects pairwise mode: every row of an item against every other row of it, [B, R, R] -- symmetric, a zero
+        diagonal, each pair computed once.  Tensors may be on the CPU or the device and of any integer dtype (they are cast to int32);
+        the result is on the device when ``beam_results`` is, otherwise CPU, as with ``align``.
+
+        ``D[:, :, 0].argmin(1)`` is the oracle row of an n-best list against one reference, so there is no method for it.  Error rates
+        are ``D / ref_lens``.  Rows of a decode beyond its number of results are empty rows and count as such: their distance to a
+        reference is the reference's length.
+
+        The shorter row of a pair is held in one wave's registers: ``min(L, Lq) > 2048`` raises ``NotImplementedError`` (the longer
+        side is not bounded).  A length outside [0, L] (references: [0, Lq]) raises ``ValueError``."""
+        if beam_results.dim() != 3 or out_lens.dim() != 2 or tuple(out_lens.shape) != tuple(beam_results.shape[:2]):
+            raise ValueError("beam_results must be [batch, rows, labels] and out_lens [batch, rows]")
+        on_device = beam_results.is_cuda
+        B, R, L = (int(v) for v in beam_results.shape)
+        pairwise = references is None
+        if pairwise:
+            if ref_lens is not None:
+                raise ValueError("ref_lens given without references")
+            Q, Lq = R, L
+        else:
+            if ref_lens is None:
+                raise ValueError("references need ref_lens")
+            if references.dim() == 2:
+                references, ref_lens = references.unsqueeze(1), ref_lens.reshape(-1, 1)
+            if references.dim() != 3 or ref_lens.dim() != 2 or tuple(ref_lens.shape) != tuple(references.shape[:2]):
+                raise ValueError("references must be [batch, refs, labels] or [batch, labels], and ref_lens [batch, refs] or [batch]")
+            if references.shape[0] != B:
+                raise ValueError("references.shape[0] (%d) does not match the batch (%d)" % (references.shape[0], B))
+            Q, Lq = int(references.shape[1]), int(references.shape[2])
+        x = beam_results.to(device=self._device, dtype=torch.int32).contiguous()
+        x_lens = out_lens.to(device=self._device, dtype=torch.int32).contiguous()
+        with torch.cuda.device(self._device):
+            y = y_lens = None
+            if not pairwise:
+                y = references.to(device=self._device, dtype=torch.int32).contiguous()
+                y_lens = ref_lens.to(device=self._device, dtype=torch.int32).contiguous()
+                if y.numel() == 0:  # (an empty tensor has no address, and a NULL y would select pairwise mode: a word that is never read)
+                    y = torch.zeros((1,), dtype=torch.int32, device=self._device)
+            out = torch.empty((B, R, Q), dtype=torch.int32, device=self._device)
+            status = torch.zeros((max(B, 1),), dtype=torch.int32, device=self._device)
+            stream = torch.cuda.current_stream(self._device).cuda_stream
+            _native.check(_native.lib.ctcd_edit_distance(self._handle, x.data_ptr(), x_lens.data_ptr(), B, R, L, None if pairwise else y.data_ptr(),
+                                                         None if pairwise else y_lens.data_ptr(), Q, Lq, out.data_ptr(), status.data_ptr(), stream))
+            bad = torch.nonzero(status[:B]).flatten().tolist() if B else []
+        if bad:
+            raise ValueError("ctcdecode_amd: edit_distance: items %s have a row with a length outside [0, %d]%s (CTCD_ALIGN_BAD_ROW)"
+                             % (bad[:8], L, "" if pairwise else " (references: [0, %d])" % Lq))
+        return out if on_device else out.cpu()
+
+    def last_edit_pairs(self):
+        """Test hook: the distances the last ``edit_distance`` computed -- B x R x Q, or B x R x (R - 1) / 2 in pairwise mode."""
+        return int(_native.lib.ctcd_last_edit_pairs(self._handle))
+
+    def set_edit_grid(self, n=0):
+        """The most workgroups the launch of ``edit_distance`` uses (include/ctcdecode_amd.h ctcd_set_edit_grid); 0 = the default, two
+        per compute unit.  The results do not depend on it."""
+        _native.check(_native.lib.ctcd_set_edit_grid(self._handle, int(n)))
+
+    def last_edit_grid(self):
+        """Test hook: the workgroups the last ``edit_distance`` launched."""
+        return int(_native.lib.ctcd_last_edit_grid(self._handle))
+
+    def mbr_select(self, beam_results, out_lens, log_weights):
+        """Minimum-Bayes-risk selection from an n-best list: for every item the row with the least expected edit distance to the other
+        rows.  Returns ``(index int64 [B], risk float64 [B, R])``, on the device when ``beam_results`` is, otherwise CPU.
+
+        ``D`` = pairwise ``edit_distance``; ``w = softmax(log_weights[b])`` in float64; ``risk[b, i] = sum_j w[b, j] * D[b, i, j]``;
+        ``index[b]`` is the smallest ``i`` of least risk.  Rows with ``log_weights == -inf`` weigh nothing, get risk ``+inf`` and are
+        never chosen; an item without a finite weight gets index ``-1`` and all risks ``+inf``.  The distances come from
+        ``edit_distance``, which reads its status words on the host (and so waits for the device, and raises ``ValueError`` for a bad
+        length); everything after them is plain torch on the device, with no further host read.
+
+        The natural weights are ``log_likelihood(probs, seq_lens, beam_results, out_lens)`` (plus whatever a language model adds).
+        Pass ``-inf`` for rows beyond a decode's result count: such rows are empty, and an empty row must not vote."""
+        if log_weights.dim() != 2 or tuple(log_weights.shape) != tuple(beam_results.shape[:2]):
+            raise ValueError("log_weights must be [batch, rows], one weight per row of beam_results")
+        on_device = beam_results.is_cuda
+        D = self.edit_distance(beam_results.to(self._device), out_lens).to(torch.float64)
+        lw = log_weights.to(device=self._device, dtype=torch.float64)
+        live = lw > float("-inf")
+        any_live = live.any(dim=1)
+        top = torch.where(live, lw, torch.full_like(lw, -1.0e308)).max(dim=1, keepdim=True).values if lw.shape[1] else lw[:, :0]
+        e = torch.where(live, torch.exp(torch.where(live, lw - top, torch.zeros_like(lw))), torch.zeros_like(lw))
+        w = e / e.sum(dim=1, keepdim=True).clamp_min(1.0e-300)
+        inf = torch.full_like(lw, float("inf"))
+        risk = torch.where(live, (D * w.unsqueeze(1)).sum(dim=2), inf)
+        if lw.shape[1]:
+            rows = torch.arange(lw.shape[1], dtype=torch.int64, device=self._device).expand_as(risk)
+            first = torch.where(risk == risk.min(dim=1, keepdim=True).values, rows, torch.full_like(rows, lw.shape[1])).min(dim=1).values
+            index = torch.where(any_live, first, torch.full_like(first, -1))
+        else:
+            index = torch.full((lw.shape[0],), -1, dtype=torch.int64, device=self._device)
+        return (index, risk) if on_device else (index.cpu(), risk.cpu())
+
     def decode_padded(self, probs, seq_lens=None, n_best=None):
         """The same call with the padded [B, K, T] tensors crossing PCIe (the delivery of round 1; kept for comparison); with ``n_best``
         the [B, n, T] ones."""

@@ -38,7 +38,8 @@ SYMBOLS = ["ctcd_log_softmax", "ctcd_compact_label_capacity", "ctcd_beam_decode_
            "ctcd_ctc_loglik", "ctcd_set_loglik_grid", "ctcd_last_loglik_grid",
            "ctcd_ctc_posteriors", "ctcd_set_posterior_scratch", "ctcd_last_posterior_grid",
            "ctcd_greedy_decode",
-           "ctcd_greedy_stream_create", "ctcd_greedy_stream_destroy", "ctcd_greedy_stream_reset", "ctcd_greedy_stream_decode", "ctcd_greedy_stream_info"]
+           "ctcd_greedy_stream_create", "ctcd_greedy_stream_destroy", "ctcd_greedy_stream_reset", "ctcd_greedy_stream_decode", "ctcd_greedy_stream_info",
+           "ctcd_edit_distance", "ctcd_last_edit_pairs", "ctcd_set_edit_grid", "ctcd_last_edit_grid"]
 
 
 def _load():
@@ -207,6 +208,13 @@ def _load():
     lib.ctcd_greedy_stream_reset.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p]
     lib.ctcd_greedy_stream_decode.argtypes = [ctypes.c_void_p] * 5 + [ctypes.c_int] * 5 + [ctypes.c_void_p] * 8
     lib.ctcd_greedy_stream_info.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_longlong)]
+    # edit distance (editdist.hip): dec, x, x_lens, B, R, L, y, y_lens, Q, Lq, out, status, stream
+    lib.ctcd_edit_distance.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_int] * 3 + [ctypes.c_void_p] * 2 + [ctypes.c_int] * 2 + [ctypes.c_void_p] * 3
+    lib.ctcd_last_edit_pairs.argtypes = [ctypes.c_void_p]
+    lib.ctcd_last_edit_pairs.restype = ctypes.c_longlong
+    lib.ctcd_set_edit_grid.argtypes = [ctypes.c_void_p, ctypes.c_longlong]
+    lib.ctcd_last_edit_grid.argtypes = [ctypes.c_void_p]
+    lib.ctcd_last_edit_grid.restype = ctypes.c_longlong
     return lib
 
 

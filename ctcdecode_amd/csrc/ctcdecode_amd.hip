@@ -44,6 +44,7 @@
 #include "loglik.h"
 #include "posterior.h"
 #include "greedy.h"
+#include "editdist.h"
 #include "prepass.h"
 
 namespace {
@@ -351,6 +352,10 @@ struct ctcd_decoder {
   long long po_budget = 0, po_grid = 0;
   // ctcd_greedy_decode (greedy.h): the frame records its argmax pass leaves its collapse pass
   Buf gr_frames;
+  // ctcd_edit_distance (editdist.h): the pairs its last call ran (ctcd_last_edit_pairs)
+  long long ed_pairs = 0;
+  // ... the cap of its grid (ctcd_set_edit_grid; 0 = the default) and the workgroups of its last launch (ctcd_last_edit_grid)
+  long long ed_cap = 0, ed_grid = 0;
   // ctcd_greedy_stream_decode (greedy.h "live streams"): a chunk call's per-stream arguments travel like ctcd_stream_decode's (two
   // page-locked slots, an event each, one copy per call)
   Buf gs_args;
@@ -433,6 +438,22 @@ int post_scratch(ctcd_decoder *d, size_t bytes, void **p) {
 }
 void post_note_grid(ctcd_decoder *d, long long grid) { d->po_grid = grid; }
 }  // namespace ctcpost
+
+// ... and the edit distance's (editdist.hip): the decoder's device and compute units, and the count of its last call's pairs
+namespace ctcedit {
+int edit_decoder_info(const ctcd_decoder *d, EditDecoderInfo *out) {
+  if (!d || !out) return fail(CTCD_EINVAL, "decoder == NULL");
+  out->device = d->device;
+  out->cus = d->cu_count;
+  out->cap = d->ed_cap;
+  return CTCD_OK;
+}
+int edit_fail(int code, const char *msg) { return fail(code, msg ? msg : ""); }
+void edit_note_pairs(ctcd_decoder *d, long long pairs, long long grid) {
+  d->ed_pairs = pairs;
+  d->ed_grid = grid;
+}
+}  // namespace ctcedit
 
 // ... and the greedy decode's (greedy.hip), beyond the alignment's hooks: its frame records
 namespace ctcgreedy {
@@ -758,6 +779,15 @@ int ctcd_set_posterior_scratch(ctcd_decoder *d, long long bytes) {
   return CTCD_OK;
 }
 long long ctcd_last_posterior_grid(const ctcd_decoder *d) { return d ? d->po_grid : -1; }
+
+// Edit distance (editdist.hip): the pairs its last call ran.
+long long ctcd_last_edit_pairs(const ctcd_decoder *d) { return d ? d->ed_pairs : -1; }
+int ctcd_set_edit_grid(ctcd_decoder *d, long long max_workgroups) {
+  if (!d || max_workgroups < 0) return fail(CTCD_EINVAL, "ctcd_set_edit_grid: a decoder and max_workgroups >= 0 (0 = the default) required");
+  d->ed_cap = max_workgroups;
+  return CTCD_OK;
+}
+long long ctcd_last_edit_grid(const ctcd_decoder *d) { return d ? d->ed_grid : -1; }
 
 int ctcd_set_cu_sharing(ctcd_decoder *d, int mode) {
   if (!d || mode < -1 || mode > 1) return fail(CTCD_EINVAL, "cu sharing mode must be -1 (automatic), 0 or 1");

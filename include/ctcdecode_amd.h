@@ -818,6 +818,44 @@ int ctcd_greedy_stream_decode(ctcd_decoder *dec, ctcd_greedy_stream **states, co
                               float *out_scores, int32_t *out_lens /* [B] */, void *stream);
 int ctcd_greedy_stream_info(ctcd_decoder *dec, const ctcd_greedy_stream *st, long long out[4]); /* waits */
 
+/* ---- Edit distance (no reference counterpart): how far apart two label rows are -- the Levenshtein distance between the rows a
+ * caller keeps and reference rows, or between all rows of an item.  It is what an error rate, the oracle row of an n-best list and
+ * minimum-Bayes-risk selection are built on.  The arithmetic is integer: the definition is exact and equality is equality.
+ *
+ * Definition.  lev(a, b) is the unit-cost Levenshtein distance between two int32 sequences: the least number of insertions, deletions
+ * and substitutions, each of cost 1, that turn a into b; a match costs 0.  lev(a, []) = len(a).
+ *   Elements are compared as int32 values and nothing else: every int32 is a token, negative values and blank_id among them.  No
+ *   vocabulary takes part, so word ids give word-level distances.
+ * The inputs: x int32 [B][R][L] with x_lens [B][R]; y int32 [B][Q][Lq] with y_lens [B][Q].
+ * The output: out int32 [B][R][Q], out[b][i][j] = lev(x[b][i][:x_lens[b][i]], y[b][j][:y_lens[b][j]]).
+ * Pairwise mode is selected by y == NULL: y is x and Q = R (the Q, Lq and y_lens passed are ignored).
+ *   The diagonal is written as 0.  Only the pairs i < j are computed; each result is written to both [i][j] and [j][i].
+ * Positions of a row at or beyond its length are never read.
+ * The validity rule: a length outside [0, L] (y: outside [0, Lq]) raises the item's word of `status` to CTCD_ALIGN_BAD_ROW (the same
+ * value, the same meaning), and ALL outputs of that item are 0.  Nothing is ever read through an unchecked length.
+ *
+ * ctcd_edit_distance: everything is device memory and asynchronous on `stream`; nothing is read on the host.  status: B device words
+ * the caller has zeroed, or NULL; words of valid items are not written.  One wave takes one pair: of the pair's two rows the shorter
+ * is held in the wave's registers, up to 32 columns per lane, and the longer is streamed past it -- lev is symmetric, so the choice
+ * is made per pair on the device, and the limit is one of tensor dimensions alone.
+ * CTCD_EINVAL, and nothing is launched: negative sizes, or a NULL tensor that is needed (x_lens, out; x when L > 0; y_lens when y is
+ * given).  B == 0, R == 0 or Q == 0 is CTCD_OK and launches nothing.  L == 0 or Lq == 0 is legal: the distances are the other side's
+ * lengths (in the general mode y must still be a non-NULL pointer; it is not read).
+ * CTCD_EUNSUPPORTED: min(L, Lq) > 2048 (pairwise mode: L > 2048); the longer side is bounded only by 2^30 positions per row, and B x R
+ * and B x Q by 2^31 - 1.
+ * ctcd_last_edit_pairs: the distances the last ctcd_edit_distance computed -- B x R x Q in the general mode, B x R x (R - 1) / 2 in
+ * pairwise mode (0: none yet, or an empty call; -1: dec == NULL).
+ * ctcd_set_edit_grid: the most workgroups (of four waves, a pair each) the launch uses; 0 = the default, two per compute unit.  The
+ * results do not depend on it; with a grid of one, four waves take all pairs in turn.  ctcd_last_edit_grid: the workgroups the last
+ * ctcd_edit_distance launched (0: none yet, or an empty call; -1: dec == NULL).
+ * Not provided: the counts of substitutions, insertions and deletions, back-traces, and sharing the common prefix of a beam's rows. */
+int ctcd_edit_distance(ctcd_decoder *dec, const int32_t *x /* [B][R][L] */, const int32_t *x_lens /* [B][R] */, int B, int R, int L,
+                       const int32_t *y /* [B][Q][Lq], or NULL: pairwise */, const int32_t *y_lens /* [B][Q] */, int Q, int Lq,
+                       int32_t *out /* [B][R][Q] */, int32_t *status /* [B] zeroed by the caller, or NULL */, void *stream);
+long long ctcd_last_edit_pairs(const ctcd_decoder *dec);
+int ctcd_set_edit_grid(ctcd_decoder *dec, long long max_workgroups);   /* 0 = the default */
+long long ctcd_last_edit_grid(const ctcd_decoder *dec);
+
 /* Tuning / introspection. */
 int ctcd_set_threads(ctcd_decoder *dec, int threads_per_workgroup); /* 0 = automatic (default); else a power of two in [64, 1024] */
 /* Two workgroups per CU.  The fixed-layout class (beam <= 128, <= 32 labels) has a second build of its kernel that fits
