@@ -990,6 +990,101 @@ class CTCBeamDecoder(object):
         """Test hook: the workgroups the last ``edit_distance`` launched."""
         return int(_native.lib.ctcd_last_edit_grid(self._handle))
 
+    def _edit_rows(self, beam_results, out_lens, references, ref_lens):
+        """The tensor handling ``edit_counts`` and ``edit_align`` share (that of ``edit_distance``).  -> (x, x_lens, y, y_lens, B, R, L,
+        Q, Lq) on the decoder's device, int32 and contiguous; y and y_lens are None in pairwise mode."""
+        if beam_results.dim() != 3 or out_lens.dim() != 2 or tuple(out_lens.shape) != tuple(beam_results.shape[:2]):
+            raise ValueError("beam_results must be [batch, rows, labels] and out_lens [batch, rows]")
+        B, R, L = (int(v) for v in beam_results.shape)
+        x = beam_results.to(device=self._device, dtype=torch.int32).contiguous()
+        x_lens = out_lens.to(device=self._device, dtype=torch.int32).contiguous()
+        if references is None:
+            if ref_lens is not None:
+                raise ValueError("ref_lens given without references")
+            return x, x_lens, None, None, B, R, L, R, L
+        if ref_lens is None:
+            raise ValueError("references need ref_lens")
+        if references.dim() == 2:
+            references, ref_lens = references.unsqueeze(1), ref_lens.reshape(-1, 1)
+        if references.dim() != 3 or ref_lens.dim() != 2 or tuple(ref_lens.shape) != tuple(references.shape[:2]):
+            raise ValueError("references must be [batch, refs, labels] or [batch, labels], and ref_lens [batch, refs] or [batch]")
+        if references.shape[0] != B:
+            raise ValueError("references.shape[0] (%d) does not match the batch (%d)" % (references.shape[0], B))
+        Q, Lq = int(references.shape[1]), int(references.shape[2])
+        y = references.to(device=self._device, dtype=torch.int32).contiguous()
+        y_lens = ref_lens.to(device=self._device, dtype=torch.int32).contiguous()
+        if y.numel() == 0:  # (an empty tensor has no address, and a NULL y selects pairwise mode: a word that is never read)
+            y = torch.zeros((1,), dtype=torch.int32, device=self._device)
+        return x, x_lens, y, y_lens, B, R, L, Q, Lq
+
+    def _edit_raise(self, what, status, B, L, Lq, pairwise):
+        bad = torch.nonzero(status[:B]).flatten().tolist() if B else []
+        if bad:
+            raise ValueError("ctcdecode_amd: %s: items %s have a row with a length outside [0, %d]%s (CTCD_ALIGN_BAD_ROW)"
+                             % (what, bad[:8], L, "" if pairwise else " (references: [0, %d])" % Lq))
+
+    def edit_counts(self, beam_results, out_lens, references=None, ref_lens=None):
+        """How an edit distance splits (include/ctcdecode_amd.h "Edit operations"): int32 [B, R, Q, 4] = ``(hits, substitutions,
+        deletions, insertions)`` of turning the reference ``references[b, j]`` into the hypothesis ``beam_results[b, i]`` -- an
+        insertion is a hypothesis token without a partner, a deletion a reference token without one.  Among the alignments of least
+        distance the counts are those with the fewest substitutions (the most hits); ``S + Del + I`` is ``edit_distance``,
+        ``H + S + I`` the hypothesis' length and ``H + S + Del`` the reference's.
+
+        Arguments, modes and tensor handling are ``edit_distance``'s.  Pairwise mode (``references=None``) gives [B, R, R, 4]:
+        ``[b, i, j]`` takes row ``i`` as the hypothesis, ``[b, j, i]`` has deletions and insertions exchanged, the diagonal is
+        ``(len, 0, 0, 0)``.  ``min(L, Lq) > 2048`` or ``max(L, Lq) > 262144`` raises ``NotImplementedError``; a length outside its
+        bounds raises ``ValueError``."""
+        on_device = beam_results.is_cuda
+        x, x_lens, y, y_lens, B, R, L, Q, Lq = self._edit_rows(beam_results, out_lens, references, ref_lens)
+        pairwise = y is None
+        with torch.cuda.device(self._device):
+            out = torch.empty((B, R, Q, 4), dtype=torch.int32, device=self._device)
+            status = torch.zeros((max(B, 1),), dtype=torch.int32, device=self._device)
+            stream = torch.cuda.current_stream(self._device).cuda_stream
+            _native.check(_native.lib.ctcd_edit_counts(self._handle, x.data_ptr(), x_lens.data_ptr(), B, R, L, None if pairwise else y.data_ptr(),
+                                                       None if pairwise else y_lens.data_ptr(), Q, Lq, out.data_ptr(), status.data_ptr(), stream))
+            self._edit_raise("edit_counts", status, B, L, Lq, pairwise)
+        return out if on_device else out.cpu()
+
+    def edit_align(self, beam_results, out_lens, references, ref_lens):
+        """The token alignment behind an edit distance (include/ctcdecode_amd.h "Edit operations").  Returns ``(hyp_to_ref int32
+        [B, R, Q, L], ref_to_hyp int32 [B, R, Q, Lq], counts int32 [B, R, Q, 4])``: ``hyp_to_ref[b, i, j, p]`` is the position in
+        ``references[b, j]`` that token ``p`` of ``beam_results[b, i]`` stands against -- a hit or a substitution -- or -1 if the
+        token is an insertion or ``p`` is at or beyond the row's length; ``ref_to_hyp`` is the same from the reference's side (-1: a
+        deletion); ``counts`` is what ``edit_counts`` returns.  Of the alignments of least distance it is one with the fewest
+        substitutions, and among those the canonical one of the header: walking back from the ends, a pair is preferred to an
+        insertion and an insertion to a deletion.  ``timesteps.gather(-1, ref_to_hyp.clamp_min(0))`` carries a hypothesis' time steps
+        onto the reference.
+
+        ``references`` are required (there is no pairwise mode); tensor handling and errors are ``edit_counts``'.  The walk's
+        directions live in decoder-owned scratch (``set_edit_scratch``); a call whose single slot does not fit the budget raises
+        ``NotImplementedError``."""
+        if references is None:
+            raise ValueError("edit_align needs references: alignments are not provided in pairwise mode")
+        on_device = beam_results.is_cuda
+        x, x_lens, y, y_lens, B, R, L, Q, Lq = self._edit_rows(beam_results, out_lens, references, ref_lens)
+        with torch.cuda.device(self._device):
+            h2r = torch.empty((B, R, Q, L), dtype=torch.int32, device=self._device)
+            r2h = torch.empty((B, R, Q, Lq), dtype=torch.int32, device=self._device)
+            counts = torch.empty((B, R, Q, 4), dtype=torch.int32, device=self._device)
+            status = torch.zeros((max(B, 1),), dtype=torch.int32, device=self._device)
+            stream = torch.cuda.current_stream(self._device).cuda_stream
+            _native.check(_native.lib.ctcd_edit_align(self._handle, x.data_ptr(), x_lens.data_ptr(), B, R, L, y.data_ptr(), y_lens.data_ptr(), Q, Lq,
+                                                      h2r.data_ptr() if h2r.numel() else None, r2h.data_ptr() if r2h.numel() else None, counts.data_ptr(),
+                                                      status.data_ptr(), stream))
+            self._edit_raise("edit_align", status, B, L, Lq, False)
+        outs = (h2r, r2h, counts)
+        return outs if on_device else tuple(o.cpu() for o in outs)
+
+    def set_edit_scratch(self, nbytes=0):
+        """The budget of ``edit_align``'s back-pointer scratch in bytes (include/ctcdecode_amd.h ctcd_set_edit_scratch); 0 = the
+        default, 1 GiB.  A call runs as many waves as the budget has slots for; the results do not depend on it."""
+        _native.check(_native.lib.ctcd_set_edit_scratch(self._handle, int(nbytes)))
+
+    def last_edit_slots(self):
+        """Test hook: the back-pointer slots (waves with work) of the last ``edit_align``."""
+        return int(_native.lib.ctcd_last_edit_slots(self._handle))
+
     def mbr_select(self, beam_results, out_lens, log_weights):
         """Minimum-Bayes-risk selection from an n-best list: for every item the row with the least expected edit distance to the other
         rows.  Returns ``(index int64 [B], risk float64 [B, R])``, on the device when ``beam_results`` is, otherwise CPU.

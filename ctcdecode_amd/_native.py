@@ -39,7 +39,8 @@ SYMBOLS = ["ctcd_log_softmax", "ctcd_compact_label_capacity", "ctcd_beam_decode_
            "ctcd_ctc_posteriors", "ctcd_set_posterior_scratch", "ctcd_last_posterior_grid",
            "ctcd_greedy_decode",
            "ctcd_greedy_stream_create", "ctcd_greedy_stream_destroy", "ctcd_greedy_stream_reset", "ctcd_greedy_stream_decode", "ctcd_greedy_stream_info",
-           "ctcd_edit_distance", "ctcd_last_edit_pairs", "ctcd_set_edit_grid", "ctcd_last_edit_grid"]
+           "ctcd_edit_distance", "ctcd_last_edit_pairs", "ctcd_set_edit_grid", "ctcd_last_edit_grid",
+           "ctcd_edit_counts", "ctcd_edit_align", "ctcd_set_edit_scratch", "ctcd_last_edit_slots"]
 
 
 def _load():
@@ -215,6 +216,12 @@ def _load():
     lib.ctcd_set_edit_grid.argtypes = [ctypes.c_void_p, ctypes.c_longlong]
     lib.ctcd_last_edit_grid.argtypes = [ctypes.c_void_p]
     lib.ctcd_last_edit_grid.restype = ctypes.c_longlong
+    # edit operations (editops.hip): counts take ctcd_edit_distance's arguments; align: dec, x, x_lens, B, R, L, y, y_lens, Q, Lq, x_to_y, y_to_x, counts, status, stream
+    lib.ctcd_edit_counts.argtypes = lib.ctcd_edit_distance.argtypes
+    lib.ctcd_edit_align.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_int] * 3 + [ctypes.c_void_p] * 2 + [ctypes.c_int] * 2 + [ctypes.c_void_p] * 5
+    lib.ctcd_set_edit_scratch.argtypes = [ctypes.c_void_p, ctypes.c_longlong]
+    lib.ctcd_last_edit_slots.argtypes = [ctypes.c_void_p]
+    lib.ctcd_last_edit_slots.restype = ctypes.c_longlong
     return lib
 
 

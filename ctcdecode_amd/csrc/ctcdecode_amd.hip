@@ -45,6 +45,7 @@
 #include "posterior.h"
 #include "greedy.h"
 #include "editdist.h"
+#include "editops.h"
 #include "prepass.h"
 
 namespace {
@@ -356,6 +357,10 @@ struct ctcd_decoder {
   long long ed_pairs = 0;
   // ... the cap of its grid (ctcd_set_edit_grid; 0 = the default) and the workgroups of its last launch (ctcd_last_edit_grid)
   long long ed_cap = 0, ed_grid = 0;
+  // ctcd_edit_align (editops.h): the back-pointer slots of its waves, their budget (ctcd_set_edit_scratch; 0 = the default) and the
+  // slots of the last call (ctcd_last_edit_slots)
+  Buf ed_bp;
+  long long ed_budget = 0, ed_slots = 0;
   // ctcd_greedy_stream_decode (greedy.h "live streams"): a chunk call's per-stream arguments travel like ctcd_stream_decode's (two
   // page-locked slots, an event each, one copy per call)
   Buf gs_args;
@@ -453,6 +458,15 @@ void edit_note_pairs(ctcd_decoder *d, long long pairs, long long grid) {
   d->ed_pairs = pairs;
   d->ed_grid = grid;
 }
+// ... and the edit operations' (editops.hip): the budget of the back-pointer scratch, the scratch, and the slots of the last call
+long long edit_budget(const ctcd_decoder *d) { return d->ed_budget; }
+int edit_scratch(ctcd_decoder *d, size_t bytes, void **p) {
+  std::lock_guard<std::mutex> lock(d->mu);
+  if (const int rc = d->ed_bp.ensure(bytes)) return rc;
+  *p = d->ed_bp.p;
+  return CTCD_OK;
+}
+void edit_note_slots(ctcd_decoder *d, long long slots) { d->ed_slots = slots; }
 }  // namespace ctcedit
 
 // ... and the greedy decode's (greedy.hip), beyond the alignment's hooks: its frame records
@@ -725,7 +739,7 @@ void ctcd_destroy(ctcd_decoder *d) {
   d->cp_scratch.release();
   if (d->h_cp) (void)hipHostFree(d->h_cp);
   d->sk_rows.release(); d->sk_kept.release(); d->sk_lsm.release();
-  d->al_bp.release(); d->al_lsm.release(); d->po_alpha.release(); d->gr_frames.release(); d->gs_args.release();
+  d->al_bp.release(); d->al_lsm.release(); d->po_alpha.release(); d->gr_frames.release(); d->gs_args.release(); d->ed_bp.release();
   for (int i = 0; i < 2; ++i) {
     if (d->h_gsargs[i]) (void)hipHostFree(d->h_gsargs[i]);
     if (d->ev_gsargs[i]) (void)hipEventDestroy(d->ev_gsargs[i]);
@@ -788,6 +802,13 @@ int ctcd_set_edit_grid(ctcd_decoder *d, long long max_workgroups) {
   return CTCD_OK;
 }
 long long ctcd_last_edit_grid(const ctcd_decoder *d) { return d ? d->ed_grid : -1; }
+// Edit operations (editops.hip): the budget of ctcd_edit_align's back-pointer scratch, and the slots its last call used.
+int ctcd_set_edit_scratch(ctcd_decoder *d, long long bytes) {
+  if (!d || bytes < 0) return fail(CTCD_EINVAL, "ctcd_set_edit_scratch: a decoder and bytes >= 0 (0 = the default) required");
+  d->ed_budget = bytes;
+  return CTCD_OK;
+}
+long long ctcd_last_edit_slots(const ctcd_decoder *d) { return d ? d->ed_slots : -1; }
 
 int ctcd_set_cu_sharing(ctcd_decoder *d, int mode) {
   if (!d || mode < -1 || mode > 1) return fail(CTCD_EINVAL, "cu sharing mode must be -1 (automatic), 0 or 1");

@@ -848,13 +848,72 @@ int ctcd_greedy_stream_info(ctcd_decoder *dec, const ctcd_greedy_stream *st, lon
  * ctcd_set_edit_grid: the most workgroups (of four waves, a pair each) the launch uses; 0 = the default, two per compute unit.  The
  * results do not depend on it; with a grid of one, four waves take all pairs in turn.  ctcd_last_edit_grid: the workgroups the last
  * ctcd_edit_distance launched (0: none yet, or an empty call; -1: dec == NULL).
- * Not provided: the counts of substitutions, insertions and deletions, back-traces, and sharing the common prefix of a beam's rows. */
+ * Not provided: sharing the common prefix of a beam's rows.  (The counts of the edits and the alignment: the next section.) */
 int ctcd_edit_distance(ctcd_decoder *dec, const int32_t *x /* [B][R][L] */, const int32_t *x_lens /* [B][R] */, int B, int R, int L,
                        const int32_t *y /* [B][Q][Lq], or NULL: pairwise */, const int32_t *y_lens /* [B][Q] */, int Q, int Lq,
                        int32_t *out /* [B][R][Q] */, int32_t *status /* [B] zeroed by the caller, or NULL */, void *stream);
 long long ctcd_last_edit_pairs(const ctcd_decoder *dec);
 int ctcd_set_edit_grid(ctcd_decoder *dec, long long max_workgroups);   /* 0 = the default */
 long long ctcd_last_edit_grid(const ctcd_decoder *dec);
+
+/* ---- Edit operations (no reference counterpart): how an edit distance splits into substitutions, deletions and insertions -- the
+ * breakdown of an error-rate report -- and which token of a hypothesis stands against which token of a reference.  Integer
+ * arithmetic throughout, exact like "Edit distance", whose comparison of tokens (int32 values, nothing else), inputs, modes, validity
+ * rule and status word are used here unchanged.
+ *
+ * Definition.  x is the hypothesis row, of lx tokens; y is the reference row, of ly tokens.  An alignment is a monotone path from
+ * (0, 0) to (lx, ly) made of three kinds of step:
+ *   a pair (i, j) -> (i+1, j+1): a HIT if x[i] == y[j], a SUBSTITUTION otherwise;
+ *   an x-only step (i, j) -> (i+1, j): x[i] has no partner, an INSERTION;
+ *   a y-only step (i, j) -> (i, j+1): y[j] has no partner, a DELETION.
+ * Its key is the tuple (D, S): D the number of substitutions, insertions and deletions, S the number of substitutions.
+ * The optimal key is the lexicographically least one: the least distance, and among the alignments of that distance the fewest
+ *   substitutions.  Since H = (lx + ly - D - S) / 2, that is the most hits.  D is lev(x, y) of "Edit distance".
+ *   The order is translation-invariant and both components add up along a path, so the cell recurrence
+ *   K[i][j] = min(K[i-1][j-1] + (x[i-1] != y[j-1] ? (1,1) : (0,0)), K[i-1][j] + (1,0), K[i][j-1] + (1,0)),
+ *   K[0][j] = (j, 0), K[i][0] = (i, 0), is exact.
+ * The counts (H, S, Del, I) of an optimal alignment follow from K[lx][ly] = (D, S) and the lengths alone:
+ *   I = (D - S + lx - ly) / 2, Del = (D - S - lx + ly) / 2, H = lx - S - I.
+ *   They do not depend on which optimal path is taken.  Exchanging x and y exchanges I and Del and leaves H and S as they are.
+ *   H + S + I == lx, H + S + Del == ly, S + Del + I == lev(x, y).
+ * The canonical alignment is found by walking back from (lx, ly).  At (i, j):
+ *   1. if i > 0 and j > 0 and K[i-1][j-1] + the pair's cost == K[i][j], take the pair;
+ *   2. otherwise, if i > 0 and K[i-1][j] + (1,0) == K[i][j], take the insertion (x-only);
+ *   3. otherwise take the deletion.
+ *   The preference is one of x and y: which of the two rows the device keeps in registers does not enter.
+ *   x = [a, b], y = [b, a]: D = 2, S = 0, x_to_y = [1, -1], y_to_x = [-1, 0].
+ * The packed form the device computes with is K = D * 4096 + S in one 32-bit word: S <= min(lx, ly) <= 2048 < 4096, and the key and
+ *   every candidate stay below 2^31 while max(L, Lq) <= 262144.
+ *
+ * ctcd_edit_counts: the arguments, modes, validity rule, status word and error codes of ctcd_edit_distance; out int32 [B][R][Q][4] =
+ * (H, S, Del, I).  Pairwise mode (y == NULL): [i][j] takes row i as x; [j][i] is the same with Del and I exchanged; the diagonal is
+ * (len, 0, 0, 0).  An invalid item: all words 0.  One more limit: max(L, Lq) > 262144 is CTCD_EUNSUPPORTED.  ctcd_set_edit_grid,
+ * ctcd_last_edit_pairs and ctcd_last_edit_grid apply to it (and to ctcd_edit_align) as to ctcd_edit_distance.
+ *
+ * ctcd_edit_align: the general mode only; y == NULL is CTCD_EINVAL.  x_to_y int32 [B][R][Q][L]: x_to_y[..][p] is the index of x[p]'s
+ * partner in y on the canonical alignment, or -1 if x[p] is an insertion, and -1 for p >= lx.  y_to_x int32 [B][R][Q][Lq] is the same
+ * from the other side (-1: a deletion, or beyond ly).  counts [B][R][Q][4] as above, or NULL.  Every word of all three is written; an
+ * invalid item has all maps -1 and all counts 0.  Everything is device memory and asynchronous on `stream`; nothing is read on the
+ * host.  The limits are those of ctcd_edit_counts.
+ * The directions of the walk, two bits per cell, live in decoder-owned scratch: one slot per wave in flight, of max(L, Lq) rows of 64
+ * words -- 4 bytes each while min(L, Lq) <= 1024, 8 bytes beyond -- sized from the tensor dimensions alone.  The launch has as many
+ * waves as the usual grid, as the call has pairs, or as the budget has slots for, whichever is least; only that many slots are
+ * allocated, when first needed.  If one slot does not fit the budget the call returns CTCD_EUNSUPPORTED, the sizes in
+ * ctcd_last_error, and the decoder stays usable.  The scratch belongs to the decoder's next ctcd_edit_align: queue it on the same
+ * stream, or wait.
+ * ctcd_set_edit_scratch: that budget in bytes; 0 = the default, 1 GiB.  The results do not depend on it.
+ * ctcd_last_edit_slots: the slots (waves with a pair to work on) of the last ctcd_edit_align (0: none yet, or an empty call; -1:
+ * dec == NULL).
+ * Not provided: alignments in pairwise mode, weighted costs, and sharing the common prefix of a beam's rows. */
+int ctcd_edit_counts(ctcd_decoder *dec, const int32_t *x /* [B][R][L] */, const int32_t *x_lens /* [B][R] */, int B, int R, int L,
+                     const int32_t *y /* [B][Q][Lq], or NULL: pairwise */, const int32_t *y_lens /* [B][Q] */, int Q, int Lq,
+                     int32_t *out /* [B][R][Q][4] = H, S, Del, I */, int32_t *status /* [B] zeroed by the caller, or NULL */, void *stream);
+int ctcd_edit_align(ctcd_decoder *dec, const int32_t *x /* [B][R][L] */, const int32_t *x_lens /* [B][R] */, int B, int R, int L,
+                    const int32_t *y /* [B][Q][Lq] */, const int32_t *y_lens /* [B][Q] */, int Q, int Lq,
+                    int32_t *x_to_y /* [B][R][Q][L] */, int32_t *y_to_x /* [B][R][Q][Lq] */, int32_t *counts /* [B][R][Q][4], or NULL */,
+                    int32_t *status /* [B] zeroed by the caller, or NULL */, void *stream);
+int ctcd_set_edit_scratch(ctcd_decoder *dec, long long bytes);   /* budget of the back-pointer scratch; 0 = the default */
+long long ctcd_last_edit_slots(const ctcd_decoder *dec);
 
 /* Tuning / introspection. */
 int ctcd_set_threads(ctcd_decoder *dec, int threads_per_workgroup); /* 0 = automatic (default); else a power of two in [64, 1024] */
