@@ -445,6 +445,16 @@ class CTCBeamDecoder(object):
         that keeps several launches in flight; 0: never; -1 (default): when a batch has more utterances than the GPU has CUs."""
         _native.check(_native.lib.ctcd_set_cu_sharing(self._handle, int(mode)))
 
+    def set_exact_shape(self, mode=-1):
+        """Exact-shape kernels (include/ctcdecode_amd.h ctcd_set_exact_shape): builds of the plain north-star kernel with beam width,
+        label count and blank index as constants -- beam 100 over 29 labels, blank 0.  -1 (default): wherever a call has exactly that
+        shape; 0: never; 1: required (a call that does not qualify raises and launches nothing).  Results are bit-identical."""
+        _native.check(_native.lib.ctcd_set_exact_shape(self._handle, int(mode)))
+
+    def last_exact_shape(self):
+        """1 if the last launch ran an exact-shape kernel, else 0."""
+        return int(_native.lib.ctcd_last_exact_shape(self._handle))
+
     def set_subtree_search(self, mode=-1):
         """Phase A1's four-subtrees-per-wave build of the north-star class kernel (include/ctcdecode_amd.h): -1 = chosen from the beam
         shape the last checked launch reported (chain-shaped beams, i.e. blank-dominated rows: on), 0 / 1 = never / always."""

@@ -14,7 +14,8 @@ CSRC = os.path.join(HERE, "csrc")
 LIB_DIR = os.path.join(HERE, "_lib")
 # CTCDECODE_AMD_LIB: load another build of the library (kernel experiments: tools/build_variants.sh)
 LIB_PATH = os.environ.get("CTCDECODE_AMD_LIB") or os.path.join(LIB_DIR, "libctcdecode_amd.so")
-SOURCES = ["ctcdecode_amd.hip", "prepass.hip", "stream_peek.hip", "stream_compact.hip", "stream_commit.hip", "stream_snapshot.hip", "blank_skip.hip", "stream_blank_skip.hip", "nbest.hip", "align.hip", "loglik.hip", "posterior.hip", "greedy.hip", "greedy_stream.hip", "editdist.hip", "editops.hip"]
+SOURCES = ["ctcdecode_amd.hip", "decode_kernel_exact.hip", "prepass.hip", "stream_peek.hip", "stream_compact.hip", "stream_commit.hip", "stream_snapshot.hip", "blank_skip.hip", "stream_blank_skip.hip", "nbest.hip", "align.hip", "loglik.hip", "posterior.hip", "greedy.hip", "greedy_stream.hip", "editdist.hip", "editops.hip"]
+# (decode_kernel_exact.hip: the exact-shape twins of the north-star kernel, decode_kernel.h CTC_EXACT_SHAPES)
 KERNEL_SOURCE = "decode_kernels.hip"  # compiled once per group of kernel instantiations (decode_kernel.h CTC_KERNEL_LIST), in parallel
 KERNEL_GROUPS = 12
 HEADERS = ["decode_kernels.hip", "decode_kernel.h", "launch_plan.h", "beam_core.h", "stl_emul.h", "exact_math.h", "exact_math_f64.h", "exact_math_f64_tables.h", "lm_tables.h", "lm_build.h", "lm_callback.h", "compact_results.h", "prepass.h", "stream_peek.h", "stream_compact.h", "stream_commit.h", "stream_snapshot.h", "blank_skip.h", "stream_blank_skip.h", "nbest.h", "align.h", "loglik.h", "posterior.h", "greedy.h", "editdist.h", "editops.h", "lsm_device.h", "lattice_device.h", "device_guard.h", os.path.join("..", "..", "include", "ctcdecode_amd.h")]

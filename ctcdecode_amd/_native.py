@@ -30,7 +30,7 @@ class SnapshotInfo(ctypes.Structure):  # ctcd_snapshot_info_t
 SYMBOLS = ["ctcd_log_softmax", "ctcd_compact_label_capacity", "ctcd_beam_decode_compact", "ctcd_expand_compact", "ctcd_beam_decode_to_host", "ctcd_scorer_create", "ctcd_scorer_destroy", "ctcd_scorer_is_character_based", "ctcd_scorer_max_order", "ctcd_scorer_dict_size",
            "ctcd_scorer_reset_params", "ctcd_scorer_cond_log_prob", "ctcd_scorer_create_callback", "ctcd_scorer_cond_log10", "ctcd_scorer_callback_calls", "ctcd_scorer_callback_seconds", "ctcd_scorer_set_callback_threads", "ctcd_scorer_create_callback_batch", "ctcd_scorer_cond_log10_batch", "ctcd_scorer_callback_batches", "ctcd_beam_decode_lm", "ctcd_beam_decode_lm_host", "ctcd_stream_create_lm",
            "ctcd_create", "ctcd_destroy", "ctcd_beam_decode", "ctcd_beam_decode_host", "ctcd_check_status", "ctcd_fetch_status_async", "ctcd_stream_create", "ctcd_stream_destroy", "ctcd_stream_frames", "ctcd_stream_decode", "ctcd_stream_decode_to_host", "ctcd_stream_peek", "ctcd_stream_compact", "ctcd_stream_commit", "ctcd_stream_committed", "ctcd_stream_save", "ctcd_stream_restore", "ctcd_snapshot_info", "ctcd_scorer_fingerprint", "ctcd_stream_pool_nodes", "ctcd_stream_pool_capacity", "ctcd_stream_bytes", "ctcd_set_stream_compaction", "ctcd_last_prune_host_rows", "ctcd_last_prune_flagged_rows", "ctcd_last_scorer_rounds", "ctcd_last_scorer_waits", "ctcd_set_scorer_wait", "ctcd_set_scorer_filter", "ctcd_last_scorer_pairs",
-           "ctcd_set_threads", "ctcd_set_cu_sharing", "ctcd_set_input_dtype", "ctcd_last_input_dtype", "ctcd_set_launch_order", "ctcd_debug_last_launch_order", "ctcd_set_subtree_search", "ctcd_last_subtree_search", "ctcd_debug_last_layout", "ctcd_debug_last_kernel", "ctcd_debug_last_prepass", "ctcd_debug_prepass_table", "ctcd_debug_set_host_path", "ctcd_set_timing", "ctcd_last_kernel_ms", "ctcd_last_prune_ms", "ctcd_last_resolve_ms", "ctcd_debug_math_check", "ctcd_debug_set_profile", "ctcd_debug_set_fixed_layout", "ctcd_debug_set_prune_resolve", "ctcd_debug_set_fused_logits", "ctcd_debug_set_prune_registers", "ctcd_debug_prune_rows", "ctcd_debug_timeline", "ctcd_debug_timeline_cap", "ctcd_debug_get_profile", "ctcd_debug_beam_dump", "ctcd_workgroup_lds_bytes", "ctcd_last_error", "ctcd_version",
+           "ctcd_set_threads", "ctcd_set_cu_sharing", "ctcd_set_exact_shape", "ctcd_last_exact_shape", "ctcd_set_input_dtype", "ctcd_last_input_dtype", "ctcd_set_launch_order", "ctcd_debug_last_launch_order", "ctcd_set_subtree_search", "ctcd_last_subtree_search", "ctcd_debug_last_layout", "ctcd_debug_last_kernel", "ctcd_debug_last_prepass", "ctcd_debug_prepass_table", "ctcd_debug_set_host_path", "ctcd_set_timing", "ctcd_last_kernel_ms", "ctcd_last_prune_ms", "ctcd_last_resolve_ms", "ctcd_debug_math_check", "ctcd_debug_set_profile", "ctcd_debug_set_fixed_layout", "ctcd_debug_set_prune_resolve", "ctcd_debug_set_fused_logits", "ctcd_debug_set_prune_registers", "ctcd_debug_prune_rows", "ctcd_debug_timeline", "ctcd_debug_timeline_cap", "ctcd_debug_get_profile", "ctcd_debug_beam_dump", "ctcd_workgroup_lds_bytes", "ctcd_last_error", "ctcd_version",
            "ctcd_blank_skip", "ctcd_remap_timesteps", "ctcd_remap_compact", "ctcd_remap_timesteps_host",
            "ctcd_set_stream_blank_skip", "ctcd_stream_frames_seen", "ctcd_stream_map_bytes", "ctcd_last_stream_blank_skip", "ctcd_last_stream_blank_skip_ms",
            "ctcd_expand_compact_nbest", "ctcd_beam_decode_nbest", "ctcd_beam_decode_to_host_nbest",
@@ -59,6 +59,8 @@ def _load():
     lib.ctcd_set_threads.argtypes = [ctypes.c_void_p, ctypes.c_int]
     lib.ctcd_set_timing.argtypes = [ctypes.c_void_p, ctypes.c_int]
     lib.ctcd_set_cu_sharing.argtypes = [ctypes.c_void_p, ctypes.c_int]
+    lib.ctcd_set_exact_shape.argtypes = [ctypes.c_void_p, ctypes.c_int]
+    lib.ctcd_last_exact_shape.argtypes = [ctypes.c_void_p]
     lib.ctcd_set_input_dtype.argtypes = [ctypes.c_void_p, ctypes.c_int]
     lib.ctcd_last_input_dtype.argtypes = [ctypes.c_void_p]
     lib.ctcd_set_launch_order.argtypes = [ctypes.c_void_p, ctypes.c_int]

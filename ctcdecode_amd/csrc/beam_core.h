@@ -457,6 +457,40 @@ struct FullSyncView {
 #define CTC_ASSUME(c) do { if (!(c)) __builtin_unreachable(); } while (0)
 #endif
 
+// Shape policy: how the frame loop learns the beam width, the number of candidate labels of a frame, the blank's rank among them
+// and the live beam size.  ShapeAny (every kernel of the library's list): the run-time values.  ShapeExact<KC, VC, BLANK>: constants
+// -- a build for ONE shape, beam KC over VC labels, blank at index BLANK, no pruning, no scorer -- in which slot arithmetic,
+// lane-group shapes, loop bounds and the select's compares are immediates and none of the four occupies a scalar register across
+// the loop (Vnb, the number of non-blank candidates, follows from the candidate count and the blank's rank).  FOLD_LIVE also folds
+// the live beam size once the beam is full (Decoder::step<FULL>).
+// A policy is a set of constants plus kExact / kFoldLive: step() reads each quantity as `SP::kExact ? SP::kBeam : d.K`, a select on
+// a constant condition, which leaves the builds under ShapeAny token for token what they were (tools/kernel_hashes.sh:
+// profiles/exact_shape_kernel_hashes.txt); dims() / blank() hand the caller of decode_utterance the shape's Dims and blank index.
+// The run-time values are still there to be looked at: the checked host build of the tests verifies that they are the constants.
+struct ShapeAny {
+  static constexpr bool kExact = false, kFoldLive = false;
+  static constexpr int kBeam = 0, kLabels = 0, kBlank = 0;  // (not read)
+  CTC_HD static const Dims &dims(const Dims &d) { return d; }
+  CTC_HD static int blank(int b) { return b; }
+};
+template <int KC, int VC, int BLANK, bool FOLD_LIVE = false>
+struct ShapeExact {
+  static_assert(KC >= 1 && KC <= kSmallK && VC >= 2 && VC <= kSmallV && BLANK >= 0 && BLANK < VC, "an exact shape lies in the fixed-layout class");
+  static constexpr bool kExact = true, kFoldLive = FOLD_LIVE;
+  static constexpr int kBeam = KC, kLabels = VC, kBlank = BLANK;
+  CTC_HD static Dims dims(const Dims &d) {
+    CTC_ASSUME(d.K == KC && d.V == VC && d.Vc_max == VC && d.use_rank_table == 0 && d.lm == 0);
+    return Dims{KC, VC, VC, 0, 0};
+  }
+  CTC_HD static int blank(int b) { CTC_ASSUME(b == BLANK); return BLANK; }
+};
+
+// The policy travels with the execution policy: X::Shape where X names one (ShapedX), ShapeAny otherwise -- so that the types and
+// the symbols of the builds without one are what they were.
+template <class X, class = void> struct ShapeOf { using type = ShapeAny; };
+template <class X> struct ShapeOf<X, decltype((void)sizeof(typename X::Shape))> { using type = typename X::Shape; };
+template <class X, class S> struct ShapedX : X { using Shape = S; };
+
 // LM: decode with the external scorer (ctc_beam_search_decoder.cpp:74-82,93-95,120-137,173-206; tables: lm_tables.h).
 // LAZY (the wide-beam layouts, whose per-slot info words live in HBM scratch): the info word of a slot -- which label,
 // which kind of candidate, which beam entry -- is a pure function of the slot layout, so it is not stored while the
@@ -466,6 +500,7 @@ struct FullSyncView {
 // FARREP: the exact replay's scratch lives in HBM (carve).  HUGE: more than 65535 candidate slots (carve BIG == 3).
 template <class X, bool IDENT, int SMALLV = 0, bool LM = false, bool LAZY = false, bool FARREP = LAZY, bool HUGE = false, bool WORDLM = false, bool CB = false>
 struct Decoder {
+  using SP = typename ShapeOf<X>::type;  // the shape policy (above)
   using EO = EkOps<HUGE>;
   using Ek = typename EO::E;
   using LrT = typename EO::Pos;
@@ -487,7 +522,7 @@ struct Decoder {
 
   CTC_HD Decoder(X &x_, Work &w_, const Dims &d_, int blank_, PoolNode *pool_, int *pool_up_, int pool_cap_, const uint64_t *tbl_,
                  const ctclm::LmView *lm_ = nullptr)
-      : x(x_), w(w_), d(d_), blank(blank_), pool(pool_), pool_up(pool_up_), pool_thi(pool_up_ + pool_cap_), pool_cap(pool_cap_), tbl(tbl_), lm(lm_) {
+      : x(x_), w(w_), d(SP::dims(d_)), blank(SP::blank(blank_)), pool(pool_), pool_up(pool_up_), pool_thi(pool_up_ + pool_cap_), pool_cap(pool_cap_), tbl(tbl_), lm(lm_) {
     if (LM) {
       const ctclm::DictNode root = lm->dict[0];
       root_lo = (int)root.mask_lo; root_hi = (int)root.mask_hi; root_fc = (int)root.first_child;
@@ -1643,14 +1678,22 @@ struct Decoder {
   // Returns ST_OK or the failure (identical in every thread; also left in VAR_STATUS).
   // `next_cnt` / `next_val`: threads below next_cnt hold a log-probability of the NEXT frame's candidates (the caller's
   // prefetch; both may still be in flight when the step starts): looked at after phase B for danger mode (see note_lp).
+  // FULL (shape policies that fold the live beam size, SP::kFoldLive): the caller has seen that the beam is full, n == K.  Without a
+  // scorer and without pruning a full beam stays full: a frame has N = n (1 + Vnb) - npin candidates, where npin <= n counts the
+  // entries whose parent is in the beam (children that already exist), so n == K gives N >= K Vnb >= K + 1 > K for Vnb >= 1 and
+  // the select keeps min(N, K) = K of them.  The first frames (n = 1, then min(1 + Vnb, K), ...) run the general form.
+  template <bool FULL = false>
   CTC_HD int step(const StepIn &in, bool last, bool stage = false, float stage_val = 0.f, int next_cnt = 0, float next_val = 0.f) {
     select_beams();
     const Beam b = w.cur;
     const Beam nb = w.nxt;
     const int tid = x.tid_fresh(), nt = x.nt();
-    const int n = st_n, pool_count = st_pool;
-    const int K = d.K;
-    const int Vc = in.Vc, brank = in.blank_rank;
+    // (the shape policy's reads are constant-condition selects, not calls: the builds without an exact shape are then the very
+    //  code they were -- a call that is inlined later left the register allocation of five kernels' rare paths elsewhere)
+    const int n = (SP::kFoldLive && FULL) ? SP::kBeam : st_n, pool_count = st_pool;
+    const int K = SP::kExact ? SP::kBeam : d.K;
+    const int Vc = SP::kExact ? SP::kLabels : in.Vc, brank = SP::kExact ? SP::kBlank : in.blank_rank;
+    if (SP::kExact) { CTC_ASSUME(d.K == SP::kBeam && in.Vc == SP::kLabels && in.blank_rank == SP::kBlank); CTC_ASSUME(!FULL || st_n == SP::kBeam); }
     if (SMALLV) { CTC_ASSUME(n >= 1 && n <= kClsK); CTC_ASSUME(Vc >= 1 && Vc <= kClsVc); CTC_ASSUME(d.K <= kClsK); }
     const int Vnb = Vc - (brank >= 0 ? 1 : 0);
     const int S = n * (2 + Vnb);
@@ -2123,6 +2166,7 @@ struct Decoder {
 
     // ---- C: the K-th best key.  #candidates = beam entries + new children - children that already exist as entries
     const int N = LM ? x.uni(pv[P_NCAND]) : n * (1 + Vnb) - x.uni(npin_total);
+    if (FULL) CTC_ASSUME(N > K);  // (the proof above step())
     uint32_t tau = 0, tauc = 0;
     bool exact = false, have_bitmap = false;
     SlotCtx lz;  // LAZY: no info words are stored; whoever needs one derives it from the layout
@@ -2813,6 +2857,8 @@ CTC_HD int decode_utterance(X &x, Work &w, const Dims &d, int blank, const float
                             PoolNode *pool, int *pool_up, int pool_cap, const uint64_t *tbl, const OutRefs *outs, int item,
                             const StreamState *ss = nullptr, const ctclm::LmView *lm = nullptr, const float *raw = nullptr,
                             int raw_log = 1, const int *frames_ready = nullptr) {
+  using SP = typename ShapeOf<X>::type;
+  // (an exact shape's caller hands in the shape's constants: SP::dims / SP::blank)
   if (SMALLV == 1) { CTC_ASSUME(d.K >= 1 && d.K <= kSmallK); CTC_ASSUME(d.V >= 1 && d.V <= kSmallV); CTC_ASSUME(d.Vc_max >= 1 && d.Vc_max <= kSmallV); CTC_ASSUME(blank >= 0 && blank < kSmallV); }
   if (SMALLV == 2) { CTC_ASSUME(d.K >= 1 && d.K <= kMidK); CTC_ASSUME(d.V >= 1 && d.V <= kMidV); CTC_ASSUME(d.Vc_max >= 1 && d.Vc_max <= kMidVc); }
   using Dec0 = Decoder<X, IDENT, SMALLV, LM, LAZY, FARREP, HUGE, WORDLM, CB>;
@@ -2952,7 +2998,13 @@ CTC_HD int decode_utterance(X &x, Work &w, const Dims &d, int blank, const float
     }
     x.tick();
     x.mark(10);
-    const int st = dec.step(in, t == len - 1, stage, pre_lp, next_cnt, next_val);
+    int st;
+    if constexpr (SP::kFoldLive) {  // (the beam is full from its third frame on and stays full: step<FULL>)
+      if (CTC_USUAL(dec.st_n == SP::kBeam)) st = dec.template step<true>(in, t == len - 1, stage, pre_lp, next_cnt, next_val);
+      else st = dec.step(in, t == len - 1, stage, pre_lp, next_cnt, next_val);
+    } else {
+      st = dec.step(in, t == len - 1, stage, pre_lp, next_cnt, next_val);
+    }
     x.mark(12);
     if (LM && CTC_RARE(st == ST_NEED_HOST)) {  // park the utterance in front of this frame; the host fills the cache and resumes it
       dec.lm_resolve_pending();                 // (queues what the pending entries need as well: fewer round trips)

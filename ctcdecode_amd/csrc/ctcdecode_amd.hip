@@ -72,6 +72,28 @@ const KernelEntry *kernel_entry(const KernelKey &k) {
     if (e.key == k) return &e;
   return nullptr;
 }
+// The exact-shape twins of <0, 0, 1, false, 1024, 0, false> (decode_kernel.h CTC_EXACT_SHAPES; compiled in decode_kernel_exact.hip):
+// outside the list the planner chooses from -- decode_common substitutes one for the planned kernel when the call has its shape.
+#define CTC_X_EXACT_EXTERN(CODE_, K_, V_, BLANK_, LIVE_) extern template __global__ void ctcdk::ctc_beam_decode_kernel<CODE_, 0, 1, false, 1024, 0, false>(ctcdk::KernelArgs);
+} namespace ctcdk { CTC_EXACT_SHAPES(CTC_X_EXACT_EXTERN) } namespace {
+#undef CTC_X_EXACT_EXTERN
+struct ExactEntry {
+  int beam, labels, blank;
+  const void *fn;
+};
+#define CTC_X_EXACT_ENTRY(CODE_, K_, V_, BLANK_, LIVE_) {K_, V_, BLANK_, (const void *)ctc_beam_decode_kernel<CODE_, 0, 1, false, 1024, 0, false>},
+const ExactEntry kExactKernels[] = {CTC_EXACT_SHAPES(CTC_X_EXACT_ENTRY)};
+#undef CTC_X_EXACT_ENTRY
+constexpr KernelKey kExactParent{0, 0, 1, 0, 1024, 0, 0};
+// The twin for a call whose planned kernel is `key`, or null: the plain north-star build only, one of the listed shapes exactly,
+// nothing pruned (dims), no scorer (the key), the whole utterance in this launch (no stream state, no resumed launch: `whole`).
+// Rows streamed from the host never get here: their plan is the PROF 4 build.
+const ExactEntry *exact_entry(const KernelKey &key, const Dims &dims, int blank, bool whole) {
+  if (!(key == kExactParent) || !whole || dims.use_rank_table || dims.lm) return nullptr;
+  for (const ExactEntry &e : kExactKernels)
+    if (e.beam == dims.K && e.labels == dims.V && e.labels == dims.Vc_max && e.blank == blank) return &e;
+  return nullptr;
+}
 
 // Compact results (beam_core.h OutRefs::c_*) -> the reference's tensors: tokens / timesteps [B, K, T], zero outside the
 // valid prefixes.  HBM-bound (it writes 8 B per label position of the padded pair).  One workgroup per item; every wave
@@ -252,6 +274,8 @@ struct ctcd_decoder {
   int max_lds = 0;
   int cu_count = 0;
   long long lds_floor = -1;  // CTCD_LDS_FLOOR (experiments): dynamic LDS bytes every decode launch asks for at least
+  int exact_shape = -1;      // ctcd_set_exact_shape: -1 = an exact-shape twin wherever a call qualifies, 0 = never, 1 = required
+  int last_exact = 0;        // ctcd_last_exact_shape: the last launch ran a twin
   int cu_sharing = -1;       // ctcd_set_cu_sharing: 1 = always launch the two-workgroups-per-CU build, 0 = never, -1 = when B > #CUs
   Buf pool, status, tables, logp, lsm, flags, stage_in, stage_out, pr_cnt, pr_ch, pr_lp, pr_ml, far, st_args;
   Buf prune_in, prune_out, st_lens;  // own staging: the host-pointer entry points keep their tensors in stage_in/out
@@ -816,6 +840,13 @@ int ctcd_set_cu_sharing(ctcd_decoder *d, int mode) {
   return CTCD_OK;
 }
 
+int ctcd_set_exact_shape(ctcd_decoder *d, int mode) {
+  if (!d || mode < -1 || mode > 1) return fail(CTCD_EINVAL, "exact shape mode must be -1 (automatic), 0 or 1");
+  d->exact_shape = mode;
+  return CTCD_OK;
+}
+int ctcd_last_exact_shape(const ctcd_decoder *d) { return d ? d->last_exact : -1; }
+
 int ctcd_set_launch_order(ctcd_decoder *d, int mode) {
   if (!d || (mode != CTCD_ORDER_BATCH && mode != CTCD_ORDER_LENGTH)) return fail(CTCD_EINVAL, "launch order must be CTCD_ORDER_BATCH or CTCD_ORDER_LENGTH");
   d->launch_order = mode;
@@ -1068,6 +1099,12 @@ static int decode_common(ctcd_decoder *d, const float *probs, const int32_t *seq
                                       [](const KernelKey &k) { return kernel_entry(k) != nullptr; });
   if (plan.rc) return fail(plan.rc, plan.msg);
   const KernelEntry *kernel = kernel_entry(plan.key);  // (plan_launch plans only what the build's list holds)
+  // an exact-shape twin in the planned kernel's place (same workgroup, same workspace, same arguments); the record of the launch --
+  // ctcd_debug_last_* -- stays the planned key
+  const ExactEntry *exact = d->exact_shape != 0 ? exact_entry(plan.key, dims, blank_id, !sc && !frames_ready) : nullptr;
+  if (d->exact_shape == 1 && !exact)
+    return fail(CTCD_EUNSUPPORTED, "ctcd_set_exact_shape(1): this call does not qualify for an exact-shape kernel (decode_kernel.h CTC_EXACT_SHAPES)");
+  const void *kernel_fn = exact ? exact->fn : kernel->fn;
   const int threads = plan.threads;
   size_t lds = plan.lds;
   const size_t far_bytes = plan.far_bytes;
@@ -1241,7 +1278,7 @@ static int decode_common(ctcd_decoder *d, const float *probs, const int32_t *seq
   a.far = (char *)d->far.p; a.far_stride = (long long)far_bytes;
   // (CTCD_LDS_FLOOR: experiments with the occupancy the LDS request allows)
   if (d->lds_floor >= 0) lds = std::max(lds, std::min((size_t)d->lds_floor, (size_t)d->max_lds - 2048));
-  HIP_TRY(hipFuncSetAttribute(kernel->fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  HIP_TRY(hipFuncSetAttribute(kernel_fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   // launch order (ctcd_set_launch_order): the one-shot entry points, and every launch of a one-shot decode through a callback scorer
   // (a resumed launch by the frames each utterance has left; the debug copy shows the first launch's order); streaming calls keep
   // batch order.  The order pass runs on the same stream, from the lengths already on the device: nothing waits for the host.
@@ -1263,8 +1300,9 @@ static int decode_common(ctcd_decoder *d, const float *probs, const int32_t *seq
     if (records) HIP_TRY(hipEventRecord(d->ev_order, stream));
   }
   void *kargs[] = {&a};
-  HIP_TRY(hipLaunchKernel(kernel->fn, dim3(B), dim3(threads), kargs, lds, stream));
+  HIP_TRY(hipLaunchKernel(kernel_fn, dim3(B), dim3(threads), kargs, lds, stream));
   HIP_TRY(hipGetLastError());
+  d->last_exact = exact ? 1 : 0;
   d->last_kernel = kernel;  // (recorded once the launch is queued: a launch that failed leaves the last record)
   if (d->timing) HIP_TRY(hipEventRecord(d->ev1, stream));
   if (records) d->last_order_items = by_length ? B : 0;  // (set once the launch is queued: a call that failed leaves the last record)

@@ -917,8 +917,30 @@ struct KernelArgs {
 // LM: 0 = no scorer, 1 = any scorer, 2 = word model over at most 64 labels (the character-model and wide-dictionary
 // branches are not compiled in: beam_core.h WORDLM), 3 = any scorer behind the host-side hook (beam_core.h CB: the tables are a
 // cache of a callback's answers; a miss parks the utterance).
-template <int PROF, int BIG, int LAYOUT, bool PRUNED, int NT = 0, int LM = 0, bool OCC2 = false>
+// Exact-shape twins (beam_core.h ShapeExact): PROF codes from kExactProf0 on name builds of the plain north-star kernel -- PROF 0, fixed
+// layout, unpruned, 1024 threads, no scorer, one workgroup per CU, rows resident in HBM -- cut for ONE shape, whose beam width, label
+// count and blank index are constants of the frame loop.  One line per shape: X(PROF code, beam, labels, blank, fold the live beam size).
+// They stay outside CTC_KERNEL_LIST (the planner does not know them): decode_kernel_exact.hip instantiates them and ctcdecode_amd.hip
+// substitutes one for the planned kernel <0, 0, 1, false, 1024, 0, false> when the call has exactly its shape.
+constexpr int kExactProf0 = 6;
+#if defined(CTC_EXACT_STAGE1)  // (measurement builds: the twin without the live beam size folded)
+#define CTC_EXACT_SHAPES(X) X(6, 100, 29, 0, false)
+#else
+#define CTC_EXACT_SHAPES(X) X(6, 100, 29, 0, true)
+#endif
+template <int PROF> struct ShapeOfProf { using type = ctcbeam::ShapeAny; };
+#define CTC_X_SHAPE(CODE_, K_, V_, BLANK_, LIVE_) template <> struct ShapeOfProf<CODE_> { using type = ctcbeam::ShapeExact<K_, V_, BLANK_, LIVE_>; };
+CTC_EXACT_SHAPES(CTC_X_SHAPE)
+#undef CTC_X_SHAPE
+// (the frame loop finds the policy through its execution policy's type: beam_core.h ShapeOf)
+template <class XB, class S, bool EXACT> struct XWithShape { using type = XB; };
+template <class XB, class S> struct XWithShape<XB, S, true> { using type = ctcbeam::ShapedX<XB, S>; };
+
+template <int PROF_, int BIG, int LAYOUT, bool PRUNED, int NT = 0, int LM = 0, bool OCC2 = false>
 __global__ void __launch_bounds__(1024, OCC2 ? 8 : 1) ctc_beam_decode_kernel(KernelArgs a) {
+  using SP = typename ShapeOfProf<PROF_>::type;
+  constexpr int PROF = SP::kExact ? 0 : PROF_;  // (an exact-shape twin is the PROF 0 build in everything but its shape policy)
+  static_assert(!SP::kExact || (BIG == 0 && LAYOUT == 1 && !PRUNED && NT == 1024 && LM == 0 && !OCC2), "exact shapes: twins of <0, 0, 1, false, 1024, 0, false>");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   __shared__ uint64_t tbl[64];
   __shared__ int red[32];
@@ -962,7 +984,7 @@ __global__ void __launch_bounds__(1024, OCC2 ? 8 : 1) ctc_beam_decode_kernel(Ker
   constexpr int XP = PROF == 4 ? 0 : PROF == 5 ? 3 : PROF;
   // (launch_plan.h plan_launch swaps a build for which this holds for its twin when the rows are streamed)
   constexpr bool kNoStreamedInput = ignores_streamed_input(kKey);
-  DevX<XP, BIG != 0, NT> x{red, 0, prof, 0, (PROF == 1 && a.dbg && b == 0) ? a.dbg : nullptr, 1 + 4 * a.K,
+  typename XWithShape<DevX<XP, BIG != 0, NT>, SP, SP::kExact>::type x{red, 0, prof, 0, (PROF == 1 && a.dbg && b == 0) ? a.dbg : nullptr, 1 + 4 * a.K,
                     (PROF == 2 && b == 0 && a.tl) ? tlbuf : nullptr, tlcnt, kTlCap, a.tl_f0, a.tl_nf, b};
   int len = a.seq_lens ? __builtin_amdgcn_readfirstlane(a.seq_lens[b]) : a.T;
   len = len < 0 ? 0 : (len > a.T ? a.T : len);  // binding.cpp:64-65
@@ -1048,6 +1070,10 @@ __global__ void __launch_bounds__(1024, OCC2 ? 8 : 1) ctc_beam_decode_kernel(Ker
       fo += (size_t)consumed;
       len -= consumed;
     }
+  } else if constexpr (SP::kExact) {
+    // (the twin: dims and blank index are the shape's constants, and nothing of a stream, a scorer or streamed rows is compiled in)
+    st = decode_utterance<true, 1>(x, w, SP::dims(a.dims), SP::blank(a.blank), a.probs + ((size_t)b * a.T + f0) * SP::kLabels, (const PrunedRows *)nullptr, len,
+                                   pool, pool_up, pool_cap, tbl, outs, b);
   } else {
   st = decode_utterance<!PRUNED, (LAYOUT == 3 ? 0 : LAYOUT), LM != 0, BIG != 0, BIG != 0 || OCC2, BIG == 3, LM == 2, LM == 3>(x, w, a.dims, a.blank, PRUNED ? nullptr : a.probs + ((size_t)b * a.T + f0) * a.V,
                                   PRUNED ? &prow : (const PrunedRows *)nullptr, len, pool, pool_up, pool_cap, tbl, outs, b,

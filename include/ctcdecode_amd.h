@@ -922,6 +922,15 @@ int ctcd_set_threads(ctcd_decoder *dec, int threads_per_workgroup); /* 0 = autom
  * workgroup runs ~7 % slower in it, two on a CU together 1.4-1.5x faster.  mode = -1 (default): used when a batch has
  * more utterances than the device has CUs; 1: always (a serving loop that keeps several launches in flight); 0: never. */
 int ctcd_set_cu_sharing(ctcd_decoder *dec, int mode);
+/* Exact-shape kernels.  The plain north-star build (beam <= 128, <= 32 labels, no pruning, no scorer, 1024 threads, one workgroup per
+ * CU, rows resident on the device) has twins cut for ONE shape each, in which beam width, label count and blank index are constants
+ * of the frame loop: today beam 100 over 29 labels with the blank at index 0 -- the reference's default beam_width over the English
+ * grapheme set.  Results are bit-identical.  mode = -1 (default): a twin runs wherever a whole-utterance call has exactly its shape
+ * (not streams, not resumed launches, not rows streamed from the host, not when another build of the class is planned); 0: never;
+ * 1: required -- a call that does not qualify returns CTCD_EUNSUPPORTED and launches nothing.  ctcd_last_exact_shape: whether the
+ * last launch ran a twin (0 / 1; -1: dec == NULL).  ctcd_debug_last_kernel / _layout keep reporting the planned kernel. */
+int ctcd_set_exact_shape(ctcd_decoder *dec, int mode);
+int ctcd_last_exact_shape(const ctcd_decoder *dec);
 /* The north-star class of shapes (beam <= 128, <= 32 labels, no scorer) has a second build of its kernel whose phase A1 settles
  * four subtrees per wavefront at once: beams shaped like chains -- what blank-dominated rows, i.e. real acoustic posteriors,
  * produce: some twenty entries with descendants in the beam per frame -- decode 7 % faster with it, bushy beams (random rows:
