@@ -2,16 +2,25 @@
 
 Shared by test_exact_shape_host.py (the exact policy of beam_core.h on the CPU, against the run-time policy and the oracle) and
 test_gpu_exact_shape.py (the twin kernel against the planned kernel and the oracle, over the same inputs).  No torch here: the CPU
-suite imports this module.  Every shape is the twin's own at T <= 64, B <= 8."""
+suite imports this module.  Every shape is the twin's own at T <= 64, B <= 8.  matrix_case() / matrix_inputs() are the kernel
+matrix's recipe at the twin's shape (the select-path certificate, with overflow frames); SHAPES / parse_exact_shapes() tie the
+tests to the header's list of shapes."""
 import ctypes
 import os
 import subprocess
 
 import numpy as np
 
+import kernel_matrix_util as km
 import oracle_util as ou
+import select_path_util as sp
+import stream_matrix_util as sm
 
 BEAM, LABELS, BLANK = 100, 29, 0
+# The table the tests cover, as decode_kernel.h CTC_EXACT_SHAPES lists it: (PROF code, beam, labels, blank, fold the live beam size).
+# test_exact_shape_host.py holds the header to it: a further shape fails there until the tests have been taught about it.
+SHAPES = [(6, 100, 29, 0, True)]
+PARENT_KERNEL = (0, 0, 1, 0, 1024, 0, 0)  # the planned kernel a twin replaces (ctcdecode_amd.hip kExactParent)
 KINDS = ["randn", "blank", "peaky", "quant", "minus_inf"]
 LENGTHS = [0, 1, 2, 3, 5, 40]
 RAGGED_T = 40
@@ -65,6 +74,37 @@ def cases():
     return out
 
 
+def parse_exact_shapes(header_text):
+    """The X(code, beam, labels, blank, fold) items of the product branch of CTC_EXACT_SHAPES (the #else branch, not the
+    CTC_EXACT_STAGE1 measurement build) -> list of (int, int, int, int, bool), in the order of the list."""
+    import re
+
+    m = re.search(r"#if defined\(CTC_EXACT_STAGE1\).*?\n#else\s*\n#define CTC_EXACT_SHAPES\(X\)(.*?)\n#endif", header_text, flags=re.S)
+    assert m, "the product branch of CTC_EXACT_SHAPES was not found"
+    words = {"true": True, "false": False}
+    out = []
+    for it in re.findall(r"\bX\(([^)]*)\)", m.group(1)):
+        args = [a.strip() for a in it.split(",")]
+        assert len(args) == 5 and args[4] in words, it
+        out.append(tuple(int(a) for a in args[:4]) + (words[args[4]],))
+    return out
+
+
+def matrix_case():
+    """The kernel matrix's recipe (kernel_matrix_util.inputs) at the twin's shape: the planned kernel's case with 29 labels, beam 100,
+    blank 0.  The twin is outside CTC_KERNEL_LIST and so outside kernel_matrix_util.CASES; this is the case it would have there."""
+    c = km._case(PARENT_KERNEL, V=LABELS, K=BEAM, T=40, B=4, threads=1024, blank=BLANK)
+    c["seed"] = 9100
+    return c
+
+
+def matrix_inputs(overflow_as_inf=False):
+    """km.inputs of matrix_case(): item 0 the full length, item 1 one frame, item 2 quantised to 0.5 (ties across the beam boundary),
+    item 3 with -3e38 in frames 2 and 3 (adding the second overflows every score to -inf: danger mode from finite inputs) and -inf at
+    frame 26 -> (lp [4, 40, 29], seq_lens [4])."""
+    return km.inputs(matrix_case(), overflow_as_inf=overflow_as_inf)
+
+
 def build_exact_host():
     """tests/native/exact_shape_host.cpp, compiled the way oracle_util.build_core_host compiles core_host.cpp (checked assumptions)."""
     src = os.path.join(ou.ROOT, "tests", "native", "exact_shape_host.cpp")
@@ -79,7 +119,7 @@ def build_exact_host():
     return EXACT_HOST_SO
 
 
-EVENTS = ["EV_FRAMES", "EV_EXACT", "EV_SPEC_OK", "EV_SPEC_UNDER", "EV_SPEC_OVER", "EV_SPEC_OTHER", "EV_TIE_FRAMES"]
+EVENTS = list(sp.COUNTERS)  # the counters of the select-path certificate (select_path_util.COUNTERS), by their place in enum Event
 
 
 def decode_host(lp, seq_lens, stage):
@@ -104,7 +144,9 @@ def decode_host(lp, seq_lens, stage):
                                  p(ln, ou._i32p), p(nres, ou._i32p), ev)
     if rc != 1:
         raise RuntimeError("exact-shape host twin returned %d" % rc)
-    return dict(tokens=tok, timesteps=ts, scores=sc, lens=ln, nres=nres), dict((name, int(ev[ids[i]])) for i, name in enumerate(EVENTS))
+    idx = dict((name, sm.event_index(name)) for name in EVENTS)
+    assert all(0 <= i < len(ev) for i in idx.values())
+    return dict(tokens=tok, timesteps=ts, scores=sc, lens=ln, nres=nres), dict((name, int(ev[i])) for name, i in idx.items())
 
 
 _ORACLE = {}

@@ -25,6 +25,7 @@ def main():
 
     rng = np.random.default_rng(a.seed)
     stats = np.zeros(5, np.int64)
+    twin_cases = 0  # one-shot cases that the exact-shape twin decoded (next to the planned kernel)
     for it in range(a.n):
         V = int(rng.choice([2, 3, 5, 9, 29, 29, 64, 200]))
         K = int(rng.choice([1, 2, 5, 16, 50, 100, 128, 300]))
@@ -36,6 +37,11 @@ def main():
         top_n = int(rng.choice([40, 40, 40, max(1, V // 2), 3]))
         cutoff = float(rng.choice([1.0, 1.0, 1.0, 0.5, 0.99]))
         threads = int(rng.choice([64, 128, 256, 512, 1024]))
+        if it % 40 == 0 and not a.degenerate:
+            # every fortieth iteration is the shape of the exact-shape twin (decode_kernel.h CTC_EXACT_SHAPES), which the draws above
+            # all but never give: beam 100 over 29 labels, blank 0, nothing pruned, 1024 threads, one-shot with the fixed layout
+            # (it % 4 == 0).  Set after every draw of the iteration, so that the other iterations keep their configurations.
+            V, K, blank, top_n, cutoff, threads = 29, 100, 0, 40, 1.0, 1024
         if K * (min(V, top_n) + 2) > 60000:
             continue
         lp = ou.synth_logprobs(B, T, V, 7000 + it, quant=quant, blank_bias=bias, blank_id=blank)
@@ -57,8 +63,30 @@ def main():
             dec.set_threads(threads)
             if it % 4 == 2:
                 dec.set_fixed_layout(False)
-            out, sc, ts, ln = dec.decode(torch.from_numpy(lp), torch.from_numpy(sl) if sl is not None else None)
-            got = dict(tokens=out.numpy(), timesteps=ts.numpy(), scores=sc.numpy(), lens=ln.numpy(), nres=want["nres"])
+            # the shape of the exact-shape twin: decoded by the twin (required: a call that does not qualify is refused) and by the
+            # planned kernel, the two compared with each other here and each with the oracle below; the tag says which ran
+            twin_shape = (V == 29 and K == 100 and blank == 0 and top_n >= V and cutoff == 1.0 and threads == 1024 and it % 4 == 0)
+            others = []
+            for mode in ((1, 0) if twin_shape else (-1,)):
+                dec.set_exact_shape(mode)
+                out, sc, ts, ln = dec.decode(torch.from_numpy(lp), torch.from_numpy(sl) if sl is not None else None)
+                ran = dec.last_exact_shape()
+                if ran != (1 if twin_shape and mode else 0):
+                    print("MISMATCH", tag, "set_exact_shape(%d) ran %s" % (mode, "the twin" if ran else "the planned kernel"), flush=True)
+                    sys.exit(1)
+                others.append((dict(tokens=out.numpy(), timesteps=ts.numpy(), scores=sc.numpy(), lens=ln.numpy(), nres=want["nres"]),
+                               tag + (" kernel=twin" if ran else " kernel=planned")))
+            (got, tag), others = others[-1], others[:-1]
+            for other, other_tag in others:
+                try:
+                    ou.assert_same(other, want, other_tag)
+                    for k in ("tokens", "timesteps", "lens"):
+                        assert np.array_equal(other[k], got[k]), "the twin and the planned kernel differ: " + k
+                    assert np.array_equal(other["scores"].view(np.uint32), got["scores"].view(np.uint32)), "the twin and the planned kernel differ: scores"
+                except AssertionError as e:
+                    print("MISMATCH", other_tag, str(e)[:200], flush=True)
+                    sys.exit(1)
+                twin_cases += 1
         else:  # streaming with random chunk boundaries
             dec = ctcdecode_amd.OnlineCTCBeamDecoder(labels, cutoff_top_n=top_n, cutoff_prob=cutoff, beam_width=K, blank_id=blank, log_probs_input=True)
             states = [ctcdecode_amd.DecoderState(dec) for _ in range(B)]
@@ -80,6 +108,7 @@ def main():
             print("MISMATCH", tag, str(e)[:200], flush=True)
             sys.exit(1)
     print("ok: %d configurations, oracle stats (steps, tie splits, revivals, child hits, lpc updates) = %s" % (a.n, stats.tolist()))
+    print("%d of them had the exact-shape twin's shape and were decoded by the twin and by the planned kernel" % twin_cases)
 
 
 if __name__ == "__main__":

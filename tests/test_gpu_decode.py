@@ -20,7 +20,10 @@ def torch_mod():
 
 
 def _decode(torch, probs, seq_lens=None, beam=100, cutoff_prob=1.0, cutoff_top_n=40, blank_id=0, log_input=True, threads=None,
-            host_entry=False, fixed_layout=True):
+            host_entry=False, fixed_layout=True, exact=None, streamed_rows=None):
+    """exact: set_exact_shape(exact) -- 0 the planned kernel, 1 its exact-shape twin required (beam 100 / 29 labels / blank 0);
+    streamed_rows: False uploads the rows whole (a CPU tensor of a megabyte or more with T >= 128 otherwise crosses PCIe while the
+    PROF 4 build of the kernel runs, which has no twin).  The result says which ran: `exact` (last_exact_shape) and `kernel`."""
     import ctcdecode_amd
 
     V = probs.shape[2]
@@ -30,8 +33,13 @@ def _decode(torch, probs, seq_lens=None, beam=100, cutoff_prob=1.0, cutoff_top_n
         dec.set_threads(threads)
     if not fixed_layout:
         dec.set_fixed_layout(False)
+    if exact is not None:
+        dec.set_exact_shape(exact)
+    if streamed_rows is not None:
+        dec.set_host_path(input_streaming=streamed_rows)
     out, sc, ts, ln = dec.decode(torch.from_numpy(np.ascontiguousarray(probs)), torch.from_numpy(seq_lens) if seq_lens is not None else None)
-    return dict(tokens=out.numpy(), timesteps=ts.numpy(), scores=sc.numpy(), lens=ln.numpy(), layout=dec.last_layout())
+    return dict(tokens=out.numpy(), timesteps=ts.numpy(), scores=sc.numpy(), lens=ln.numpy(), layout=dec.last_layout(),
+                exact=dec.last_exact_shape(), kernel=dec.last_kernel())
 
 
 def _with_nres(got, want):
@@ -202,21 +210,40 @@ def test_randomised_stress_subset(torch_mod):
     r = subprocess.run([_sys.executable, os.path.join(os.path.dirname(os.path.abspath(__file__)), "sweeps", "gpu_stress.py"),
                         "--n", "120", "--seed", "5"], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    # (iterations 0, 40 and 80 have the exact-shape twin's shape: decoded by the twin and by the planned kernel, each asserted there)
+    assert "3 of them had the exact-shape twin's shape" in r.stdout, r.stdout[-500:]
 
 
 def test_north_star_shape_parity_and_properties(torch_mod):
     """BASELINE.json configs[1]: B=256, T=1000, V=29, beam=100.  ALL 256 items bit-exact against the real reference
     (oracle/_ref, one host thread per core: ~20 s on the GPU box; the restatement stands in where it is not built),
-    size-independent properties on all of them, and run-to-run determinism."""
+    size-independent properties on all of them, and run-to-run determinism.
+
+    Three kernels decode this shape, and each is held against the oracle here on all 256 items, saying which it is: the exact-shape
+    twin (set_exact_shape(1): required), the planned kernel <0,0,1,false,1024,0,false> it replaces (set_exact_shape(0)) -- both with
+    the rows uploaded whole, and equal to each other bit for bit -- and, as decode() of a CPU tensor of this size runs by default,
+    the PROF 4 build that reads the rows while they cross PCIe (no twin).  Determinism and the properties: on the twin's result."""
     B, T, V, K = 256, 1000, 29, 100
     lp = ou.synth_logprobs(B, T, V, 2024)
-    got = _decode(torch_mod, lp, beam=K)
-    again = _decode(torch_mod, lp, beam=K)
+    got = _decode(torch_mod, lp, beam=K, exact=1, streamed_rows=False)
+    again = _decode(torch_mod, lp, beam=K, exact=1, streamed_rows=False)
     for k in got:
         assert np.array_equal(got[k], again[k]), "non-deterministic " + k
+    assert got["exact"] == 1 and got["kernel"] == (0, 0, 1, 0, 1024, 0, 0), (got["exact"], got["kernel"])
     which = "reference" if ou.have_reference() else "restated"
     want = ou.decode(lp, beam=K, which=which, threads=os.cpu_count())
-    ou.assert_same(_with_nres(got, want), want, "north-star, all items vs " + which)
+    ou.assert_same(_with_nres(got, want), want, "north-star (the exact-shape twin), all items vs " + which)
+    parent = _decode(torch_mod, lp, beam=K, exact=0, streamed_rows=False)
+    assert parent["exact"] == 0 and parent["kernel"] == got["kernel"], (parent["exact"], parent["kernel"])
+    ou.assert_same(_with_nres(parent, want), want, "north-star (the planned kernel), all items vs " + which)
+    for k in ("tokens", "timesteps", "lens"):
+        assert np.array_equal(got[k], parent[k]), "the twin and the planned kernel differ: " + k
+    assert np.array_equal(got["scores"].view(np.uint32), parent["scores"].view(np.uint32)), "the twin and the planned kernel differ: scores"
+    del parent, again
+    streamed = _decode(torch_mod, lp, beam=K)  # (as an unmodified caller runs it: streamed rows)
+    assert streamed["exact"] == 0 and streamed["kernel"] == (4, 0, 1, 0, 1024, 0, 0), (streamed["exact"], streamed["kernel"])
+    ou.assert_same(_with_nres(streamed, want), want, "north-star (streamed rows), all items vs " + which)
+    del streamed
     lens, sc, tok, ts = got["lens"], got["scores"], got["tokens"], got["timesteps"]
     assert (np.diff(sc, axis=1) >= 0).all(), "beam_scores must ascend (best first)"
     assert (lens >= 0).all() and (lens <= T).all()
@@ -384,13 +411,21 @@ def test_degenerate_inputs_follow_the_reference_argument_order(torch_mod, thread
 
 
 def test_degenerate_frames_inside_the_north_star_shape(torch_mod):
-    """-inf tail padding without seq_lens and a -inf frame in the middle at full size (T=1000, V=29, beam 100)."""
+    """-inf tail padding without seq_lens and a -inf frame in the middle at full size (T=1000, V=29, beam 100): through the planned
+    kernel (set_exact_shape(0)) and through its exact-shape twin (required), each asserted."""
     lp = ou.synth_logprobs(4, 1000, 29, 77)
     lp[0, 700:, :] = -np.inf
     lp[1, 500, :] = -np.inf
     lp[2, 100:104, :] = -3.0e38
     want = ou.decode(lp, beam=100, which="reference" if ou.have_reference() else "restated")
-    ou.assert_same(_with_nres(_decode(torch_mod, lp, beam=100), want), want)
+    res = {}
+    for exact in (0, 1):
+        res[exact] = got = _decode(torch_mod, lp, beam=100, exact=exact)
+        assert got["exact"] == exact and got["kernel"] == (0, 0, 1, 0, 1024, 0, 0), (exact, got["exact"], got["kernel"])
+        ou.assert_same(_with_nres(got, want), want, "the exact-shape twin" if exact else "the planned kernel")
+    for k in ("tokens", "timesteps", "lens"):
+        assert np.array_equal(res[0][k], res[1][k]), "the twin and the planned kernel differ: " + k
+    assert np.array_equal(res[0]["scores"].view(np.uint32), res[1]["scores"].view(np.uint32))
 
 
 def test_two_workgroups_per_cu_build(torch_mod):
@@ -400,12 +435,16 @@ def test_two_workgroups_per_cu_build(torch_mod):
     import ctcdecode_amd
     import degenerate_util as du
 
-    def run(lp, sl=None, mode=1, **kw):
+    def run(lp, sl=None, mode=1, exact=None, **kw):
         V = lp.shape[2]
         d = ctcdecode_amd.CTCBeamDecoder([str(i) for i in range(V)], cutoff_top_n=kw.get("cutoff_top_n", 40), beam_width=kw["beam"],
                                          blank_id=kw.get("blank_id", 0), log_probs_input=True, device="cuda:0")
         d.set_cu_sharing(mode)
+        if exact is not None:
+            d.set_exact_shape(exact)
         out, sc, ts, ln = d.decode(torch_mod.from_numpy(lp), torch_mod.from_numpy(sl) if sl is not None else None)
+        if exact is not None:
+            assert d.last_exact_shape() == exact and d.last_kernel() == (0, 0, 1, 0, 1024, 0, 0), (d.last_exact_shape(), d.last_kernel())
         return dict(tokens=out.numpy(), timesteps=ts.numpy(), scores=sc.numpy(), lens=ln.numpy())
 
     for c in CASES:
@@ -433,7 +472,9 @@ def test_two_workgroups_per_cu_build(torch_mod):
     lp = ou.synth_logprobs(ncu + 44, 40, 29, 323, quant=1.0)
     want = ou.decode(lp, beam=100)
     ou.assert_same(_with_nres(run(lp, mode=-1, beam=100), want), want, "B > #CUs")
-    ou.assert_same(_with_nres(run(lp, mode=0, beam=100), want), want, "B > #CUs, default build")
+    # (beam 100 / 29 labels / blank 0 on the default build: the planned kernel, asserted -- its exact-shape twin runs this batch in
+    #  test_gpu_exact_shape.py::test_more_workgroups_than_cus)
+    ou.assert_same(_with_nres(run(lp, mode=0, exact=0, beam=100), want), want, "B > #CUs, default build")
 
 
 def test_time_steps_beyond_16_bits(torch_mod):

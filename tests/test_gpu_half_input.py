@@ -83,15 +83,30 @@ def _oracle_check(x, got, kind, **kw):
 @pytest.mark.parametrize("dtype", HALVES)
 @pytest.mark.parametrize("kind", KINDS)
 def test_unpruned_north_star_class(torch_mod, dtype, kind):
+    """Beam 100 over 29 labels, blank 0: the shape of the exact-shape twin (ctcd_set_exact_shape).  Log-probability rows run in both
+    modes -- the planned kernel (0) and the twin required (1) -- and say which ran; probabilities and logits run as a caller gets
+    them (test_gpu_exact_shape.py::test_rows_that_pass_a_prepass_first holds both kernels behind those pre-passes)."""
     x = _rows(torch_mod, 8, 300, 29, 11, kind, dtype)
     dec = _decoder(29, kind, beam_width=100)
-    got = _np(dec.decode_device(x))
-    assert _in_dtype(dec) == (1 if dtype == "float16" else 2)
-    want = _np(dec.decode_device(x.float()))
-    assert _in_dtype(dec) == 0
-    _assert_bits(got, want, "%s %s" % (dtype, kind))
-    if kind == "logp" and dtype == "bfloat16":
-        _oracle_check(x[:2], _np(dec.decode_device(x[:2])), kind, beam=100)
+    dec.set_subtree_search(0)  # (the automatic choice follows the last checked launch: every call here plans the plain build)
+    res = {}
+    for mode in ((0, 1) if kind == "logp" else (-1,)):
+        dec.set_exact_shape(mode)
+        got = _np(dec.decode_device(x))
+        assert _in_dtype(dec) == (1 if dtype == "float16" else 2)
+        ran = dec.last_exact_shape()
+        want = _np(dec.decode_device(x.float()))
+        assert _in_dtype(dec) == 0
+        assert ran == dec.last_exact_shape() == (1 if mode else 0), (mode, ran, dec.last_exact_shape())
+        _assert_bits(got, want, "%s %s, exact-shape mode %d" % (dtype, kind, mode))
+        res[mode] = got
+    if kind == "logp":
+        _assert_bits(res[1], res[0], "%s %s: the twin against the planned kernel" % (dtype, kind))
+        if dtype == "bfloat16":
+            for mode in (0, 1):
+                dec.set_exact_shape(mode)
+                _oracle_check(x[:2], _np(dec.decode_device(x[:2])), kind, beam=100)
+                assert dec.last_exact_shape() == mode
 
 
 @pytest.mark.parametrize("V", [10000, 1001])
