@@ -828,6 +828,18 @@ class CTCBeamDecoder(object):
         """Test hook: the workgroups the last ``align`` launched."""
         return int(_native.lib.ctcd_last_align_grid(self._handle))
 
+    def set_long_rows(self, band=4096):
+        """Long rows for ``align`` and ``log_likelihood`` (include/ctcdecode_amd.h ctcd_set_long_rows): with a band of 256, 1024 or 4096
+        states, rows of up to 2^20 - 1 labels are accepted -- a row of more than ``band`` states (2 x labels + 1) runs in bands of that
+        many -- instead of 2047; 0 turns the mode off (the default).  The band width never changes a result.  ``align`` then needs
+        about ``T x (min(L, T) / 2 + 16)`` bytes of scratch per row in flight (``set_align_scratch``).  ``label_posteriors`` keeps its limit.
+        Raises ``ValueError`` for any other band."""
+        _native.check(_native.lib.ctcd_set_long_rows(self._handle, int(band)))
+
+    def last_long_rows(self):
+        """The band of the banded kernel that the last ``align`` or ``log_likelihood`` launched; 0 if it launched none."""
+        return int(_native.lib.ctcd_last_long_rows(self._handle))
+
     def log_likelihood(self, probs, seq_lens, beam_results, out_lens):
         """The CTC log-likelihood on the device (include/ctcdecode_amd.h "CTC log-likelihood"): for every row
         ``beam_results[b, r, :out_lens[b, r]]``, ``log P(y | x)`` -- the sum over ALL alignments of its labels through the rows

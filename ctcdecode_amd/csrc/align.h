@@ -94,6 +94,24 @@ CTC_HD long long align_grid(long long rows, long long budget, size_t slot_bytes)
 // states per lane of a hypothesis the whole workgroup runs
 CTC_HD int align_npl(int S) { return S <= kAlignThreads ? 1 : (S <= kAlignThreads * 4 ? 4 : 16); }
 
+// ---- long rows (ctcd_set_long_rows): a row of S > W states runs in bands of W = 256 * NPL states ------------------------------------
+// Band j holds the states [jW, min((j + 1)W, S)) and walks all frames; of band j - 1 it needs that band's last two states at every
+// frame: an edge column of T pairs (d[t][jW - 1], d[t][jW - 2]), 8 bytes each.  A workgroup has two columns and the bands of a row
+// take them in turn: band j writes column j & 1 and reads column (j - 1) & 1.
+constexpr int kAlignLongMaxLabels = (1 << 20) - 1;  // min(L_stride, T) with long rows on (no 32-bit quantity of the walk binds earlier)
+CTC_HD bool band_ok(int band) { return band == kAlignThreads || band == kAlignThreads * 4 || band == kAlignThreads * 16; }
+CTC_HD int band_count(int S, int band) { return (S + band - 1) / band; }
+CTC_HD int band_first_state(int j, int band) { return j * band; }
+CTC_HD size_t edge_col_bytes(int T) { return (size_t)T * 8; }
+// the alignment's slot: its back-pointer rows, then the two columns
+CTC_HD size_t align_long_slot_bytes(int T, int L_stride) { return align_slot_bytes(T, L_stride) + 2 * edge_col_bytes(T); }
+CTC_HD size_t align_edge_offset(int T, int L_stride, int parity) { return align_slot_bytes(T, L_stride) + (size_t)parity * edge_col_bytes(T); }
+// the log-likelihood's slot: the two columns only
+CTC_HD size_t loglik_long_slot_bytes(int T) { return 2 * edge_col_bytes(T); }
+CTC_HD size_t loglik_edge_offset(int T, int parity) { return (size_t)parity * edge_col_bytes(T); }
+// the band a launch runs banded rows at: `band` if the mode is on and the shape admits a row beyond it, else 0 (no banded kernel)
+CTC_HD int launch_band(int band, int T, int L_stride) { return band > 0 && n_states(align_lmax(T, L_stride)) > band ? band : 0; }
+
 // ---- row validation --------------------------------------------------------------------------------------------------------------
 CTC_HD bool len_ok(int L, int L_stride) { return L >= 0 && L <= L_stride; }
 CTC_HD bool label_ok(int c, int V, int blank) { return (unsigned)c < (unsigned)V && c != blank; }
@@ -174,6 +192,7 @@ struct AlignDecoderInfo {
   int device;
   int in_dtype;
   long long budget;  // ctcd_set_align_scratch (0: the default)
+  int band;          // ctcd_set_long_rows (0: off)
 };
 
 }  // namespace ctcalign
@@ -186,14 +205,16 @@ namespace ctcalign {
 // What ctcd_ctc_align and ctcd_ctc_loglik do alike before their launch (align.hip): the checks of the arguments they share -- `fn`, the
 // entry point's name, stands in the messages; `outputs`: its output tensors are there -- the decoder's info, its device entered
 // through `guard`, and for raw logits the log-softmax pass.  -> CTCD_OK with e filled in (rows == 0: nothing to do), or the failure.
+// long_rows: the entry point has a banded kernel, so ctcd_set_long_rows lifts its limit on min(L_stride, T).
 struct AlignEntry {
   long long rows;     // B * R
+  int band;           // launch_band: the band of the banded kernel this call launches, 0 if it launches none
   const void *probs;  // the rows to read, of element type `dtype`, log-probabilities unless log_input == 0
   int dtype;
   AlignDecoderInfo inf;
 };
 int align_entry(const char *fn, ctcd_decoder *d, const void *probs, const int32_t *seq_lens, int B, int T, int V, int blank_id, int log_input, const int32_t *tokens,
-                const int32_t *lens, int R, int L_stride, bool outputs, void *stream, ctcdev::DeviceGuard *guard, AlignEntry *e);
+                const int32_t *lens, int R, int L_stride, bool outputs, void *stream, ctcdev::DeviceGuard *guard, AlignEntry *e, bool long_rows = false);
 int align_decoder_info(const ctcd_decoder *d, AlignDecoderInfo *out);
 int align_fail(int code, const char *msg);
 // the decoder's back-pointer scratch, grown to `bytes`
@@ -201,4 +222,5 @@ int align_scratch(ctcd_decoder *d, size_t bytes, void **p);
 // raw logits: the log-softmax pass (ctcd_log_softmax) into decoder-owned float32 rows
 int align_lsm_rows(ctcd_decoder *d, const void *logits, const int32_t *seq_lens, int B, int T, int V, void *stream, const float **rows);
 void align_note_grid(ctcd_decoder *d, long long grid);  // ctcd_last_align_grid
+void align_note_band(ctcd_decoder *d, int band);        // ctcd_last_long_rows
 }  // namespace ctcalign

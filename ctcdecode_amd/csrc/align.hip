@@ -5,6 +5,9 @@
 //                                     back-pointers.  The walk over the rows, their classes (CLS) and the walk over a row's frames are
 //                                     lattice_device.h's, shared with loglik.hip; here are what a cell records (its back-pointer), what
 //                                     is kept of a frame (the back-pointer words) and what follows the last one (the back-trace).
+//   ctc_align_banded_kernel<DT, PROB, NPL>   long rows (ctcd_set_long_rows): the rows of more than W = 256 * NPL states, one per
+//                                     workgroup in bands of W states (lattice_device.h walk_row_banded); the same cell, frame words
+//                                     and back-trace, and behind a slot's back-pointer rows the two edge columns of its bands.
 // It also holds the entry prelude that ctcd_ctc_align and ctcd_ctc_loglik share (align_entry).
 #include <hip/hip_runtime.h>
 
@@ -104,6 +107,12 @@ template <int DT, bool PROB> struct AlignRows {
     run<1, 1>(row, b, n, L, slot + (size_t)wave * align_wave_words(T), lane);
   }
   template <int NPL> __device__ __forceinline__ void long_row(long long row, int b, int n, int L, int tid) { run<kAlignWaves, NPL>(row, b, n, L, slot, tid); }
+  // (the slot is then align_long_slot_bytes: the two edge columns lie behind the back-pointer rows)
+  template <int NPL> __device__ __forceinline__ void banded_row(long long row, int b, int n, int L, int tid) {
+    AlignRow<kAlignWaves, NPL> r{slot, n, bp_row_words(n_states(L)), out_st + (size_t)row * L_stride, out_en + (size_t)row * L_stride, out_sc + row, L_stride, 0u};
+    ctclattice::walk_row_banded<NPL, DT, PROB>(r, probs, (size_t)b * T, n, T, V, blank, tokens + (size_t)row * L_stride, L, tid,
+                                               reinterpret_cast<char *>(slot) + align_edge_offset(T, L_stride, 0));
+  }
   // the outputs zero, the score given
   template <int WAVES> __device__ __forceinline__ void no_row(long long row, float sc, int utid) {
     zero_words(out_st + (size_t)row * L_stride, L_stride, utid, 64 * WAVES);
@@ -120,11 +129,20 @@ __global__ void __launch_bounds__(kAlignThreads) ctc_align_kernel(const void *pr
   ctclattice::walk_groups<CLS>(pol, seq_lens, T, V, blank, tokens, lens, R, L_stride, rows, status);
 }
 
+template <int DT, bool PROB, int NPL>
+__global__ void __launch_bounds__(kAlignThreads) ctc_align_banded_kernel(const void *probs, const int32_t *seq_lens, int T, int V, int blank, const int32_t *tokens,
+                                                                         const int32_t *lens, int R, int L_stride, long long rows, char *scratch, size_t slot_bytes,
+                                                                         int32_t *out_st, int32_t *out_en, float *out_sc, int32_t *status) {
+  AlignRows<DT, PROB> pol{probs, T, V, blank, tokens, L_stride, reinterpret_cast<uint32_t *>(scratch + (size_t)blockIdx.x * slot_bytes), out_st, out_en, out_sc};
+  ctclattice::walk_groups<-NPL>(pol, seq_lens, T, V, blank, tokens, lens, R, L_stride, rows, status);
+}
+
 // What ctcd_ctc_align and ctcd_ctc_loglik do alike before their launch; `fn`: the entry point's name, for the messages.
 int align_entry(const char *fn, ctcd_decoder *d, const void *probs, const int32_t *seq_lens, int B, int T, int V, int blank_id, int log_input, const int32_t *tokens,
-                const int32_t *lens, int R, int L_stride, bool outputs, void *stream, ctcdev::DeviceGuard *guard, AlignEntry *e) {
+                const int32_t *lens, int R, int L_stride, bool outputs, void *stream, ctcdev::DeviceGuard *guard, AlignEntry *e, bool long_rows) {
   const std::string f = std::string(fn) + ": ";
   e->rows = 0;
+  e->band = 0;
   if (!d) return align_fail(CTCD_EINVAL, "decoder == NULL");
   if (B < 0 || T < 0 || V < 1 || R < 0 || L_stride < 0) return align_fail(CTCD_EINVAL, (f + "B, T, R, L_stride >= 0 and V >= 1 required").c_str());
   if (blank_id < 0 || blank_id >= V) return align_fail(CTCD_EINVAL, "blank_id must index the vocabulary");
@@ -132,11 +150,15 @@ int align_entry(const char *fn, ctcd_decoder *d, const void *probs, const int32_
   e->rows = (long long)B * R;
   if (e->rows == 0) return CTCD_OK;
   if ((!tokens && L_stride > 0) || !lens || !outputs || (T > 0 && !probs)) return align_fail(CTCD_EINVAL, (f + "null tensor").c_str());
-  if (align_lmax(T, L_stride) > kAlignMaxLabels)
+  if (const int rc = align_decoder_info(d, &e->inf)) return rc;
+  const int band = long_rows ? e->inf.band : 0;
+  if (band > 0 && align_lmax(T, L_stride) > kAlignLongMaxLabels)
+    return align_fail(CTCD_EUNSUPPORTED, (f + "rows of more than 2^20 - 1 labels (min(L_stride, T) > 1048575) are not built").c_str());
+  if (band == 0 && align_lmax(T, L_stride) > kAlignMaxLabels)
     return align_fail(CTCD_EUNSUPPORTED, (f + "rows of more than 2047 labels (min(L_stride, T) > 2047) are not built").c_str());
+  e->band = launch_band(band, T, L_stride);
   if (V > (1 << 28)) return align_fail(CTCD_EUNSUPPORTED, (f + "V > 2^28").c_str());  // (a row's byte offsets are 32 bits)
   if (e->rows > 0x7fffffffLL) return align_fail(CTCD_EUNSUPPORTED, (f + "too many rows for one launch").c_str());
-  if (const int rc = align_decoder_info(d, &e->inf)) return rc;
   if (guard->enter(e->inf.device) != hipSuccess) return align_fail(CTCD_EHIP, (std::string("hipSetDevice: ") + hipGetErrorString(guard->err)).c_str());
   e->probs = probs;
   e->dtype = e->inf.in_dtype;
@@ -160,21 +182,29 @@ int ctcd_ctc_align(ctcd_decoder *d, const void *probs, const int32_t *seq_lens, 
   ctcdev::DeviceGuard guard;
   AlignEntry en;
   const int rc = align_entry("ctcd_ctc_align", d, probs, seq_lens, B, T, V, blank_id, log_input, tokens, lens, R, L_stride,
-                             out_scores && (L_stride == 0 || (out_start && out_end)), stream, &guard, &en);
-  if (rc != CTCD_OK || en.rows == 0) return rc;
-  const size_t slot = align_slot_bytes(T, L_stride);
+                             out_scores && (L_stride == 0 || (out_start && out_end)), stream, &guard, &en, true);
+  if (rc != CTCD_OK) return rc;
+  align_note_band(d, en.band);
+  if (en.rows == 0) return rc;
+  // (a launch with a banded kernel: every kernel's slot carries the two edge columns)
+  const size_t slot = en.band ? align_long_slot_bytes(T, L_stride) : align_slot_bytes(T, L_stride);
   const long long grid = align_grid(en.rows, en.inf.budget, slot);
   void *scratch = nullptr;
   if (const int rc2 = align_scratch(d, (size_t)grid * slot, &scratch)) return rc2;
   align_note_grid(d, grid);
   // class 0 takes a group of four rows per workgroup at a time (at most the groups), the other classes one row
   const long long groups = align_groups(en.rows);
-  const hipError_t e = ctclattice::launch_classes(en.dtype, log_input == 0, T, L_stride, [&](auto dt, auto prob, auto cls) {
-    const long long g = decltype(cls)::value == 0 && grid > groups ? groups : grid;
-    hipLaunchKernelGGL((ctc_align_kernel<decltype(dt)::value, decltype(prob)::value, decltype(cls)::value>), dim3((unsigned)g), dim3(kAlignThreads), 0,
-                       (hipStream_t)stream, en.probs, seq_lens, T, V, blank_id, tokens, lens, R, L_stride, en.rows, (char *)scratch, slot, out_start, out_end, out_scores,
-                       status);
-  });
+  const hipError_t e = ctclattice::launch_classes<true>(en.dtype, log_input == 0, T, L_stride, [&](auto dt, auto prob, auto cls) {
+    constexpr int DT = decltype(dt)::value, CLS = decltype(cls)::value;
+    constexpr bool PROB = decltype(prob)::value;
+    const long long g = CLS == 0 && grid > groups ? groups : grid;
+    if constexpr (CLS < 0)
+      hipLaunchKernelGGL((ctc_align_banded_kernel<DT, PROB, -CLS>), dim3((unsigned)g), dim3(kAlignThreads), 0, (hipStream_t)stream, en.probs, seq_lens, T, V, blank_id,
+                         tokens, lens, R, L_stride, en.rows, (char *)scratch, slot, out_start, out_end, out_scores, status);
+    else
+      hipLaunchKernelGGL((ctc_align_kernel<DT, PROB, CLS>), dim3((unsigned)g), dim3(kAlignThreads), 0, (hipStream_t)stream, en.probs, seq_lens, T, V, blank_id,
+                         tokens, lens, R, L_stride, en.rows, (char *)scratch, slot, out_start, out_end, out_scores, status);
+  }, en.band);
   return e == hipSuccess ? CTCD_OK : align_fail(CTCD_EHIP, (std::string("alignment: ") + hipGetErrorString(e)).c_str());
 }
 

@@ -369,6 +369,9 @@ struct ctcd_decoder {
   // budget of the former (ctcd_set_align_scratch; 0 = the default) and the grid of the last call (ctcd_last_align_grid)
   Buf al_bp, al_lsm;
   long long al_budget = 0, al_grid = 0;
+  // long rows (align.h): the band ctcd_set_long_rows set (0: off), and the band of the banded kernel that the last ctcd_ctc_align or
+  // ctcd_ctc_loglik launched (ctcd_last_long_rows; 0: none)
+  int al_band = 0, al_last_band = 0;
   // ctcd_ctc_loglik (loglik.h): the cap of its grid (ctcd_set_loglik_grid; 0 = the default) and the widest grid of the last call
   long long ll_cap = 0, ll_grid = 0;
   // ctcd_ctc_posteriors (posterior.h): the slots that keep the forward values between its two walks, their budget
@@ -425,6 +428,7 @@ int align_decoder_info(const ctcd_decoder *d, AlignDecoderInfo *out) {
   out->device = d->device;
   out->in_dtype = d->in_dtype;
   out->budget = d->al_budget;
+  out->band = d->al_band;
   return CTCD_OK;
 }
 int align_fail(int code, const char *msg) { return fail(code, msg ? msg : ""); }
@@ -443,6 +447,7 @@ int align_lsm_rows(ctcd_decoder *d, const void *logits, const int32_t *seq_lens,
   return ctcd_log_softmax(d, (const float *)logits, seq_lens, B, T, V, (float *)d->al_lsm.p, stream);
 }
 void align_note_grid(ctcd_decoder *d, long long grid) { d->al_grid = grid; }
+void align_note_band(ctcd_decoder *d, int band) { d->al_last_band = band; }
 }  // namespace ctcalign
 
 // ... and the log-likelihood's (loglik.hip), beyond the alignment's hooks: the cap of its grid and the device's compute units
@@ -801,6 +806,15 @@ int ctcd_set_align_scratch(ctcd_decoder *d, long long bytes) {
   return CTCD_OK;
 }
 long long ctcd_last_align_grid(const ctcd_decoder *d) { return d ? d->al_grid : -1; }
+
+// Long rows (align.hip, loglik.hip): the band of the banded kernels, and the band the last alignment or log-likelihood ran one at.
+int ctcd_set_long_rows(ctcd_decoder *d, int band_states) {
+  if (!d || (band_states != 0 && !ctcalign::band_ok(band_states)))
+    return fail(CTCD_EINVAL, "ctcd_set_long_rows: a decoder and band_states of 0 (off), 256, 1024 or 4096 required");
+  d->al_band = band_states;
+  return CTCD_OK;
+}
+int ctcd_last_long_rows(const ctcd_decoder *d) { return d ? d->al_last_band : -1; }
 
 // CTC log-likelihood (loglik.hip): the cap of its grid, and the widest grid its last call launched.
 int ctcd_set_loglik_grid(ctcd_decoder *d, long long max_workgroups) {

@@ -177,6 +177,181 @@ __device__ __forceinline__ void walk_row(P &pol, const void *probs, size_t row0,
   pol.finish(last, before, L, utid);
 }
 
+// ---- long rows: a hypothesis of more states than a workgroup holds, in bands (align.h "long rows") -----------------------------------
+// An edge column holds, per frame, a band's last two states as one 8-byte pair: (d[t][last], d[t][last - 1]).  The band that owns the
+// column writes it with plain vector stores; the band behind it -- the same workgroup, a __threadfence() and a barrier later -- reads
+// it with device-scope loads, as the back-trace reads its back-pointers.
+struct EdgePair {
+  float last, before;
+};
+__device__ __forceinline__ EdgePair edge_load(const unsigned long long *col, int t) {
+  const unsigned long long w = __hip_atomic_load(col + t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  return EdgePair{__uint_as_float((unsigned)w), __uint_as_float((unsigned)(w >> 32))};
+}
+
+// Band `base / W` of one hypothesis on the whole workgroup, W = kAlignThreads * NPL: thread `tid` holds the states base + tid * NPL ..
+// + NPL - 1 and the band walks all n frames as walk_row does -- the same cells in the same order, the same policy hooks with the
+// global state index.  What differs lies at the band's two edges.  Thread 0's neighbours base - 1 and base - 2 of frame t - 1 are the
+// pair t - 1 of `edge_in` (NPL == 1: thread 1's second neighbour is base - 1 too); a chunk's pairs are fetched with the chunk's lp
+// gathers, CH frames ahead of their use, so no frame waits for a load of its own.  edge_in == nullptr: the row's first band, whose
+// state 0 has no predecessor.  Behind every frame the last thread writes the pair (base + W - 1, base + W - 2) to `edge_out`, unless
+// that is nullptr (the row's last band).  Frame 0 of a band behind the first is all -inf.  mine1 / mine2: frame n - 1's states S - 1
+// and S - 2 on the threads that hold them.  S may end inside the band: the states beyond it compute on and nothing reads them.
+template <int NPL, int DT, bool PROB, class P>
+__device__ __forceinline__ void walk_band(P &pol, const void *probs, size_t row0, int n, int V, int blank, const int32_t *tok, int S, int base,
+                                          const unsigned long long *edge_in, float2 *edge_out, int tid, float &mine1, float &mine2) {
+  constexpr int CH = NPL == 1 ? 8 : (NPL == 4 ? 4 : 2);
+  constexpr int WAVES = kAlignWaves;
+  const int lane = tid & 63, wave = tid >> 6;
+  const int s0 = base + tid * NPL;
+  const bool takes_edge = edge_in != nullptr && tid < (NPL == 1 ? 2 : 1);
+  __shared__ float s_bxch[2 * kAlignWaves * 2];
+  float *xch = s_bxch;
+  constexpr unsigned kElem = DT == ctcskip::kSkipF32 ? 4u : 2u;
+  unsigned zo[NPL];
+  unsigned has2 = 0u;
+#pragma unroll
+  for (int k = 0; k < NPL; ++k) {
+    const int s = s0 + k;
+    zo[k] = (unsigned)blank * kElem;
+    if (s < S) {
+      if (s & 1) zo[k] = (unsigned)tok[s >> 1] * kElem;
+      if (state_skips(tok, s)) has2 |= 1u << k;  // (a band's first odd state looks at a label of the band before it)
+    }
+  }
+  auto load = [&](float(&dst)[NPL], int t) {
+    const int tt = t < n ? t : n - 1;
+    const char *fr = (const char *)probs + (row0 + (size_t)tt) * (size_t)V * kElem;
+#pragma unroll
+    for (int k = 0; k < NPL; ++k) dst[k] = ctcskip::widen_at<DT>(fr + (size_t)zo[k], 0);
+  };
+  auto convert = [&](float(&v)[NPL]) {
+    if (PROB) {
+#pragma unroll
+      for (int k = 0; k < NPL; ++k) v[k] = prob_to_lp(v[k]);
+    }
+  };
+  // what frame t (>= 1) needs of the band before: its pair of frame t - 1 (a frame at or beyond n: frame n - 1's pair, unused)
+  auto edge = [&](EdgePair &dst, int t) {
+    if (takes_edge) dst = edge_load(edge_in, (t < n ? t : n) - 1);
+  };
+  float a[NPL];
+  auto publish = [&](int t) {
+    const float before = NPL >= 2 ? a[NPL >= 2 ? NPL - 2 : 0] : __shfl_up(a[0], 1, 64);
+    if (lane == 63) {
+      xch[((t & 1) * WAVES + wave) * 2] = a[NPL - 1];
+      xch[((t & 1) * WAVES + wave) * 2 + 1] = before;
+    }
+    if (edge_out != nullptr && tid == kAlignThreads - 1) edge_out[t] = make_float2(a[NPL - 1], before);
+    __syncthreads();
+  };
+
+  float cur[CH][NPL], nxt[CH][NPL];
+  EdgePair ecur[CH], enxt[CH];
+#pragma unroll
+  for (int c = 0; c < CH; ++c) ecur[c] = enxt[c] = EdgePair{neg_inf(), neg_inf()};
+  load(cur[0], 0);
+  convert(cur[0]);
+#pragma unroll
+  for (int k = 0; k < NPL; ++k) a[k] = (s0 + k < 2 && s0 + k < S) ? cur[0][k] : neg_inf();
+  publish(0);
+#pragma unroll
+  for (int c = 0; c < CH; ++c) {
+    load(cur[c], 1 + c);
+    edge(ecur[c], 1 + c);
+  }
+#pragma unroll
+  for (int c = 0; c < CH; ++c) convert(cur[c]);
+  for (int t0 = 1; t0 < n; t0 += CH) {
+#pragma unroll
+    for (int c = 0; c < CH; ++c) {
+      load(nxt[c], t0 + CH + c);
+      edge(enxt[c], t0 + CH + c);
+    }
+#pragma unroll
+    for (int c = 0; c < CH; ++c) {
+      const int t = t0 + c;
+      if (t < n) {
+        float a_in, b_in;
+        if (NPL == 1) {
+          a_in = __shfl_up(a[0], 1, 64);
+          b_in = __shfl_up(a[0], 2, 64);
+        } else {
+          a_in = __shfl_up(a[NPL - 1], 1, 64);
+          b_in = __shfl_up(a[NPL >= 2 ? NPL - 2 : 0], 1, 64);
+        }
+        if (wave > 0) {
+          const int at = (((t - 1) & 1) * WAVES + wave - 1) * 2;
+          if (lane == 0) {
+            a_in = xch[at];
+            b_in = xch[at + 1];
+          }
+          if (NPL == 1 && lane == 1) b_in = xch[at];
+        }
+        if (tid == 0) {  // (the first band: -inf, which never exceeds what it is compared with)
+          a_in = ecur[c].last;
+          b_in = ecur[c].before;
+        }
+        if (NPL == 1 && tid == 1) b_in = ecur[c].last;
+#pragma unroll
+        for (int k = NPL - 1; k >= 0; --k) {
+          const float p1 = k >= 1 ? a[k >= 1 ? k - 1 : 0] : a_in;
+          const float p2 = k >= 2 ? a[k >= 2 ? k - 2 : 0] : (k == 1 ? a_in : b_in);
+          a[k] = pol.cell(k, cur[c][k], a[k], p1, p2, (has2 >> k) & 1u);
+        }
+        pol.frame(t, s0, lane);
+        publish(t);
+      }
+    }
+#pragma unroll
+    for (int c = 0; c < CH; ++c) {
+#pragma unroll
+      for (int k = 0; k < NPL; ++k) cur[c][k] = nxt[c][k];
+      convert(cur[c]);
+      ecur[c] = enxt[c];
+    }
+  }
+  mine1 = 0.0f;
+  mine2 = 0.0f;
+#pragma unroll
+  for (int k = 0; k < NPL; ++k) {
+    if (s0 + k == S - 1) mine1 = a[k];
+    if (s0 + k == S - 2) mine2 = a[k];
+  }
+}
+
+// One hypothesis of S > W states on the workgroup: its bands one after the other, a __threadfence() and a barrier between two, then
+// what walk_row does behind the last frame.  `edges`: the workgroup's two edge columns, edge_col_bytes(T) apart (band j writes column
+// j & 1).  When S - 1 is the last band's first state, S - 2 is the last state of the band before: the last pair of its column.
+template <int NPL, int DT, bool PROB, class P>
+__device__ __forceinline__ void walk_row_banded(P &pol, const void *probs, size_t row0, int n, int T, int V, int blank, const int32_t *tok, int L, int tid,
+                                                char *edges) {
+  constexpr int W = kAlignThreads * NPL;
+  __shared__ float s_bfin[2];
+  const int S = n_states(L), nb = band_count(S, W);
+  float mine1 = 0.0f, mine2 = 0.0f;
+  for (int j = 0; j < nb; ++j) {
+    const unsigned long long *in = j > 0 ? reinterpret_cast<const unsigned long long *>(edges + edge_col_bytes(T) * (size_t)((j - 1) & 1)) : nullptr;
+    float2 *out = j + 1 < nb ? reinterpret_cast<float2 *>(edges + edge_col_bytes(T) * (size_t)(j & 1)) : nullptr;
+    walk_band<NPL, DT, PROB>(pol, probs, row0, n, V, blank, tok, S, band_first_state(j, W), in, out, tid, mine1, mine2);
+    if (j + 1 < nb) {
+      __threadfence();
+      __syncthreads();
+    }
+  }
+  pol.frames_done();
+  const int base = band_first_state(nb - 1, W), s0 = base + tid * NPL;
+  if (s0 <= S - 1 && S - 1 < s0 + NPL) s_bfin[0] = mine1;
+  if (s0 <= S - 2 && S - 2 < s0 + NPL) s_bfin[1] = mine2;
+  __syncthreads();
+  const float last = s_bfin[0];
+  float before = 0.0f;
+  if (L >= 1)
+    before = S - 2 >= base ? s_bfin[1]
+                           : edge_load(reinterpret_cast<const unsigned long long *>(edges + edge_col_bytes(T) * (size_t)((nb - 2) & 1)), n - 1).last;
+  pol.finish(last, before, L, tid);
+}
+
 // The rows fall into four classes, and each class has a kernel of its own (CLS), so that each gets the registers its class needs and
 // no more: 0 = the rows of a group of four consecutive rows that all fit a wave (S <= 64, and the rows that run no recurrence), one
 // per wave side by side without a barrier (workgroup g takes the groups g, g + grid, ...); 1 / 4 / 16 = the rows of every other group,
@@ -187,6 +362,11 @@ __device__ __forceinline__ void walk_row(P &pol, const void *probs, size_t row0,
 //   void short_row(long long row, int b, int n, int L, int lane, int wave)        run the row on this wave (S <= 64)
 //   template <int NPL> void long_row(long long row, int b, int n, int L, int tid) run the row on the workgroup, NPL states per lane
 //   template <int WAVES> void no_row(long long row, float score, int utid)        a row that runs no recurrence: its score is given
+// Long rows (align.h): CLS = -NPL is the banded kernel of band W = kAlignThreads * NPL.  It takes the rows of S > W states, one per
+// workgroup like the classes 1 / 4 / 16, and leaves every other row to them:
+//   template <int NPL> void banded_row(long long row, int b, int n, int L, int tid)   run the row on the workgroup in bands of W states
+// A row of more than kAlignMaxStates states belongs to no other class; of the rows between W and that, the classes above W would
+// take theirs, and the host does not launch those (launch_classes).
 template <int CLS, class P>
 __device__ __forceinline__ void walk_groups(P &pol, const int32_t *seq_lens, int T, int V, int blank, const int32_t *tokens, const int32_t *lens, int R,
                                             int L_stride, long long rows, int32_t *status) {
@@ -230,7 +410,9 @@ __device__ __forceinline__ void walk_groups(P &pol, const int32_t *seq_lens, int
       const int b = (int)(u / R), n = ctcskip::clamped_len(seq_lens, b, T);
       if (code < 0) {
         if (CLS == 1) pol.template no_row<kAlignWaves>(u, no_row_score(code, lens[u], n), tid);
-      } else if (align_npl(n_states(code)) == CLS) {  // (the entry points refuse shapes whose rows can exceed kAlignMaxStates)
+      } else if constexpr (CLS < 0) {
+        if (n_states(code) > kAlignThreads * -CLS) pol.template banded_row<-CLS>(u, b, n, code, tid);
+      } else if (align_npl(n_states(code)) == CLS && (CLS != kAlignMaxNpl || n_states(code) <= kAlignMaxStates)) {  // (rows beyond: the banded kernel's)
         pol.template long_row<CLS == 0 ? 1 : CLS>(u, b, n, code, tid);
       }
     }
@@ -240,14 +422,21 @@ __device__ __forceinline__ void walk_groups(P &pol, const int32_t *seq_lens, int
 
 // The kernels a launch needs, one behind the other on the stream: f(DT, PROB, CLS) -- std::integral_constant values of the kernels'
 // template arguments -- for the input's element type and mode and every class the shape allows (S <= 2 * min(L_stride, T) + 1).
+// BANDED: the caller has banded kernels, and `band` (align.h launch_band; 0: none) is the band this launch runs its rows beyond
+// `band` states at: f(DT, PROB, -band / kAlignThreads) behind the register classes up to `band` -- the classes above it are not launched.
 template <int N> using Int = std::integral_constant<int, N>;
-template <class F> hipError_t launch_classes(int dtype, bool prob, int T, int L_stride, F &&f) {
+template <bool BANDED = false, class F> hipError_t launch_classes(int dtype, bool prob, int T, int L_stride, F &&f, int band = 0) {
   const int smax = n_states(align_lmax(T, L_stride));
   auto classes = [&](auto dt, auto pr) {
     f(dt, pr, Int<0>());
     if (smax > 64) f(dt, pr, Int<1>());
-    if (smax > kAlignThreads) f(dt, pr, Int<4>());
-    if (smax > kAlignThreads * 4) f(dt, pr, Int<16>());
+    if (smax > kAlignThreads && (!BANDED || band == 0 || band >= kAlignThreads * 4)) f(dt, pr, Int<4>());
+    if (smax > kAlignThreads * 4 && (!BANDED || band == 0 || band >= kAlignThreads * 16)) f(dt, pr, Int<16>());
+    if constexpr (BANDED) {
+      if (band == kAlignThreads) f(dt, pr, Int<-1>());
+      else if (band == kAlignThreads * 4) f(dt, pr, Int<-4>());
+      else if (band == kAlignThreads * 16) f(dt, pr, Int<-16>());
+    }
   };
   auto modes = [&](auto dt) { prob ? classes(dt, std::true_type()) : classes(dt, std::false_type()); };
   if (dtype == CTCD_DTYPE_F16) modes(Int<ctcskip::kSkipF16>());

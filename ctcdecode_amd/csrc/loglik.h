@@ -56,8 +56,10 @@ CTC_HD float end_value(int L, float a_last, float a_before, const uint64_t *tbl)
 // than 96 SGPRs (DESIGN.md 2i has the register counts).  A grid beyond that would only queue; one below it leaves SIMDs idle.
 CTC_HD long long loglik_units(long long rows, int cls) { return cls == 0 ? ctcalign::align_groups(rows) : rows; }
 CTC_HD int loglik_occupancy(int cls) { return cls == 16 ? 2 : (cls == 4 ? 4 : (cls == 1 ? 7 : 6)); }
+// ... and of the banded kernel of NPL states per lane (long rows; DESIGN.md 2q has its register counts)
+CTC_HD int loglik_banded_occupancy(int npl) { return npl == 16 ? 2 : 4; }
 CTC_HD long long loglik_grid(long long units, long long cap, int cus, int cls) {
-  long long g = cap > 0 ? cap : (long long)(cus > 0 ? cus : 1) * loglik_occupancy(cls);
+  long long g = cap > 0 ? cap : (long long)(cus > 0 ? cus : 1) * (cls < 0 ? loglik_banded_occupancy(-cls) : loglik_occupancy(cls));
   if (g > units) g = units;
   return g < 1 ? 1 : g;
 }

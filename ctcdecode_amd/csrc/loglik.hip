@@ -5,6 +5,9 @@
 //                                     over a row's frames are lattice_device.h's, shared with align.hip; here are the cell (lse3 on
 //                                     exact_math.h's tables, staged into LDS) and the end rule.  No back-pointers and no scratch: the
 //                                     only memory a row writes is its float.
+//   ctc_loglik_banded_kernel<DT, PROB, NPL>  long rows (ctcd_set_long_rows): the rows of more than W = 256 * NPL states, one per
+//                                     workgroup in bands of W states (lattice_device.h walk_row_banded); its only scratch is the two
+//                                     edge columns of a workgroup's bands.
 #include <hip/hip_runtime.h>
 
 #include <string>
@@ -43,6 +46,7 @@ template <int DT, bool PROB> struct LoglikRows {
   const int32_t *tokens;
   int L_stride;
   float *out;
+  char *edges;  // the workgroup's two edge columns (the banded kernel), or nullptr
 
   template <int WAVES, int NPL> __device__ __forceinline__ void run(long long row, int b, int n, int L, int utid) {
     LoglikRow r{tbl, 0.0f};
@@ -51,10 +55,22 @@ template <int DT, bool PROB> struct LoglikRows {
   }
   __device__ __forceinline__ void short_row(long long row, int b, int n, int L, int lane, int) { run<1, 1>(row, b, n, L, lane); }
   template <int NPL> __device__ __forceinline__ void long_row(long long row, int b, int n, int L, int tid) { run<kAlignWaves, NPL>(row, b, n, L, tid); }
+  template <int NPL> __device__ __forceinline__ void banded_row(long long row, int b, int n, int L, int tid) {
+    LoglikRow r{tbl, 0.0f};
+    ctclattice::walk_row_banded<NPL, DT, PROB>(r, probs, (size_t)b * T, n, T, V, blank, tokens + (size_t)row * L_stride, L, tid, edges);
+    if (tid == 0) out[row] = r.ll;
+  }
   template <int WAVES> __device__ __forceinline__ void no_row(long long row, float ll, int utid) {
     if (utid == 0) out[row] = ll;
   }
 };
+
+// exact_math.h's tables into the workgroup's LDS (the first barrier of the walk stands between these stores and their readers)
+__device__ __forceinline__ void stage_tables(uint64_t *s_tbl, int tid) {
+  if (tid < 32) s_tbl[tid] = kExpTab[tid];
+  else if (tid < 48) s_tbl[tid] = (uint64_t)__double_as_longlong(kLogInvc[tid - 32]);
+  else if (tid < 64) s_tbl[tid] = (uint64_t)__double_as_longlong(kLogLogc[tid - 48]);
+}
 
 template <int DT, bool PROB, int CLS>
 __global__ void __launch_bounds__(kAlignThreads) ctc_loglik_kernel(const void *probs, const int32_t *seq_lens, int T, int V, int blank, const int32_t *tokens,
@@ -65,8 +81,18 @@ __global__ void __launch_bounds__(kAlignThreads) ctc_loglik_kernel(const void *p
   else if (tid < 48) s_tbl[tid] = (uint64_t)__double_as_longlong(kLogInvc[tid - 32]);
   else if (tid < 64) s_tbl[tid] = (uint64_t)__double_as_longlong(kLogLogc[tid - 48]);
   // (the first barrier of the walk stands between these stores and their readers)
-  LoglikRows<DT, PROB> pol{s_tbl, probs, T, V, blank, tokens, L_stride, out};
+  LoglikRows<DT, PROB> pol{s_tbl, probs, T, V, blank, tokens, L_stride, out, nullptr};
   ctclattice::walk_groups<CLS>(pol, seq_lens, T, V, blank, tokens, lens, R, L_stride, rows, status);
+}
+
+template <int DT, bool PROB, int NPL>
+__global__ void __launch_bounds__(kAlignThreads) ctc_loglik_banded_kernel(const void *probs, const int32_t *seq_lens, int T, int V, int blank, const int32_t *tokens,
+                                                                          const int32_t *lens, int R, int L_stride, long long rows, float *out, int32_t *status,
+                                                                          char *scratch) {
+  __shared__ uint64_t s_tbl[64];
+  stage_tables(s_tbl, (int)threadIdx.x);
+  LoglikRows<DT, PROB> pol{s_tbl, probs, T, V, blank, tokens, L_stride, out, scratch + (size_t)blockIdx.x * loglik_long_slot_bytes(T)};
+  ctclattice::walk_groups<-NPL>(pol, seq_lens, T, V, blank, tokens, lens, R, L_stride, rows, status);
 }
 
 }  // namespace ctcloglik
@@ -79,19 +105,32 @@ int ctcd_ctc_loglik(ctcd_decoder *d, const void *probs, const int32_t *seq_lens,
                     const int32_t *lens, int R, int L_stride, float *out_loglik, int32_t *status, void *stream) {
   ctcdev::DeviceGuard guard;
   AlignEntry en;
-  const int rc = align_entry("ctcd_ctc_loglik", d, probs, seq_lens, B, T, V, blank_id, log_input, tokens, lens, R, L_stride, out_loglik != nullptr, stream, &guard, &en);
-  if (rc != CTCD_OK || en.rows == 0) return rc;
+  const int rc = align_entry("ctcd_ctc_loglik", d, probs, seq_lens, B, T, V, blank_id, log_input, tokens, lens, R, L_stride, out_loglik != nullptr, stream, &guard, &en, true);
+  if (rc != CTCD_OK) return rc;
+  align_note_band(d, en.band);
+  if (en.rows == 0) return rc;
   LoglikDecoderInfo linf;
   if (const int rc2 = loglik_decoder_info(d, &linf)) return rc2;
+  // the banded kernel's edge columns: slots of the alignment's scratch under its budget, one per workgroup
+  const long long slots = align_grid(en.rows, en.inf.budget, loglik_long_slot_bytes(T));
+  void *scratch = nullptr;
+  if (en.band)
+    if (const int rc3 = align_scratch(d, (size_t)slots * loglik_long_slot_bytes(T), &scratch)) return rc3;
   // no scratch binds the grids: each class's own (loglik.h loglik_grid); the largest of them is noted
   long long widest = 0;
-  const hipError_t e = ctclattice::launch_classes(en.dtype, log_input == 0, T, L_stride, [&](auto dt, auto prob, auto cls) {
-    constexpr int CLS = decltype(cls)::value;
-    const long long grid = loglik_grid(loglik_units(en.rows, CLS), linf.cap, linf.cus, CLS);
+  const hipError_t e = ctclattice::launch_classes<true>(en.dtype, log_input == 0, T, L_stride, [&](auto dt, auto prob, auto cls) {
+    constexpr int DT = decltype(dt)::value, CLS = decltype(cls)::value;
+    constexpr bool PROB = decltype(prob)::value;
+    long long grid = loglik_grid(loglik_units(en.rows, CLS), linf.cap, linf.cus, CLS);
+    if (CLS < 0 && grid > slots) grid = slots;
     if (grid > widest) widest = grid;
-    hipLaunchKernelGGL((ctc_loglik_kernel<decltype(dt)::value, decltype(prob)::value, CLS>), dim3((unsigned)grid), dim3(kAlignThreads), 0, (hipStream_t)stream,
-                       en.probs, seq_lens, T, V, blank_id, tokens, lens, R, L_stride, en.rows, out_loglik, status);
-  });
+    if constexpr (CLS < 0)
+      hipLaunchKernelGGL((ctc_loglik_banded_kernel<DT, PROB, -CLS>), dim3((unsigned)grid), dim3(kAlignThreads), 0, (hipStream_t)stream, en.probs, seq_lens, T, V,
+                         blank_id, tokens, lens, R, L_stride, en.rows, out_loglik, status, (char *)scratch);
+    else
+      hipLaunchKernelGGL((ctc_loglik_kernel<DT, PROB, CLS>), dim3((unsigned)grid), dim3(kAlignThreads), 0, (hipStream_t)stream, en.probs, seq_lens, T, V, blank_id,
+                         tokens, lens, R, L_stride, en.rows, out_loglik, status);
+  }, en.band);
   loglik_note_grid(d, widest);
   return e == hipSuccess ? CTCD_OK : align_fail(CTCD_EHIP, (std::string("log-likelihood: ") + hipGetErrorString(e)).c_str());
 }

@@ -611,7 +611,22 @@ int ctcd_beam_decode_to_host_nbest(ctcd_decoder *dec, const float *probs, const 
  * CTCD_EINVAL for bad shapes (negative sizes, V < 1, blank_id outside [0, V), log_input outside 0 .. 2, a NULL tensor), and nothing is
  * launched.  CTCD_EUNSUPPORTED: min(L_stride, T) > 2047 (an extended sequence beyond the 4096 states one workgroup holds).
  * ctcd_set_align_scratch: the budget of the back-pointer scratch in bytes; 0 = the default (256 MiB).
- * ctcd_last_align_grid: the workgroups the last ctcd_ctc_align launched (0: none yet; -1: dec == NULL). */
+ * ctcd_last_align_grid: the workgroups the last ctcd_ctc_align launched (0: none yet; -1: dec == NULL).
+ *
+ * Long rows.  ctcd_set_long_rows(dec, band_states) lifts the limit for ctcd_ctc_align and ctcd_ctc_loglik: band_states = 256, 1024
+ * or 4096 turns the mode on, 0 turns it off (the default: everything above, the CTCD_EUNSUPPORTED at 2048 included); any other value
+ * is CTCD_EINVAL.  With the mode on a row of more than band_states states runs in bands of that many states: band j holds the states
+ * [j x band, (j + 1) x band) in registers and walks all frames, and reads the last two states of band j - 1 at every frame from a
+ * column of T float pairs that band wrote.  No cell's arithmetic and no cell's order changes: THE BAND WIDTH NEVER CHANGES A RESULT,
+ * and neither does the mode -- the definition above holds bit for bit for every row.  Rows of at most band_states states run as with
+ * the mode off.  The limit is then min(L_stride, T) <= 2^20 - 1 (no 32-bit quantity of the walk binds earlier: state indices stay
+ * below 2^21 + 4096, and a slot's byte count is a size_t); one step beyond is CTCD_EUNSUPPORTED, returned before anything is read or
+ * allocated.  When the shape admits a row beyond the band, a slot of the alignment's scratch is its back-pointer rows plus two
+ * columns of T x 8 bytes -- T x (min(L_stride, T) / 2 + 16) bytes and more, hundreds of megabytes for an hour of speech, which is why
+ * the mode is opt-in; the budget rule is unchanged (min(B x R, budget / slot bytes) workgroups, at least one), and a slot the device
+ * cannot allocate fails the call with the allocation's error.  ctcd_ctc_posteriors keeps its limit of 2047 whatever the mode.
+ * ctcd_last_long_rows: the band of the banded kernel that the last ctcd_ctc_align or ctcd_ctc_loglik launched, or 0 if it launched
+ * none (mode off, or min(L_stride, T) admits no row beyond the band: the host knows from the shape alone); -1: dec == NULL. */
 #define CTCD_ALIGN_BAD_ROW 8
 int ctcd_ctc_align(ctcd_decoder *dec, const void *probs, const int32_t *seq_lens, int B, int T, int V, int blank_id, int log_input,
                    const int32_t *tokens /* [B][R][L_stride] */, const int32_t *lens /* [B][R] */, int R, int L_stride,
@@ -619,6 +634,8 @@ int ctcd_ctc_align(ctcd_decoder *dec, const void *probs, const int32_t *seq_lens
                    int32_t *status /* [B] zeroed by the caller, or NULL */, void *stream);
 int ctcd_set_align_scratch(ctcd_decoder *dec, long long bytes);   /* budget of the back-pointer scratch; 0 = the default */
 long long ctcd_last_align_grid(const ctcd_decoder *dec);
+int ctcd_set_long_rows(ctcd_decoder *dec, int band_states);   /* 0 = off (the default), or 256 / 1024 / 4096 */
+int ctcd_last_long_rows(const ctcd_decoder *dec);
 
 /* ---- CTC log-likelihood (no reference counterpart): for the rows a caller keeps, log P(y | x) -- the sum over ALL alignments of
  * the row through the item's acoustic rows, by the forward algorithm.  It is the quantity CTC defines: it does not depend on what
@@ -662,7 +679,11 @@ long long ctcd_last_align_grid(const ctcd_decoder *dec);
  * log_input outside 0 .. 2, a NULL tensor), and nothing is launched; CTCD_EUNSUPPORTED for min(L_stride, T) > 2047, V > 2^28 or more
  * than 2^31 - 1 rows.  B x R == 0 is CTCD_OK and launches nothing.  Streams are out of scope: score the concatenated rows one-shot.
  * ctcd_set_loglik_grid: the cap of every launch's grid; 0 = the default.  The results do not depend on it.
- * ctcd_last_loglik_grid: the widest grid the last ctcd_ctc_loglik launched (0: none yet; -1: dec == NULL). */
+ * ctcd_last_loglik_grid: the widest grid the last ctcd_ctc_loglik launched (0: none yet; -1: dec == NULL).
+ * Long rows: ctcd_set_long_rows and ctcd_last_long_rows ("Forced alignment") hold here as they do there -- the limit becomes
+ * min(L_stride, T) <= 2^20 - 1, rows beyond the band run in bands, and the band width never changes a result.  The banded kernel's
+ * only scratch is two columns of T x 8 bytes per workgroup, slots of the alignment's scratch under ctcd_set_align_scratch's budget
+ * (min(grid, budget / slot bytes) workgroups, at least one): it belongs to the decoder's next alignment or log-likelihood. */
 int ctcd_ctc_loglik(ctcd_decoder *dec, const void *probs, const int32_t *seq_lens, int B, int T, int V, int blank_id, int log_input,
                     const int32_t *tokens /* [B][R][L_stride] */, const int32_t *lens /* [B][R] */, int R, int L_stride,
                     float *out_loglik /* [B][R] */, int32_t *status /* [B] zeroed by the caller, or NULL */, void *stream);
