@@ -959,7 +959,8 @@ class CTCBeamDecoder(object):
         reference is the reference's length.
 
         The shorter row of a pair is held in one wave's registers: ``min(L, Lq) > 2048`` raises ``NotImplementedError`` (the longer
-        side is not bounded).  A length outside [0, L] (references: [0, Lq]) raises ``ValueError``."""
+        side is not bounded) unless ``set_edit_long`` is on -- a pair whose shorter row is beyond 2048 tokens then runs on a workgroup
+        of its own.  A length outside [0, L] (references: [0, Lq]) raises ``ValueError``."""
         if beam_results.dim() != 3 or out_lens.dim() != 2 or tuple(out_lens.shape) != tuple(beam_results.shape[:2]):
             raise ValueError("beam_results must be [batch, rows, labels] and out_lens [batch, rows]")
         on_device = beam_results.is_cuda
@@ -1054,8 +1055,9 @@ class CTCBeamDecoder(object):
 
         Arguments, modes and tensor handling are ``edit_distance``'s.  Pairwise mode (``references=None``) gives [B, R, R, 4]:
         ``[b, i, j]`` takes row ``i`` as the hypothesis, ``[b, j, i]`` has deletions and insertions exchanged, the diagonal is
-        ``(len, 0, 0, 0)``.  ``min(L, Lq) > 2048`` or ``max(L, Lq) > 262144`` raises ``NotImplementedError``; a length outside its
-        bounds raises ``ValueError``."""
+        ``(len, 0, 0, 0)``.  ``min(L, Lq) > 2048`` or ``max(L, Lq) > 262144`` raises ``NotImplementedError`` -- with ``set_edit_long``
+        on, a call with ``min(L, Lq) > 2048`` is accepted and neither limit holds for it; a length outside its bounds raises
+        ``ValueError``."""
         on_device = beam_results.is_cuda
         x, x_lens, y, y_lens, B, R, L, Q, Lq = self._edit_rows(beam_results, out_lens, references, ref_lens)
         pairwise = y is None
@@ -1080,7 +1082,7 @@ class CTCBeamDecoder(object):
 
         ``references`` are required (there is no pairwise mode); tensor handling and errors are ``edit_counts``'.  The walk's
         directions live in decoder-owned scratch (``set_edit_scratch``); a call whose single slot does not fit the budget raises
-        ``NotImplementedError``."""
+        ``NotImplementedError``.  ``set_edit_long`` does not reach here: alignments keep ``min(L, Lq) <= 2048``."""
         if references is None:
             raise ValueError("edit_align needs references: alignments are not provided in pairwise mode")
         on_device = beam_results.is_cuda
@@ -1107,6 +1109,23 @@ class CTCBeamDecoder(object):
         """Test hook: the back-pointer slots (waves with work) of the last ``edit_align``."""
         return int(_native.lib.ctcd_last_edit_slots(self._handle))
 
+    def set_edit_long(self, waves=16):
+        """Long pairs for ``edit_distance``, ``edit_counts`` and ``mbr_select`` (include/ctcdecode_amd.h ctcd_set_edit_long): with
+        ``waves`` of 2, 4, 8 or 16, tensors with ``min(L, Lq) > 2048`` are accepted, and a pair whose shorter row is beyond 2048 tokens
+        runs on one workgroup of that many waves, which share the row in tiles of 2048 columns; 0 turns the mode off (the default).
+        ``waves`` never changes a result.  A long pair needs ``4 x (max(L, Lq) + 1)`` bytes of scratch per workgroup, twice that for
+        counts, under the budget of ``set_edit_scratch``; a call whose single slot does not fit raises ``NotImplementedError``.
+        ``edit_align`` keeps its limit.  Raises ``ValueError`` for any other ``waves``."""
+        _native.check(_native.lib.ctcd_set_edit_long(self._handle, int(waves)))
+
+    def last_edit_long(self):
+        """The pairs the long kernel ran in the last ``edit_distance`` or ``edit_counts``: 0 if none, and 0 with the mode off.  Reads
+        one word from the device, behind that call's kernels."""
+        n = int(_native.lib.ctcd_last_edit_long(self._handle))
+        if n < 0:  # (an error code of the read)
+            _native.check(n)
+        return n
+
     def mbr_select(self, beam_results, out_lens, log_weights):
         """Minimum-Bayes-risk selection from an n-best list: for every item the row with the least expected edit distance to the other
         rows.  Returns ``(index int64 [B], risk float64 [B, R])``, on the device when ``beam_results`` is, otherwise CPU.
@@ -1115,7 +1134,8 @@ class CTCBeamDecoder(object):
         ``index[b]`` is the smallest ``i`` of least risk.  Rows with ``log_weights == -inf`` weigh nothing, get risk ``+inf`` and are
         never chosen; an item without a finite weight gets index ``-1`` and all risks ``+inf``.  The distances come from
         ``edit_distance``, which reads its status words on the host (and so waits for the device, and raises ``ValueError`` for a bad
-        length); everything after them is plain torch on the device, with no further host read.
+        length); everything after them is plain torch on the device, with no further host read.  Rows beyond 2048 tokens need
+        ``set_edit_long``.
 
         The natural weights are ``log_likelihood(probs, seq_lens, beam_results, out_lens)`` (plus whatever a language model adds).
         Pass ``-inf`` for rows beyond a decode's result count: such rows are empty, and an empty row must not vote."""

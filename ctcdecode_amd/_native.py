@@ -40,7 +40,8 @@ SYMBOLS = ["ctcd_log_softmax", "ctcd_compact_label_capacity", "ctcd_beam_decode_
            "ctcd_greedy_decode",
            "ctcd_greedy_stream_create", "ctcd_greedy_stream_destroy", "ctcd_greedy_stream_reset", "ctcd_greedy_stream_decode", "ctcd_greedy_stream_info",
            "ctcd_edit_distance", "ctcd_last_edit_pairs", "ctcd_set_edit_grid", "ctcd_last_edit_grid",
-           "ctcd_edit_counts", "ctcd_edit_align", "ctcd_set_edit_scratch", "ctcd_last_edit_slots"]
+           "ctcd_edit_counts", "ctcd_edit_align", "ctcd_set_edit_scratch", "ctcd_last_edit_slots",
+           "ctcd_set_edit_long", "ctcd_last_edit_long"]
 
 
 def _load():
@@ -226,6 +227,10 @@ def _load():
     lib.ctcd_set_edit_scratch.argtypes = [ctypes.c_void_p, ctypes.c_longlong]
     lib.ctcd_last_edit_slots.argtypes = [ctypes.c_void_p]
     lib.ctcd_last_edit_slots.restype = ctypes.c_longlong
+    # long edit pairs (editlong.hip)
+    lib.ctcd_set_edit_long.argtypes = [ctypes.c_void_p, ctypes.c_int]
+    lib.ctcd_last_edit_long.argtypes = [ctypes.c_void_p]
+    lib.ctcd_last_edit_long.restype = ctypes.c_longlong
     return lib
 
 

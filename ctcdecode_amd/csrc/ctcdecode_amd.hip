@@ -46,6 +46,7 @@
 #include "greedy.h"
 #include "editdist.h"
 #include "editops.h"
+#include "editlong.h"
 #include "prepass.h"
 
 namespace {
@@ -388,6 +389,12 @@ struct ctcd_decoder {
   // slots of the last call (ctcd_last_edit_slots)
   Buf ed_bp;
   long long ed_budget = 0, ed_slots = 0;
+  // long edit pairs (editlong.h): the waves ctcd_set_edit_long set (0: off); the list of a call's long pairs, its counter in front, and
+  // the slots of the long kernel's workgroups; whether the last edit call launched that kernel, and on which stream (ctcd_last_edit_long)
+  int el_waves = 0;
+  Buf el_list, el_slots;
+  bool el_launched = false;
+  void *el_stream = nullptr;
   // ctcd_greedy_stream_decode (greedy.h "live streams"): a chunk call's per-stream arguments travel like ctcd_stream_decode's (two
   // page-locked slots, an event each, one copy per call)
   Buf gs_args;
@@ -496,6 +503,20 @@ int edit_scratch(ctcd_decoder *d, size_t bytes, void **p) {
   return CTCD_OK;
 }
 void edit_note_slots(ctcd_decoder *d, long long slots) { d->ed_slots = slots; }
+// ... and the long edit pairs' (editlong.hip): the mode, the two buffers, and what ctcd_last_edit_long needs
+int edit_long_waves(const ctcd_decoder *d) { return d->el_waves; }
+int edit_long_buffers(ctcd_decoder *d, size_t list_bytes, size_t slot_bytes, void **list, void **slots) {
+  std::lock_guard<std::mutex> lock(d->mu);
+  if (const int rc = d->el_list.ensure(list_bytes)) return rc;
+  if (const int rc = d->el_slots.ensure(slot_bytes)) return rc;
+  *list = d->el_list.p;
+  *slots = d->el_slots.p;
+  return CTCD_OK;
+}
+void edit_note_long(ctcd_decoder *d, bool launched, void *stream) {
+  d->el_launched = launched;
+  d->el_stream = stream;
+}
 }  // namespace ctcedit
 
 // ... and the greedy decode's (greedy.hip), beyond the alignment's hooks: its frame records
@@ -768,7 +789,7 @@ void ctcd_destroy(ctcd_decoder *d) {
   d->cp_scratch.release();
   if (d->h_cp) (void)hipHostFree(d->h_cp);
   d->sk_rows.release(); d->sk_kept.release(); d->sk_lsm.release();
-  d->al_bp.release(); d->al_lsm.release(); d->po_alpha.release(); d->gr_frames.release(); d->gs_args.release(); d->ed_bp.release();
+  d->al_bp.release(); d->al_lsm.release(); d->po_alpha.release(); d->gr_frames.release(); d->gs_args.release(); d->ed_bp.release(); d->el_list.release(); d->el_slots.release();
   for (int i = 0; i < 2; ++i) {
     if (d->h_gsargs[i]) (void)hipHostFree(d->h_gsargs[i]);
     if (d->ev_gsargs[i]) (void)hipEventDestroy(d->ev_gsargs[i]);
@@ -847,6 +868,24 @@ int ctcd_set_edit_scratch(ctcd_decoder *d, long long bytes) {
   return CTCD_OK;
 }
 long long ctcd_last_edit_slots(const ctcd_decoder *d) { return d ? d->ed_slots : -1; }
+// Long edit pairs (editlong.hip): the waves of a long pair's workgroup, and the pairs the long kernel ran in the last edit call.
+int ctcd_set_edit_long(ctcd_decoder *d, int waves) {
+  if (!d || (waves != 0 && !ctcedit::long_waves_ok(waves))) return fail(CTCD_EINVAL, "ctcd_set_edit_long: a decoder and waves of 0 (off), 2, 4, 8 or 16 required");
+  d->el_waves = waves;
+  return CTCD_OK;
+}
+long long ctcd_last_edit_long(ctcd_decoder *d) {
+  if (!d) return -1;
+  if (!d->el_launched) return 0;
+  // the count lives on the device alone: the first word of the list, read behind the call's kernels
+  ctcdev::DeviceGuard guard;
+  if (guard.enter(d->device) != hipSuccess) return fail(CTCD_EHIP, std::string("hipSetDevice: ") + hipGetErrorString(guard.err));
+  unsigned n = 0;
+  hipError_t e = hipMemcpyAsync(&n, d->el_list.p, sizeof(n), hipMemcpyDeviceToHost, (hipStream_t)d->el_stream);
+  if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)d->el_stream);
+  if (e != hipSuccess) return fail(CTCD_EHIP, std::string("ctcd_last_edit_long: ") + hipGetErrorString(e));
+  return (long long)n;
+}
 
 int ctcd_set_cu_sharing(ctcd_decoder *d, int mode) {
   if (!d || mode < -1 || mode > 1) return fail(CTCD_EINVAL, "cu sharing mode must be -1 (automatic), 0 or 1");

@@ -79,24 +79,26 @@ template <int C> struct Lane {
   int diag;      // column lane * C of the row before the next one to compute
   int32_t tok;   // the streamed token of the lane's latest row: what it hands to lane + 1
 };
-template <int C> CTC_HD void lane_init(Lane<C> &L, int lane, const int32_t *strip, int n) {
+// col0: the columns in front of lane 0's first -- 0 for a strip that one wave holds; a tile of a longer strip (editlong.h) starts further on
+template <int C> CTC_HD void lane_init(Lane<C> &L, int lane, const int32_t *strip, int n, int col0 = 0) {
 #pragma unroll
   for (int k = 0; k < C; ++k) {
-    const int col = lane * C + k;  // 0-based token index; D's column col + 1
+    const int col = col0 + lane * C + k;  // 0-based token index; D's column col + 1
     const int32_t tok = strip[col < n ? col : n - 1];  // (an index inside the row whatever the column: the loads need no branch)
     L.a[k] = col < n ? tok : 0;
     L.prev[k] = col + 1;  // row 0
   }
-  L.diag = lane * C;
+  L.diag = col0 + lane * C;
   L.tok = 0;
 }
 // Step s.  in_left / in_tok: prev[C - 1] and tok of lane - 1 as they stood BEFORE this step (lane 0: ignored); fresh: the streamed
-// token of row s + 1 (lane 0 alone looks at it).
-template <int C> CTC_HD void lane_step(Lane<C> &L, int lane, int s, int m, int in_left, int32_t in_tok, int32_t fresh) {
+// token of row s + 1 (lane 0 alone looks at it).  EDGE: lane 0's left edge comes from outside too -- in_left is column col0 of its row,
+// which the caller knows (editlong.h) -- instead of being the row number.
+template <int C, bool EDGE = false> CTC_HD void lane_step(Lane<C> &L, int lane, int s, int m, int in_left, int32_t in_tok, int32_t fresh) {
   const int r = lane_row(s, lane);
   if (r < 1 || r > m) return;
   const int32_t t = lane == 0 ? fresh : in_tok;
-  int left = lane == 0 ? r : in_left;
+  int left = !EDGE && lane == 0 ? r : in_left;
   int diag = L.diag;
   L.diag = left;
   L.tok = t;

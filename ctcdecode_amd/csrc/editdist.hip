@@ -6,6 +6,10 @@
 //                          tokens and the lane's row of D stay in registers; a lane's last column and its streamed token move to the
 //                          next lane by a one-lane shift across the wave; the streamed row is read 64 tokens at a time, a block
 //                          ahead of its use, and handed to lane 0 by a read of one lane.  No LDS, no scratch.
+//                          <LONG = false> is the kernel of every call with ctcd_set_edit_long off, or with min(L, Lq) <= 2048.
+//                          <true> differs in one uniform branch: a pair whose strip is beyond 2048 columns is not swept; lane 0
+//                          appends its work index to the decoder's list of long pairs (one atomicAdd on the counter), and the
+//                          long kernel of editlong.hip, launched behind this one, takes it from there.
 // Every store is a plain C++ store; there is no inline assembly.
 #include <hip/hip_runtime.h>
 
@@ -13,7 +17,7 @@
 
 #include "../../include/ctcdecode_amd.h"
 #include "device_guard.h"
-#include "editdist.h"
+#include "editlong.h"
 
 namespace ctcedit {
 
@@ -59,8 +63,10 @@ __device__ __forceinline__ bool item_ok_wave(const int32_t *x_lens, int b, int R
   return __ballot(!ok) == 0ull;
 }
 
+template <bool LONG>
 __global__ void __launch_bounds__(kEditThreads) edit_distance_kernel(const int32_t *x, const int32_t *x_lens, int B, int R, int L, const int32_t *y,
-                                                                    const int32_t *y_lens, int Q, int Lq, long long work, int32_t *out, int32_t *status) {
+                                                                    const int32_t *y_lens, int Q, int Lq, long long work, int32_t *out, int32_t *status,
+                                                                    long long *long_list, unsigned *long_count) {
   const bool pairwise = y == nullptr;  // (the host has set Q = R, Lq = L)
   const int lane = (int)threadIdx.x & (kEditLanes - 1);
   const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x / kEditLanes);
@@ -84,6 +90,10 @@ __global__ void __launch_bounds__(kEditThreads) edit_distance_kernel(const int32
         const bool x_strip = lx <= ly;
         const int32_t *strip = x_strip ? xr : yr, *stream = x_strip ? yr : xr;
         const int n = x_strip ? lx : ly, m = x_strip ? ly : lx;  // 1 <= n <= min(L, Lq) <= 2048, n <= m
+        if (LONG && long_pair(n, m, false)) {  // (the same for the whole wave; fewer than `work` appends: inside the list)
+          if (lane == 0) long_list[atomicAdd(long_count, 1u)] = w;
+          continue;
+        }
         switch (strip_class(n)) {  // (the same for the whole wave)
           case 1: d = sweep<1>(strip, n, stream, m, lane); break;
           case 2: d = sweep<2>(strip, n, stream, m, lane); break;
@@ -124,12 +134,14 @@ int ctcd_edit_distance(ctcd_decoder *d, const int32_t *x, const int32_t *x_lens,
   if (B < 0 || R < 0 || L < 0 || Q < 0 || Lq < 0) return edit_fail(CTCD_EINVAL, (f + "B, R, L, Q, Lq >= 0 required").c_str());
   EditDecoderInfo inf;
   if (const int rc = edit_decoder_info(d, &inf)) return rc;
+  edit_note_long(d, false, stream);  // (ctcd_last_edit_long: no long pair yet)
   if (B == 0 || R == 0 || Q == 0) {
     edit_note_pairs(d, 0, 0);
     return CTCD_OK;
   }
   if (!x_lens || !out || (!x && L > 0) || (!pairwise && !y_lens)) return edit_fail(CTCD_EINVAL, (f + "null tensor").c_str());
-  if ((L < Lq ? L : Lq) > kEditMaxStrip)
+  const bool long_mode = edit_long_waves(d) > 0 && (L < Lq ? L : Lq) > kEditMaxStrip;
+  if ((L < Lq ? L : Lq) > kEditMaxStrip && !long_mode)
     return edit_fail(CTCD_EUNSUPPORTED, (f + "min(L, Lq) > 2048: the shorter row of a pair lives in one wave's registers, 32 columns per lane").c_str());
   if (L > kEditMaxDim || Lq > kEditMaxDim) return edit_fail(CTCD_EUNSUPPORTED, (f + "rows of more than 2^30 positions").c_str());
   if ((long long)B * R > 0x7fffffffLL || (long long)B * Q > 0x7fffffffLL) return edit_fail(CTCD_EUNSUPPORTED, (f + "too many rows for one launch").c_str());
@@ -140,11 +152,19 @@ int ctcd_edit_distance(ctcd_decoder *d, const int32_t *x, const int32_t *x_lens,
   const long long cap = inf.cap > 0 ? (inf.cap < (1ll << 20) ? inf.cap : (1ll << 20)) : (long long)(inf.cus > 0 ? inf.cus : 1) * (kEditWavesPerCu / kEditWaves);
   long long grid = (work + kEditWaves - 1) / kEditWaves;
   grid = grid < 1 ? 1 : (grid > cap ? cap : grid);  // (a pairwise call of one-row items has no pair and a diagonal to write)
-  hipLaunchKernelGGL(edit_distance_kernel, dim3((unsigned)grid), dim3(kEditThreads), 0, (hipStream_t)stream, x, x_lens, B, R, L, y, y_lens, Q, Lq, work, out,
-                     status);
+  LongPlan plan = {};
+  if (long_mode) {  // the list's counter is cleared in front of the per-wave kernel, the long kernel reads it behind
+    if (const int rc = long_prepare(d, inf, f.c_str(), false, L, Lq, work, stream, &plan)) return rc;
+    hipLaunchKernelGGL(edit_distance_kernel<true>, dim3((unsigned)grid), dim3(kEditThreads), 0, (hipStream_t)stream, x, x_lens, B, R, L, y, y_lens, Q, Lq, work,
+                       out, status, plan.list, plan.count);
+  } else {
+    hipLaunchKernelGGL(edit_distance_kernel<false>, dim3((unsigned)grid), dim3(kEditThreads), 0, (hipStream_t)stream, x, x_lens, B, R, L, y, y_lens, Q, Lq, work,
+                       out, status, (long long *)nullptr, (unsigned *)nullptr);
+  }
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return edit_fail(CTCD_EHIP, (std::string("edit distance: ") + hipGetErrorString(e)).c_str());
   edit_note_pairs(d, work, grid);
+  if (long_mode) return long_launch(d, plan, false, x, x_lens, R, L, y, y_lens, Q, Lq, out, stream);
   return CTCD_OK;
 }
 

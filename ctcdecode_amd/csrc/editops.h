@@ -48,14 +48,15 @@ CTC_HD int key_cell_dir(int up, int left, int diag, int32_t a, int32_t b, bool x
 
 // ---- the counts ----------------------------------------------------------------------------------------------------------------------
 // (H, S, Del, I) of every optimal alignment of rows of lx and ly tokens whose key is `key`; empty rows included: key = (lx + ly, 0)
-CTC_HD void counts_of(int key, int lx, int ly, int32_t out[4]) {
-  const int D = key >> kKeyShift, S = key & kKeyMask;
+// ... from D and S apart: what a key of any width comes down to (editlong.h carries them in 64 bits)
+CTC_HD void counts_of_ds(int D, int S, int lx, int ly, int32_t out[4]) {
   const int ins = (D - S + lx - ly) / 2, del = (D - S - lx + ly) / 2;
   out[0] = lx - S - ins;
   out[1] = S;
   out[2] = del;
   out[3] = ins;
 }
+CTC_HD void counts_of(int key, int lx, int ly, int32_t out[4]) { counts_of_ds(key >> kKeyShift, key & kKeyMask, lx, ly, out); }
 CTC_HD int key_trivial(int lx, int ly) { return (lx + ly) * kKeyEdit; }  // pair_trivial's answer as a key
 
 // ---- the back-pointer slot ---------------------------------------------------------------------------------------------------------------

@@ -3,6 +3,9 @@
 // schedule -- a wave per pair, four pairs per workgroup, a persistent grid, the shorter row as the strip in registers, the longer one
 // streamed past it 64 tokens ahead, two one-lane shifts per step -- over the packed key (D, S) of editops.h:
 //   edit_counts_kernel   the sweep and an epilogue that turns K[m][n] and the two lengths into (H, S, Del, I).  No LDS, no scratch.
+//                        <LONG = true> (ctcd_set_edit_long on and min(L, Lq) > 2048) leaves a pair whose strip is beyond 2048 columns,
+//                        or whose streamed row is beyond the packed key's 262144, to the long kernel of editlong.hip, as
+//                        edit_distance_kernel<true> does; <false> is the kernel of every other call.
 //   edit_align_kernel    the sweep also resolves, per cell, the direction the canonical walk takes there, in x / y terms from the
 //                        wave-uniform role flag; a lane's C directions of a step are one 32- or 64-bit word, stored to the wave's slot
 //                        of the decoder-owned back-pointer scratch.  Then the wave walks back from (lx, ly): it fetches 64 rows of the
@@ -15,7 +18,7 @@
 
 #include "../../include/ctcdecode_amd.h"
 #include "device_guard.h"
-#include "editops.h"
+#include "editlong.h"
 
 namespace ctcedit {
 
@@ -88,8 +91,10 @@ __device__ __forceinline__ bool ops_item_ok(const int32_t *x_lens, int b, int R,
   return __ballot(!ok) == 0ull;
 }
 
+template <bool LONG>
 __global__ void __launch_bounds__(kEditThreads) edit_counts_kernel(const int32_t *x, const int32_t *x_lens, int B, int R, int L, const int32_t *y,
-                                                                  const int32_t *y_lens, int Q, int Lq, long long work, int32_t *out, int32_t *status) {
+                                                                  const int32_t *y_lens, int Q, int Lq, long long work, int32_t *out, int32_t *status,
+                                                                  long long *long_list, unsigned *long_count) {
   const bool pairwise = y == nullptr;  // (the host has set Q = R, Lq = L)
   const int lane = (int)threadIdx.x & (kEditLanes - 1);
   const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x / kEditLanes);
@@ -114,6 +119,10 @@ __global__ void __launch_bounds__(kEditThreads) edit_counts_kernel(const int32_t
         const bool x_strip = lx <= ly;
         const int32_t *strip = x_strip ? xr : yr, *stream = x_strip ? yr : xr;
         const int n = x_strip ? lx : ly, m = x_strip ? ly : lx;  // 1 <= n <= min(L, Lq) <= 2048, n <= m <= 2^18
+        if (LONG && long_pair(n, m, true)) {  // (the same for the whole wave; fewer than `work` appends: inside the list)
+          if (lane == 0) long_list[atomicAdd(long_count, 1u)] = w;
+          continue;
+        }
         switch (strip_class(n)) {  // (the same for the whole wave)
           case 1: key = key_sweep<1, false>(strip, n, stream, m, lane, x_strip, nullptr); break;
           case 2: key = key_sweep<2, false>(strip, n, stream, m, lane, x_strip, nullptr); break;
@@ -199,10 +208,11 @@ __global__ void __launch_bounds__(kEditThreads) __attribute__((amdgpu_waves_per_
 }
 
 // the checks both entry points share with ctcd_edit_distance, and the limit of the packed key.  -> CTCD_OK, or the code to return
-static int ops_check(const std::string &f, int B, int R, int L, int Q, int Lq) {
-  if ((L < Lq ? L : Lq) > kEditMaxStrip)
+// (long_mode: ctcd_set_edit_long on and min(L, Lq) > 2048 -- the long kernel takes what these two limits are about)
+static int ops_check(const std::string &f, int B, int R, int L, int Q, int Lq, bool long_mode = false) {
+  if ((L < Lq ? L : Lq) > kEditMaxStrip && !long_mode)
     return edit_fail(CTCD_EUNSUPPORTED, (f + "min(L, Lq) > 2048: the shorter row of a pair lives in one wave's registers, 32 columns per lane").c_str());
-  if ((L < Lq ? Lq : L) > kOpsMaxDim)
+  if ((L < Lq ? Lq : L) > (long_mode ? kEditMaxDim : kOpsMaxDim))
     return edit_fail(CTCD_EUNSUPPORTED, (f + "max(L, Lq) > 262144: the packed key (distance * 4096 + substitutions) would leave int32").c_str());
   if ((long long)B * R > 0x7fffffffLL || (long long)B * Q > 0x7fffffffLL) return edit_fail(CTCD_EUNSUPPORTED, (f + "too many rows for one launch").c_str());
   return CTCD_OK;
@@ -229,20 +239,31 @@ int ctcd_edit_counts(ctcd_decoder *d, const int32_t *x, const int32_t *x_lens, i
   if (B < 0 || R < 0 || L < 0 || Q < 0 || Lq < 0) return edit_fail(CTCD_EINVAL, (f + "B, R, L, Q, Lq >= 0 required").c_str());
   EditDecoderInfo inf;
   if (const int rc = edit_decoder_info(d, &inf)) return rc;
+  edit_note_long(d, false, stream);  // (ctcd_last_edit_long: no long pair yet)
   if (B == 0 || R == 0 || Q == 0) {
     edit_note_pairs(d, 0, 0);
     return CTCD_OK;
   }
   if (!x_lens || !out || (!x && L > 0) || (!pairwise && !y_lens)) return edit_fail(CTCD_EINVAL, (f + "null tensor").c_str());
-  if (const int rc = ops_check(f, B, R, L, Q, Lq)) return rc;
+  const bool long_mode = edit_long_waves(d) > 0 && (L < Lq ? L : Lq) > kEditMaxStrip;
+  if (const int rc = ops_check(f, B, R, L, Q, Lq, long_mode)) return rc;
   const long long work = pairs_per_item(R, Q, pairwise) * B;
   ctcdev::DeviceGuard guard;
   if (guard.enter(inf.device) != hipSuccess) return edit_fail(CTCD_EHIP, (std::string("hipSetDevice: ") + hipGetErrorString(guard.err)).c_str());
   const long long grid = ops_grid(inf, work);  // (a pairwise call of one-row items has no pair and a diagonal to write)
-  hipLaunchKernelGGL(edit_counts_kernel, dim3((unsigned)grid), dim3(kEditThreads), 0, (hipStream_t)stream, x, x_lens, B, R, L, y, y_lens, Q, Lq, work, out, status);
+  LongPlan plan = {};
+  if (long_mode) {  // the list's counter is cleared in front of the per-wave kernel, the long kernel reads it behind
+    if (const int rc = long_prepare(d, inf, f.c_str(), true, L, Lq, work, stream, &plan)) return rc;
+    hipLaunchKernelGGL(edit_counts_kernel<true>, dim3((unsigned)grid), dim3(kEditThreads), 0, (hipStream_t)stream, x, x_lens, B, R, L, y, y_lens, Q, Lq, work, out,
+                       status, plan.list, plan.count);
+  } else {
+    hipLaunchKernelGGL(edit_counts_kernel<false>, dim3((unsigned)grid), dim3(kEditThreads), 0, (hipStream_t)stream, x, x_lens, B, R, L, y, y_lens, Q, Lq, work, out,
+                       status, (long long *)nullptr, (unsigned *)nullptr);
+  }
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return edit_fail(CTCD_EHIP, (std::string("edit counts: ") + hipGetErrorString(e)).c_str());
   edit_note_pairs(d, work, grid);
+  if (long_mode) return long_launch(d, plan, true, x, x_lens, R, L, y, y_lens, Q, Lq, out, stream);
   return CTCD_OK;
 }
 

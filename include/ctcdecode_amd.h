@@ -862,8 +862,8 @@ int ctcd_greedy_stream_info(ctcd_decoder *dec, const ctcd_greedy_stream *st, lon
  * CTCD_EINVAL, and nothing is launched: negative sizes, or a NULL tensor that is needed (x_lens, out; x when L > 0; y_lens when y is
  * given).  B == 0, R == 0 or Q == 0 is CTCD_OK and launches nothing.  L == 0 or Lq == 0 is legal: the distances are the other side's
  * lengths (in the general mode y must still be a non-NULL pointer; it is not read).
- * CTCD_EUNSUPPORTED: min(L, Lq) > 2048 (pairwise mode: L > 2048); the longer side is bounded only by 2^30 positions per row, and B x R
- * and B x Q by 2^31 - 1.
+ * CTCD_EUNSUPPORTED: min(L, Lq) > 2048 (pairwise mode: L > 2048) unless ctcd_set_edit_long is on ("Long edit pairs" below); the
+ * longer side is bounded only by 2^30 positions per row, and B x R and B x Q by 2^31 - 1.
  * ctcd_last_edit_pairs: the distances the last ctcd_edit_distance computed -- B x R x Q in the general mode, B x R x (R - 1) / 2 in
  * pairwise mode (0: none yet, or an empty call; -1: dec == NULL).
  * ctcd_set_edit_grid: the most workgroups (of four waves, a pair each) the launch uses; 0 = the default, two per compute unit.  The
@@ -908,14 +908,16 @@ long long ctcd_last_edit_grid(const ctcd_decoder *dec);
  *
  * ctcd_edit_counts: the arguments, modes, validity rule, status word and error codes of ctcd_edit_distance; out int32 [B][R][Q][4] =
  * (H, S, Del, I).  Pairwise mode (y == NULL): [i][j] takes row i as x; [j][i] is the same with Del and I exchanged; the diagonal is
- * (len, 0, 0, 0).  An invalid item: all words 0.  One more limit: max(L, Lq) > 262144 is CTCD_EUNSUPPORTED.  ctcd_set_edit_grid,
+ * (len, 0, 0, 0).  An invalid item: all words 0.  One more limit: max(L, Lq) > 262144 is CTCD_EUNSUPPORTED (not for a call that
+ * "Long edit pairs" accepts).  ctcd_set_edit_grid,
  * ctcd_last_edit_pairs and ctcd_last_edit_grid apply to it (and to ctcd_edit_align) as to ctcd_edit_distance.
  *
  * ctcd_edit_align: the general mode only; y == NULL is CTCD_EINVAL.  x_to_y int32 [B][R][Q][L]: x_to_y[..][p] is the index of x[p]'s
  * partner in y on the canonical alignment, or -1 if x[p] is an insertion, and -1 for p >= lx.  y_to_x int32 [B][R][Q][Lq] is the same
  * from the other side (-1: a deletion, or beyond ly).  counts [B][R][Q][4] as above, or NULL.  Every word of all three is written; an
  * invalid item has all maps -1 and all counts 0.  Everything is device memory and asynchronous on `stream`; nothing is read on the
- * host.  The limits are those of ctcd_edit_counts.
+ * host.  The limits are those of ctcd_edit_counts with ctcd_set_edit_long off, whatever that mode is: alignments of rows beyond
+ * 2048 are out of scope (two bits per cell of 30000 x 30000 want another design, Hirschberg's or a band).
  * The directions of the walk, two bits per cell, live in decoder-owned scratch: one slot per wave in flight, of max(L, Lq) rows of 64
  * words -- 4 bytes each while min(L, Lq) <= 1024, 8 bytes beyond -- sized from the tensor dimensions alone.  The launch has as many
  * waves as the usual grid, as the call has pairs, or as the budget has slots for, whichever is least; only that many slots are
@@ -935,6 +937,28 @@ int ctcd_edit_align(ctcd_decoder *dec, const int32_t *x /* [B][R][L] */, const i
                     int32_t *status /* [B] zeroed by the caller, or NULL */, void *stream);
 int ctcd_set_edit_scratch(ctcd_decoder *dec, long long bytes);   /* budget of the back-pointer scratch; 0 = the default */
 long long ctcd_last_edit_slots(const ctcd_decoder *dec);
+
+/* ---- Long edit pairs: ctcd_edit_distance and ctcd_edit_counts for pairs whose SHORTER row is beyond 2048 tokens -- a chapter against
+ * its transcript at character level.  The definitions of "Edit distance" and "Edit operations" hold unchanged; so do the modes
+ * (pairwise included), the validity rule and the status word.
+ * ctcd_set_edit_long(dec, waves): waves = 2, 4, 8 or 16 turns the mode on, 0 turns it off (the default: everything above, the
+ * CTCD_EUNSUPPORTED at min(L, Lq) = 2049 included); any other value is CTCD_EINVAL.  With the mode on a call with min(L, Lq) > 2048 is
+ * accepted.  The lengths stay on the device: the usual kernel runs every pair it can hold -- unchanged results -- and appends the
+ * others to a decoder-owned list; a second kernel behind it gives each listed pair a workgroup of `waves` waves, which cut the
+ * shorter row into tiles of 2048 columns and pipeline them, a tile two blocks of 64 rows behind its left neighbour.  `waves` never
+ * changes a result.  A call with min(L, Lq) <= 2048 launches what it launches with the mode off.
+ * Counts of long pairs carry (D, S) in 64 bits, so max(L, Lq) <= 262144 does not apply to an accepted call (a pair whose longer row
+ * is beyond it runs on the long kernel whatever its shorter row); rows stay within 2^30 positions.
+ * Scratch: a long pair's workgroup owns a slot of 4 x (max(L, Lq) + 1) bytes (counts: 8 x), rounded up to 256, under the budget of
+ * ctcd_set_edit_scratch: as many workgroups run as the budget has slots for, as ctcd_set_edit_grid allows (default: one per compute
+ * unit) and as the call has pairs; if one slot does not fit the call returns CTCD_EUNSUPPORTED, the byte counts in ctcd_last_error,
+ * and the decoder stays usable.  ctcd_last_edit_slots reports the slots of a call that launched the long kernel; any other ctcd_edit_distance or ctcd_edit_counts
+ * leaves that value as it was.  The list takes 8 bytes per pair of the call.
+ * ctcd_last_edit_long: the pairs the long kernel ran in the last ctcd_edit_distance or ctcd_edit_counts: 0 if that call did not
+ * launch it (mode off, or min(L, Lq) <= 2048), -1: dec == NULL.  It reads one device word and waits for that call's stream.
+ * Not provided: ctcd_edit_align beyond 2048, weighted costs, several workgroups on one pair. */
+int ctcd_set_edit_long(ctcd_decoder *dec, int waves);   /* 0 = off (the default), 2, 4, 8, 16 */
+long long ctcd_last_edit_long(ctcd_decoder *dec);
 
 /* Tuning / introspection. */
 int ctcd_set_threads(ctcd_decoder *dec, int threads_per_workgroup); /* 0 = automatic (default); else a power of two in [64, 1024] */
