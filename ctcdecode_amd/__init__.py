@@ -1082,7 +1082,9 @@ class CTCBeamDecoder(object):
 
         ``references`` are required (there is no pairwise mode); tensor handling and errors are ``edit_counts``'.  The walk's
         directions live in decoder-owned scratch (``set_edit_scratch``); a call whose single slot does not fit the budget raises
-        ``NotImplementedError``.  ``set_edit_long`` does not reach here: alignments keep ``min(L, Lq) <= 2048``."""
+        ``NotImplementedError``.  With ``set_edit_long`` on, ``min(L, Lq) > 2048`` is accepted as in ``edit_counts``: a pair whose
+        shorter row is beyond 2048 tokens is aligned from checkpoints of the key matrix, in scratch that grows with ``L + Lq`` (11 MB
+        per workgroup at 30000 x 30000); the maps and counts are the same definition's."""
         if references is None:
             raise ValueError("edit_align needs references: alignments are not provided in pairwise mode")
         on_device = beam_results.is_cuda
@@ -1110,16 +1112,17 @@ class CTCBeamDecoder(object):
         return int(_native.lib.ctcd_last_edit_slots(self._handle))
 
     def set_edit_long(self, waves=16):
-        """Long pairs for ``edit_distance``, ``edit_counts`` and ``mbr_select`` (include/ctcdecode_amd.h ctcd_set_edit_long): with
+        """Long pairs for ``edit_distance``, ``edit_counts``, ``edit_align`` and ``mbr_select`` (include/ctcdecode_amd.h ctcd_set_edit_long): with
         ``waves`` of 2, 4, 8 or 16, tensors with ``min(L, Lq) > 2048`` are accepted, and a pair whose shorter row is beyond 2048 tokens
         runs on one workgroup of that many waves, which share the row in tiles of 2048 columns; 0 turns the mode off (the default).
         ``waves`` never changes a result.  A long pair needs ``4 x (max(L, Lq) + 1)`` bytes of scratch per workgroup, twice that for
         counts, under the budget of ``set_edit_scratch``; a call whose single slot does not fit raises ``NotImplementedError``.
-        ``edit_align`` keeps its limit.  Raises ``ValueError`` for any other ``waves``."""
+        ``edit_align`` of a long pair needs a slot of column and row checkpoints and a 512 KiB block buffer instead (the header's
+        "Long edit pairs").  Raises ``ValueError`` for any other ``waves``."""
         _native.check(_native.lib.ctcd_set_edit_long(self._handle, int(waves)))
 
     def last_edit_long(self):
-        """The pairs the long kernel ran in the last ``edit_distance`` or ``edit_counts``: 0 if none, and 0 with the mode off.  Reads
+        """The pairs the long kernel ran in the last ``edit_distance``, ``edit_counts`` or ``edit_align``: 0 if none, and 0 with the mode off.  Reads
         one word from the device, behind that call's kernels."""
         n = int(_native.lib.ctcd_last_edit_long(self._handle))
         if n < 0:  # (an error code of the read)

@@ -158,9 +158,14 @@ __global__ void __launch_bounds__(kEditThreads) edit_counts_kernel(const int32_t
 
 // General mode only.  slots: the waves that have a slot of slot_bytes in scratch, wave g the g-th; the others leave at once, and the
 // waves that stay stride over the pairs by their own number.
+// <LONG = true> (ctcd_set_edit_long on and min(L, Lq) > 2048) fills the maps of every pair and leaves a pair whose strip is beyond 2048
+// columns, or whose streamed row is beyond the packed key's 262144, to the long kernel of editlong.hip -- its walk and its counts --
+// as edit_counts_kernel<true> does; <false> is the kernel of every other call.
+template <bool LONG>
 __global__ void __launch_bounds__(kEditThreads) __attribute__((amdgpu_waves_per_eu(2))) edit_align_kernel(const int32_t *x, const int32_t *x_lens, int R, int L, const int32_t *y, const int32_t *y_lens,
                                                                  int Q, int Lq, long long work, char *scratch, size_t slot_bytes, long long slots,
-                                                                 int32_t *x_to_y, int32_t *y_to_x, int32_t *counts, int32_t *status) {
+                                                                 int32_t *x_to_y, int32_t *y_to_x, int32_t *counts, int32_t *status, long long *long_list,
+                                                                 unsigned *long_count) {
   const int lane = (int)threadIdx.x & (kEditLanes - 1);
   const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x / kEditLanes);
   const long long first = (long long)blockIdx.x * kEditWaves + wave;
@@ -189,6 +194,11 @@ __global__ void __launch_bounds__(kEditThreads) __attribute__((amdgpu_waves_per_
         const bool x_strip = lx <= ly;
         const int32_t *strip = x_strip ? xr : yr, *stream = x_strip ? yr : xr;
         const int n = x_strip ? lx : ly, m = x_strip ? ly : lx;  // m <= max(L, Lq) rows of 64 words of the class: inside slot_bytes
+        if (LONG && long_pair(n, m, true)) {  // (the same for the whole wave; fewer than `work` appends: inside the list)
+          if (lane == 0) long_list[atomicAdd(long_count, 1u)] = w;
+          continue;
+        }
+        // (LONG: n <= 2048 and m <= 262144 rows of 64 words from here on, long_short_slot_bytes)
         switch (strip_class(n)) {
           case 1: key = align_class<1>(strip, n, stream, m, lane, x_strip, slot, xm, ym); break;
           case 2: key = align_class<2>(strip, n, stream, m, lane, x_strip, slot, xm, ym); break;
@@ -275,18 +285,20 @@ int ctcd_edit_align(ctcd_decoder *d, const int32_t *x, const int32_t *x_lens, in
   if (B < 0 || R < 0 || L < 0 || Q < 0 || Lq < 0) return edit_fail(CTCD_EINVAL, (f + "B, R, L, Q, Lq >= 0 required").c_str());
   EditDecoderInfo inf;
   if (const int rc = edit_decoder_info(d, &inf)) return rc;
+  edit_note_long(d, false, stream);  // (ctcd_last_edit_long: no long pair yet)
   if (B == 0 || R == 0 || Q == 0) {
     edit_note_pairs(d, 0, 0);
     edit_note_slots(d, 0);
     return CTCD_OK;
   }
   if (!x_lens || !y_lens || (!x && L > 0) || (!x_to_y && L > 0) || (!y_to_x && Lq > 0)) return edit_fail(CTCD_EINVAL, (f + "null tensor").c_str());
-  if (const int rc = ops_check(f, B, R, L, Q, Lq)) return rc;
+  const bool long_mode = edit_long_waves(d) > 0 && (L < Lq ? L : Lq) > kEditMaxStrip;
+  if (const int rc = ops_check(f, B, R, L, Q, Lq, long_mode)) return rc;
   const long long work = pairs_per_item(R, Q, false) * B;
   // a slot per wave in flight: the usual grid's waves, or as many as the budget holds
   long long slots = ops_grid(inf, work) * kEditWaves;
   slots = slots < work ? slots : work;
-  const size_t slot_bytes = ops_slot_bytes(L, Lq);
+  const size_t slot_bytes = long_mode ? long_short_slot_bytes(L, Lq) : ops_slot_bytes(L, Lq);
   if (slot_bytes) {
     const long long budget = edit_budget(d) > 0 ? edit_budget(d) : kOpsDefaultScratch, fit = budget / (long long)slot_bytes;
     if (fit < 1)
@@ -298,14 +310,22 @@ int ctcd_edit_align(ctcd_decoder *d, const int32_t *x, const int32_t *x_lens, in
   ctcdev::DeviceGuard guard;
   if (guard.enter(inf.device) != hipSuccess) return edit_fail(CTCD_EHIP, (std::string("hipSetDevice: ") + hipGetErrorString(guard.err)).c_str());
   void *scratch = nullptr;
-  if (slot_bytes)
-    if (const int rc = edit_scratch(d, (size_t)slots * slot_bytes, &scratch)) return rc;
-  hipLaunchKernelGGL(edit_align_kernel, dim3((unsigned)grid), dim3(kEditThreads), 0, (hipStream_t)stream, x, x_lens, R, L, y, y_lens, Q, Lq, work, (char *)scratch,
-                     slot_bytes, slots, x_to_y, y_to_x, counts, status);
+  LongPlan plan = {};
+  if (long_mode) {  // one allocation for this kernel's slots and, behind it on the stream, the long kernel's; the list's counter is cleared
+    if (const int rc = long_prepare_align(d, inf, f.c_str(), L, Lq, work, (size_t)slots * slot_bytes, stream, &plan)) return rc;
+    hipLaunchKernelGGL(edit_align_kernel<true>, dim3((unsigned)grid), dim3(kEditThreads), 0, (hipStream_t)stream, x, x_lens, R, L, y, y_lens, Q, Lq, work, plan.slots,
+                       slot_bytes, slots, x_to_y, y_to_x, counts, status, plan.list, plan.count);
+  } else {
+    if (slot_bytes)
+      if (const int rc = edit_scratch(d, (size_t)slots * slot_bytes, &scratch)) return rc;
+    hipLaunchKernelGGL(edit_align_kernel<false>, dim3((unsigned)grid), dim3(kEditThreads), 0, (hipStream_t)stream, x, x_lens, R, L, y, y_lens, Q, Lq, work, (char *)scratch,
+                       slot_bytes, slots, x_to_y, y_to_x, counts, status, (long long *)nullptr, (unsigned *)nullptr);
+  }
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return edit_fail(CTCD_EHIP, (std::string("edit align: ") + hipGetErrorString(e)).c_str());
   edit_note_pairs(d, work, grid);
   edit_note_slots(d, slots);
+  if (long_mode) return long_launch_align(d, plan, x, x_lens, R, L, y, y_lens, Q, Lq, x_to_y, y_to_x, counts, stream);
   return CTCD_OK;
 }
 

@@ -916,8 +916,9 @@ long long ctcd_last_edit_grid(const ctcd_decoder *dec);
  * partner in y on the canonical alignment, or -1 if x[p] is an insertion, and -1 for p >= lx.  y_to_x int32 [B][R][Q][Lq] is the same
  * from the other side (-1: a deletion, or beyond ly).  counts [B][R][Q][4] as above, or NULL.  Every word of all three is written; an
  * invalid item has all maps -1 and all counts 0.  Everything is device memory and asynchronous on `stream`; nothing is read on the
- * host.  The limits are those of ctcd_edit_counts with ctcd_set_edit_long off, whatever that mode is: alignments of rows beyond
- * 2048 are out of scope (two bits per cell of 30000 x 30000 want another design, Hirschberg's or a band).
+ * host.  The limits are those of ctcd_edit_counts: with ctcd_set_edit_long off min(L, Lq) <= 2048 and max(L, Lq) <= 262144; with it
+ * on a call with min(L, Lq) > 2048 is accepted and neither holds ("Long edit pairs" below: the same maps and counts, from checkpoints
+ * of the key matrix instead of two bits per cell).
  * The directions of the walk, two bits per cell, live in decoder-owned scratch: one slot per wave in flight, of max(L, Lq) rows of 64
  * words -- 4 bytes each while min(L, Lq) <= 1024, 8 bytes beyond -- sized from the tensor dimensions alone.  The launch has as many
  * waves as the usual grid, as the call has pairs, or as the budget has slots for, whichever is least; only that many slots are
@@ -954,9 +955,20 @@ long long ctcd_last_edit_slots(const ctcd_decoder *dec);
  * unit) and as the call has pairs; if one slot does not fit the call returns CTCD_EUNSUPPORTED, the byte counts in ctcd_last_error,
  * and the decoder stays usable.  ctcd_last_edit_slots reports the slots of a call that launched the long kernel; any other ctcd_edit_distance or ctcd_edit_counts
  * leaves that value as it was.  The list takes 8 bytes per pair of the call.
- * ctcd_last_edit_long: the pairs the long kernel ran in the last ctcd_edit_distance or ctcd_edit_counts: 0 if that call did not
+ * ctcd_last_edit_long: the pairs the long kernel ran in the last ctcd_edit_distance, ctcd_edit_counts or ctcd_edit_align: 0 if that call did not
  * launch it (mode off, or min(L, Lq) <= 2048), -1: dec == NULL.  It reads one device word and waits for that call's stream.
- * Not provided: ctcd_edit_align beyond 2048, weighted costs, several workgroups on one pair. */
+ * ctcd_edit_align with the mode on and min(L, Lq) > 2048: the per-wave kernel fills every pair's maps with -1, aligns the pairs it can
+ * hold and lists the others as ctcd_edit_counts does; the long kernel's sweep of a listed pair keeps CHECKPOINTS of the key matrix --
+ * the right edge of every tile of 2048 columns, and every 1024th row -- and one wave then walks back from the ends block by block,
+ * sweeping the block of 1024 rows x 2048 columns it stands in again from its checkpoints with the canonical direction per cell.  The
+ * maps and counts are those of "Edit operations", no rule changes.  A long pair's slot, with tiles(n) = ceil(n / 2048):
+ * tiles(min(L, Lq)) x (max(L, Lq) + 1) x 8 bytes of column checkpoints, (max(L, Lq) / 1024) x tiles(min(L, Lq)) x 2048 x 8 bytes of row
+ * checkpoints and a block buffer of 512 KiB, rounded up to 256 -- 11.25 MB at 30000 x 30000, where two bits per cell are 225 MB.  The
+ * per-wave kernel's slot in such a call is min(max(L, Lq), 262144) x 512 bytes.  The two kinds of slot are used one after the other on
+ * the stream and share one allocation of the larger need; each is held to ctcd_set_edit_scratch's budget, and a single slot of either
+ * kind that does not fit is CTCD_EUNSUPPORTED with its byte count.  ctcd_last_edit_long and ctcd_last_edit_slots report for such a
+ * call as for ctcd_edit_counts.
+ * Not provided: alignments in pairwise mode, weighted costs, several workgroups on one pair. */
 int ctcd_set_edit_long(ctcd_decoder *dec, int waves);   /* 0 = off (the default), 2, 4, 8, 16 */
 long long ctcd_last_edit_long(ctcd_decoder *dec);
 
