@@ -943,6 +943,62 @@ class CTCBeamDecoder(object):
         outs = self.greedy_decode_device(probs, seq_lens)
         return tuple(o.cpu() for o in outs) if outs[0].numel() == 0 else tuple(_to_host(outs))
 
+    def find_keywords(self, probs, seq_lens, keywords, keyword_lens, details=False):
+        """Keyword search on the device (include/ctcdecode_amd.h "Keyword search"): for every keyword ``keywords[q, :keyword_lens[q]]`` and
+        every item, the window of the rows ``probs[b, :seq_lens[b]]`` in which the keyword's best path scores highest against the best
+        unconstrained path over the same frames.  Returns ``(scores [B, Q] float32, starts [B, Q] int32, ends [B, Q] int32)``: the
+        score is at most 0, and exactly 0 where the keyword is part of the item's greedy transcript; ``starts`` / ``ends`` are the
+        window's first and last frame (inclusive), both -1 where no window fits (score ``-inf``).  With ``details=True`` two traces
+        follow, ``end_scores`` float32 and ``end_starts`` int32 [B, Q, T]: the best score of a window that ends at each frame and where
+        it starts, 0 at or beyond an item's length -- threshold them to find every occurrence.
+
+        ``keywords`` int32 [Q, Lk] / ``keyword_lens`` int32 [Q]: one list serves every item of the batch.  CPU or device tensors; the
+        results are on the device when ``keywords`` is, otherwise CPU.  Follows the decoder's ``blank_id`` and input mode; half dtypes
+        on the device are read as they are.  No language model, no vocabulary prune and no ``blank_skip`` take part.  Raises
+        ``ValueError`` for a keyword with a label outside the vocabulary, a blank label or a length outside [1, Lk], and
+        ``NotImplementedError`` for ``Lk > 64``."""
+        if probs.dim() != 3:
+            raise ValueError("probs must be [batch, time, labels]")
+        if keywords.dim() != 2 or keyword_lens.dim() != 1 or keyword_lens.shape[0] != keywords.shape[0]:
+            raise ValueError("keywords must be [keywords, labels] and keyword_lens [keywords]")
+        Q, Lk = int(keywords.shape[0]), int(keywords.shape[1])
+        if Lk > 64:
+            raise NotImplementedError("ctcdecode_amd: find_keywords: keywords of more than 64 labels are not built")
+        on_device = keywords.is_cuda
+        probs = _input_rows(self, probs)
+        B, T, V = probs.shape
+        if V != self._num_labels:
+            raise ValueError("probs.shape[2] (%d) does not match the number of labels (%d)" % (V, self._num_labels))
+        if not 0 <= int(self._blank_id) < V:
+            raise ValueError("ctcdecode_amd: blank_id must index the vocabulary")
+        if seq_lens is not None:
+            seq_lens = seq_lens.to(device=self._device, dtype=torch.int32).contiguous()
+            if seq_lens.numel() != B:
+                raise ValueError("seq_lens must have one entry per batch item")
+        kws = keywords.to(device=self._device, dtype=torch.int32).contiguous()
+        lens = keyword_lens.to(device=self._device, dtype=torch.int32).contiguous()
+        with torch.cuda.device(self._device):
+            outs = [torch.empty((B, Q), dtype=dt, device=self._device) for dt in (torch.float32, torch.int32, torch.int32)]
+            if details:
+                outs += [torch.empty((B, Q, T), dtype=dt, device=self._device) for dt in (torch.float32, torch.int32)]
+            status = torch.zeros((max(Q, 1),), dtype=torch.int32, device=self._device)
+            stream = torch.cuda.current_stream(self._device).cuda_stream
+            ptrs = [o.data_ptr() for o in outs] + ([] if details else [None, None])
+            _native.check(_native.lib.ctcd_ctc_keywords(self._handle, probs.data_ptr(), seq_lens.data_ptr() if seq_lens is not None else None, B, T, V,
+                                                        int(self._blank_id), self._log_probs, kws.data_ptr(), lens.data_ptr(), Q, Lk, *ptrs,
+                                                        status.data_ptr(), stream))
+            bad = torch.nonzero(status[:Q]).flatten().tolist() if B and Q else []
+        if bad:
+            raise ValueError("ctcdecode_amd: find_keywords: keywords %s have a label outside the vocabulary, a blank label or a length outside "
+                             "[1, %d] (CTCD_ALIGN_BAD_ROW)" % (bad[:8], Lk))
+        return tuple(outs) if on_device else tuple(o.cpu() for o in outs)
+
+    def last_keyword_kernel(self):
+        """Test hook (include/ctcdecode_amd.h ctcd_last_keyword_kernel): ``(dtype, probabilities?, staged?, lane-group width)`` of the
+        kernel the last ``find_keywords`` launched; None before the first."""
+        code = int(_native.lib.ctcd_last_keyword_kernel(self._handle))
+        return None if code < 0 else ((code >> 8) & 3, bool(code >> 8 & 4), bool(code >> 8 & 8), code & 255)
+
     def edit_distance(self, beam_results, out_lens, references=None, ref_lens=None):
         """Levenshtein distances on the device (include/ctcdecode_amd.h "Edit distance"): ``D[b, i, j]``, int32 [B, R, Q], is the least
         number of insertions, deletions and substitutions that turn ``beam_results[b, i, :out_lens[b, i]]`` into

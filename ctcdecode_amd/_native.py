@@ -41,7 +41,8 @@ SYMBOLS = ["ctcd_log_softmax", "ctcd_compact_label_capacity", "ctcd_beam_decode_
            "ctcd_greedy_stream_create", "ctcd_greedy_stream_destroy", "ctcd_greedy_stream_reset", "ctcd_greedy_stream_decode", "ctcd_greedy_stream_info",
            "ctcd_edit_distance", "ctcd_last_edit_pairs", "ctcd_set_edit_grid", "ctcd_last_edit_grid",
            "ctcd_edit_counts", "ctcd_edit_align", "ctcd_set_edit_scratch", "ctcd_last_edit_slots",
-           "ctcd_set_edit_long", "ctcd_last_edit_long"]
+           "ctcd_set_edit_long", "ctcd_last_edit_long",
+           "ctcd_ctc_keywords", "ctcd_last_keyword_kernel"]
 
 
 def _load():
@@ -231,6 +232,10 @@ def _load():
     lib.ctcd_set_edit_long.argtypes = [ctypes.c_void_p, ctypes.c_int]
     lib.ctcd_last_edit_long.argtypes = [ctypes.c_void_p]
     lib.ctcd_last_edit_long.restype = ctypes.c_longlong
+    # keyword search (keyword.hip): dec, probs, seq_lens, B, T, V, blank_id, log_input, keywords, keyword_lens, Q, L_stride, out_scores,
+    # out_starts, out_ends, out_end_scores, out_end_starts, status, stream
+    lib.ctcd_ctc_keywords.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_int] * 5 + [ctypes.c_void_p] * 2 + [ctypes.c_int] * 2 + [ctypes.c_void_p] * 7
+    lib.ctcd_last_keyword_kernel.argtypes = [ctypes.c_void_p]
     return lib
 
 

@@ -44,6 +44,7 @@
 #include "loglik.h"
 #include "posterior.h"
 #include "greedy.h"
+#include "keyword.h"
 #include "editdist.h"
 #include "editops.h"
 #include "editlong.h"
@@ -381,6 +382,8 @@ struct ctcd_decoder {
   long long po_budget = 0, po_grid = 0;
   // ctcd_greedy_decode (greedy.h): the frame records its argmax pass leaves its collapse pass
   Buf gr_frames;
+  // ctcd_ctc_keywords (keyword.h): the kernel its last call launched (ctcd_last_keyword_kernel; -1: none yet).  Its m(t) are gr_frames.
+  int kw_kernel = -1;
   // ctcd_edit_distance (editdist.h): the pairs its last call ran (ctcd_last_edit_pairs)
   long long ed_pairs = 0;
   // ... the cap of its grid (ctcd_set_edit_grid; 0 = the default) and the workgroups of its last launch (ctcd_last_edit_grid)
@@ -479,6 +482,11 @@ int post_scratch(ctcd_decoder *d, size_t bytes, void **p) {
 }
 void post_note_grid(ctcd_decoder *d, long long grid) { d->po_grid = grid; }
 }  // namespace ctcpost
+
+// ... and the keyword search's (keyword.hip), beyond the alignment's and the greedy decode's hooks: the kernel of its last call
+namespace ctckw {
+void keyword_note_kernel(ctcd_decoder *d, int code) { d->kw_kernel = code; }
+}  // namespace ctckw
 
 // ... and the edit distance's (editdist.hip): the decoder's device and compute units, and the count of its last call's pairs
 namespace ctcedit {
@@ -886,6 +894,8 @@ long long ctcd_last_edit_long(ctcd_decoder *d) {
   if (e != hipSuccess) return fail(CTCD_EHIP, std::string("ctcd_last_edit_long: ") + hipGetErrorString(e));
   return (long long)n;
 }
+
+int ctcd_last_keyword_kernel(const ctcd_decoder *d) { return d ? d->kw_kernel : -1; }
 
 int ctcd_set_cu_sharing(ctcd_decoder *d, int mode) {
   if (!d || mode < -1 || mode > 1) return fail(CTCD_EINVAL, "cu sharing mode must be -1 (automatic), 0 or 1");

@@ -972,6 +972,61 @@ long long ctcd_last_edit_slots(const ctcd_decoder *dec);
 int ctcd_set_edit_long(ctcd_decoder *dec, int waves);   /* 0 = off (the default), 2, 4, 8, 16 */
 long long ctcd_last_edit_long(ctcd_decoder *dec);
 
+/* ---- Keyword search (no reference counterpart): does a word or phrase occur in an utterance, where, and how confidently -- the
+ * keyword-filler model.  For every keyword and every item: the window of frames in which the keyword's best path scores highest
+ * against the best unconstrained path over the same frames.  One list of keywords serves every item of the batch.
+ *
+ * Definition.  For item b: n = clamp(seq_lens[b], 0, T) (T when seq_lens is NULL).
+ * The rows:
+ *   lp(t, c) is the lp of "Forced alignment".  For log_input == 2 the call first runs the log-softmax pass (ctcd_log_softmax) into
+ *   decoder-owned float32 rows and then reads them as log_input == 1.
+ *   m(t) is lp(t, c*(t)) of "Greedy decode", taken on the rows the call reads.
+ *   r(t, c) is -inf where lp(t, c) == -inf, otherwise lp(t, c) - m(t): one float32 subtraction.
+ *   NaN and +inf inputs are undefined.  Nothing is read or written out of bounds because of one.
+ * The states:
+ *   Keyword k[0..L), 1 <= L <= 64, has S = 2L - 1 states: z[2i] = k[i], z[2i+1] = blank_id.  A state 2i >= 2 may be entered from
+ *   state 2i - 2 iff k[i] != k[i-1].  A cell is a pair (v, start).  Before frame 0 every cell is (-inf, -1).
+ * The cell update:
+ *   d[t][s] = (r(t, z[s]) + best.v, best.start), one float32 addition, where best is the greatest of the allowed candidates: stay
+ *   d[t-1][s]; d[t-1][s-1]; d[t-1][s-2] where the entry rule allows it; for s == 0 also the entry (0.0f, t) -- the filler path, whose
+ *   relative score is 0.  Among equal values the order is stay, before s - 1, before s - 2, before the entry: a strict `>` in that
+ *   order, as "Forced alignment" compares.
+ * The result:
+ *   Walk t = 0 .. n-1 with `>=` from (-inf, -1, -1): the LATEST frame that attains the maximum of d[t][S-1].v wins.  score is that
+ *   value, end that frame, start that cell's start.  If the score is -inf (n == 0, a keyword that needs more frames than the item
+ *   has, labels the rows rule out), start = end = -1.
+ * The traces (out_end_scores, out_end_starts, both or neither):
+ *   end_scores[b][q][t] = d[t][S-1].v and end_starts[b][q][t] = d[t][S-1].start for t < n; every other position is 0.  A caller
+ *   thresholds them to find every occurrence.
+ * An invalid keyword -- a length outside [1, L_stride], a label outside [0, V) or equal to blank_id -- is checked before its first
+ *   frame: score 0, start = end = -1, traces 0, and status[q] is raised to CTCD_ALIGN_BAD_ROW's value (8); the caller zeroes status.
+ * What follows:
+ *   On rows without +inf the score is at most 0: every r is at most 0, the entry is 0, and float32 addition is monotone.
+ *   A keyword that equals labels i .. j of the item's greedy transcript scores exactly 0.0f, with start = greedy's starts[i] and
+ *   end = greedy's ends[j] (of the latest such run, should the labels recur): on the greedy path every r is 0, a path that is 0 already keeps its earlier start against the entry, and
+ *   the frame behind ends[j] carries another label, so its r is below 0 wherever the frame's greatest value is attained once.
+ *   score, start and end do not depend on Q, on the other keywords, on the lane-group width or on the staging route.
+ *
+ * ctcd_ctc_keywords: everything is device memory and asynchronous on `stream`; nothing is read on the host.  probs [B][T][V] has the
+ * dtype ctcd_set_input_dtype set.  keywords int32 [Q][L_stride], keyword_lens int32 [Q].  out_scores float, out_starts and out_ends
+ * int32, each [B][Q]; out_end_scores float and out_end_starts int32, each [B][Q][T], or NULL both; status int32 [Q] or NULL.  Two
+ * kernels run behind each other: ctcd_greedy_decode's argmax pass into the decoder's frame records, and the keyword kernel -- a
+ * workgroup per item and block of keywords, a keyword on a lane group of 8, 16, 32 or 64 lanes (the least that holds L_stride), the
+ * rows staged through LDS for V <= 128 and gathered per lane beyond.  The frame records belong to this call until it finishes, as
+ * they belong to the decoder's next greedy call: queue such a call on the same stream, or wait.
+ * ctcd_last_keyword_kernel (test hook): the kernel the last ctcd_ctc_keywords launched, ((dtype | 4 * (log_input == 0) | 8 * staged)
+ * << 8) | lane-group width; -1: none yet, or dec == NULL.
+ * CTCD_EINVAL for bad shapes (negative sizes, V < 1, blank_id outside [0, V), log_input outside 0 .. 2, a NULL tensor, one trace
+ * without the other), and nothing is launched.  CTCD_EUNSUPPORTED for L_stride > 64, V > 2^28 or more than 65535 blocks of keywords.
+ * B == 0 or Q == 0 is CTCD_OK and launches nothing.
+ * Not provided: keywords beyond 64 labels, live streams, several workgroups on one item's frames, non-maximum suppression of
+ * several occurrences (the traces are the hook for that), a scorer, a vocabulary prune, the blank-frame filter. */
+int ctcd_ctc_keywords(ctcd_decoder *dec, const void *probs, const int32_t *seq_lens, int B, int T, int V, int blank_id, int log_input,
+                      const int32_t *keywords /* [Q][L_stride] */, const int32_t *keyword_lens /* [Q] */, int Q, int L_stride,
+                      float *out_scores, int32_t *out_starts, int32_t *out_ends /* [B][Q] */, float *out_end_scores,
+                      int32_t *out_end_starts /* [B][Q][T] or NULL */, int32_t *status /* [Q] or NULL */, void *stream);
+int ctcd_last_keyword_kernel(const ctcd_decoder *dec);
+
 /* Tuning / introspection. */
 int ctcd_set_threads(ctcd_decoder *dec, int threads_per_workgroup); /* 0 = automatic (default); else a power of two in [64, 1024] */
 /* Two workgroups per CU.  The fixed-layout class (beam <= 128, <= 32 labels) has a second build of its kernel that fits
