@@ -15,7 +15,7 @@ import torch
 from . import _native
 from ._native import NativeError  # noqa: F401
 
-__all__ = ["CTCBeamDecoder", "OnlineCTCBeamDecoder", "DecoderState", "GreedyState", "NativeError", "CallbackScorer", "KenlmScorer", "DecodePipeline", "snapshot_info"]
+__all__ = ["CTCBeamDecoder", "OnlineCTCBeamDecoder", "DecoderState", "GreedyState", "KeywordState", "NativeError", "CallbackScorer", "KenlmScorer", "DecodePipeline", "snapshot_info"]
 HAVE_LM = True  # the external-scorer tier (model_path / alpha / beta) is part of this build
 
 
@@ -1762,6 +1762,71 @@ class OnlineCTCBeamDecoder(object):
         outs = self.greedy_decode_device(probs, states, is_eos_s, seq_lens, details)
         return tuple(o.cpu() for o in outs) if any(o.numel() == 0 for o in outs) else tuple(_to_host(outs))
 
+    def find_keywords(self, probs, states, is_eos_s, seq_lens=None, details=False):
+        """Keyword search of live streams on the device (extension; include/ctcdecode_amd.h "Keyword search of live streams"): feeds the
+        chunk ``probs[b, :seq_lens[b]]`` to the ``KeywordState`` ``states[b]`` and returns, for every keyword of the stream's own list,
+        the best window over ALL frames the stream was fed so far -- ``(scores [B, Q] float32, starts [B, Q] int32, ends [B, Q] int32)``,
+        what ``CTCBeamDecoder.find_keywords`` returns for the concatenation, bit for bit and however the frames are cut, with frame
+        numbers counted from the stream's ``first_frame``.  A chunk costs its own frames, not the stream's age.
+
+        With ``details=True`` five more tensors follow: ``end_scores`` float32 / ``end_starts`` int32 [B, Q, Tc], the one-shot traces
+        at this chunk's frames (0 at or beyond a chunk's length), and ``chunk_scores`` / ``chunk_starts`` / ``chunk_ends`` [B, Q], the
+        best occurrence that ENDS in this chunk (``-inf``, -1, -1 if none does) -- what a live spotter thresholds.
+
+        All tensors are in HBM on the decoder's device, asynchronous on the current stream.  The states of one call share the shape of
+        their keyword lists (Q, Lk); the lists may differ.  ``is_eos_s[b]`` ends stream ``b`` with this chunk (an empty chunk too); an
+        ended state raises ``ValueError`` until it is ``reset()``.  Follows the decoder's ``blank_id`` and input mode; half dtypes on
+        the device are read as they are.  No ``blank_skip`` takes part and there is no ``save`` / ``restore``.  Raises ``ValueError``,
+        after the outputs are written, for keywords with a label outside the vocabulary, a blank label or a length outside [1, Lk]."""
+        if probs.dim() != 3:
+            raise ValueError("probs must be [batch, time, labels]")
+        probs = _input_rows(self, probs)
+        B, T, V = probs.shape
+        if V != self._num_labels:
+            raise ValueError("probs.shape[2] (%d) does not match the number of labels (%d)" % (V, self._num_labels))
+        if not 0 <= int(self._blank_id) < V:
+            raise ValueError("ctcdecode_amd: blank_id must index the vocabulary")
+        if len(states) != B or len(is_eos_s) != B:
+            raise ValueError("states and is_eos_s need one entry per batch item")
+        for st in states:
+            if not isinstance(st, KeywordState):
+                raise ValueError("find_keywords takes KeywordState objects")
+            if st._decoder is not self:
+                raise ValueError("a KeywordState is fed through the decoder it was created with")
+        Q = states[0]._Q if B else 0
+        if seq_lens is not None:
+            seq_lens = seq_lens.to(device=self._device, dtype=torch.int32).contiguous()
+            if seq_lens.numel() != B:
+                raise ValueError("seq_lens must have one entry per batch item")
+        ptrs = (ctypes.c_void_p * max(B, 1))(*[st._handle.value for st in states])
+        eos = (ctypes.c_ubyte * max(B, 1)).from_buffer_copy(bytes(bytearray(1 if e else 0 for e in is_eos_s)) or b"\0")
+        with torch.cuda.device(self._device):
+            outs = [torch.empty((B, Q), dtype=dt, device=self._device) for dt in (torch.float32, torch.int32, torch.int32)]
+            if details:
+                outs += [torch.empty((B, Q, T), dtype=dt, device=self._device) for dt in (torch.float32, torch.int32)]
+                outs += [torch.empty((B, Q), dtype=dt, device=self._device) for dt in (torch.float32, torch.int32, torch.int32)]
+            stream = torch.cuda.current_stream(self._device).cuda_stream
+            optr = [o.data_ptr() if o.numel() else None for o in outs] + ([] if details else [None] * 5)
+            # (no status tensor: a stream's list is fixed, so KeywordState has told its invalid keywords apart on the host already,
+            #  by the device's rule, and a chunk call reads nothing back)
+            _native.check(_native.lib.ctcd_keyword_stream_find(self._handle, ptrs, eos, probs.data_ptr() if probs.numel() else None,
+                                                               seq_lens.data_ptr() if seq_lens is not None else None, B, T, V, int(self._blank_id),
+                                                               self._log_probs, *optr, None, stream))
+            for st, e in zip(states, is_eos_s):
+                if e:
+                    st._ended = True
+        bad = [(b, q) for b, st in enumerate(states) for q in st._bad]
+        if bad:
+            raise ValueError("ctcdecode_amd: find_keywords: (stream, keyword) %s have a label outside the vocabulary, a blank label or a length "
+                             "outside [1, Lk] (CTCD_ALIGN_BAD_ROW)" % (bad[:8],))
+        return tuple(outs)
+
+    def last_keyword_kernel(self):
+        """Test hook (include/ctcdecode_amd.h ctcd_last_keyword_kernel): ``(dtype, probabilities?, staged?, lane-group width)`` of the
+        stream kernel the last ``find_keywords`` launched; None before the first."""
+        code = int(_native.lib.ctcd_last_keyword_kernel(self._handle))
+        return None if code < 0 or not code >> 16 & 1 else ((code >> 8) & 3, bool(code >> 8 & 4), bool(code >> 8 & 8), code & 255)
+
     def peek(self, states, n_best=1, since=None):
         """Interim results of live streams (extension; the reference reports nothing before ``is_eos``): what the streams' one-shot
         decode of the frames fed so far returns, without feeding a frame and without disturbing the streams.
@@ -2095,6 +2160,62 @@ class GreedyState(object):
         if h is not None and h.value and d is not None and getattr(d, "_handle", None) is not None:
             try:
                 _native.destroy(_native.lib.ctcd_greedy_stream_destroy, d._handle, h)
+            except Exception:
+                pass
+            self._handle = None
+
+
+class KeywordState(object):
+    """State of one audio stream under keyword search (extension; ``OnlineCTCBeamDecoder.find_keywords``): the stream's own list of
+    keywords -- ``keywords`` int32 [Q, Lk], ``keyword_lens`` int32 [Q], Q >= 1, 1 <= Lk <= 64, copied to the decoder's device -- and,
+    per keyword, its ``2L - 1`` cells and its best hit so far: 16 bytes per label and keyword.  ``first_frame``: the number of the
+    stream's first frame (``starts`` and ``ends`` count from it); a stream's frame numbers stay below 2**31 - 1
+    (``NotImplementedError`` from the call that would pass it).  Not reusable after its stream ended, until ``reset()``."""
+
+    def __init__(self, decoder, keywords, keyword_lens, first_frame=0):
+        if keywords.dim() != 2 or keyword_lens.dim() != 1 or keyword_lens.shape[0] != keywords.shape[0]:
+            raise ValueError("keywords must be [keywords, labels] and keyword_lens [keywords]")
+        if int(keywords.shape[1]) > 64:
+            raise NotImplementedError("ctcdecode_amd: KeywordState: keywords of more than 64 labels are not built")
+        self._decoder = decoder
+        self._device = decoder._device
+        self._ended = False
+        kws = keywords.to(device="cpu", dtype=torch.int32).contiguous()
+        lens = keyword_lens.to(device="cpu", dtype=torch.int32).contiguous()
+        self._Q, self._Lk = int(kws.shape[0]), int(kws.shape[1])
+        # the keywords every call reports as invalid (include/ctcdecode_amd.h "Keyword search": the device applies the same rule)
+        inside = torch.arange(self._Lk)[None, :] < lens[:, None]
+        wrong = inside & ((kws < 0) | (kws >= decoder._num_labels) | (kws == int(decoder._blank_id)))
+        self._bad = torch.nonzero((lens < 1) | (lens > self._Lk) | wrong.any(1)).flatten().tolist()
+        h = ctypes.c_void_p()
+        _native.check(_native.lib.ctcd_keyword_stream_create(decoder._handle, ctypes.byref(h), kws.data_ptr(), lens.data_ptr(), self._Q, self._Lk,
+                                                             int(first_frame)))
+        self._handle = h
+
+    def reset(self, first_frame=0):
+        """A fresh stream with the same keywords (queued on the current stream of the state's device)."""
+        with torch.cuda.device(self._device):
+            stream = torch.cuda.current_stream(self._device).cuda_stream
+            _native.check(_native.lib.ctcd_keyword_stream_reset(self._decoder._handle, self._handle, int(first_frame), stream))
+        self._ended = False
+
+    @property
+    def ended(self):
+        """True once a call has fed the stream with ``is_eos`` set."""
+        return self._ended
+
+    def info(self):
+        """Waits for the device: ``dict(frames, keywords, labels, ended)`` -- frames fed, Q, Lk, and whether the stream has ended."""
+        out = (ctypes.c_longlong * 4)()
+        _native.check(_native.lib.ctcd_keyword_stream_info(self._decoder._handle, self._handle, out))
+        return dict(frames=int(out[0]), keywords=int(out[1]), labels=int(out[2]), ended=bool(out[3]))
+
+    def __del__(self):
+        h = getattr(self, "_handle", None)
+        d = getattr(self, "_decoder", None)
+        if h is not None and h.value and d is not None and getattr(d, "_handle", None) is not None:
+            try:
+                _native.destroy(_native.lib.ctcd_keyword_stream_destroy, d._handle, h)
             except Exception:
                 pass
             self._handle = None

@@ -1019,13 +1019,67 @@ long long ctcd_last_edit_long(ctcd_decoder *dec);
  * CTCD_EINVAL for bad shapes (negative sizes, V < 1, blank_id outside [0, V), log_input outside 0 .. 2, a NULL tensor, one trace
  * without the other), and nothing is launched.  CTCD_EUNSUPPORTED for L_stride > 64, V > 2^28 or more than 65535 blocks of keywords.
  * B == 0 or Q == 0 is CTCD_OK and launches nothing.
- * Not provided: keywords beyond 64 labels, live streams, several workgroups on one item's frames, non-maximum suppression of
+ * Not provided: keywords beyond 64 labels, several workgroups on one item's frames, non-maximum suppression of
  * several occurrences (the traces are the hook for that), a scorer, a vocabulary prune, the blank-frame filter. */
 int ctcd_ctc_keywords(ctcd_decoder *dec, const void *probs, const int32_t *seq_lens, int B, int T, int V, int blank_id, int log_input,
                       const int32_t *keywords /* [Q][L_stride] */, const int32_t *keyword_lens /* [Q] */, int Q, int L_stride,
                       float *out_scores, int32_t *out_starts, int32_t *out_ends /* [B][Q] */, float *out_end_scores,
                       int32_t *out_end_starts /* [B][Q][T] or NULL */, int32_t *status /* [Q] or NULL */, void *stream);
 int ctcd_last_keyword_kernel(const ctcd_decoder *dec);
+
+/* ---- Keyword search of live streams: "Keyword search" for a stream that arrives chunk by chunk -- a wake word, a command, a watch
+ * list over a call in progress.  A chunk call costs O(chunk), not O(frames so far): a cell of "Keyword search" is (value, start) and
+ * nothing is traced back, so what a keyword carries between calls is its 2L - 1 cells and its best hit so far.
+ *
+ * A keyword stream is created with a list of keywords [Q][L_stride] and keyword_lens [Q] (host memory; copied to the device and owned
+ * by the stream; Q >= 1, 1 <= L_stride <= 64) and a first frame number F0, 0 <= F0 <= 2^31 - 1.  A call feeds stream b the chunk
+ * probs[b, :n_b], n_b = clamp(seq_lens[b], 0, Tc) (Tc when seq_lens is NULL), and carries a host flag is_eos[b].
+ * Definition.  X: all frames the stream was fed so far, this chunk included; N: their count before the call.  For stream b, keyword q:
+ *   scores, starts, ends [B][Q]: what "Keyword search" defines for X as one item of N + n_b frames, every frame number shifted by F0
+ *   (the entry (0.0f, t), the end frame and the cells' starts use the shifted number; a -1 stays -1).  It is the running best, valid
+ *   after every call and not only at the end.
+ *   With traces: end_scores, end_starts [B][Q][Tc]: positions 0 .. n_b hold the traces of X at frames N .. N + n_b, starts shifted by
+ *   F0; positions from n_b on are 0.
+ *   With traces also: chunk_scores, chunk_starts, chunk_ends [B][Q]: the `>=` walk of "Keyword search" from (-inf, -1, -1) over THIS
+ *   chunk's frames only -- the best occurrence that ends in this chunk, which a live spotter thresholds without reading Tc columns;
+ *   (-inf, -1, -1) when n_b == 0 or nothing ends in the chunk.
+ *   An invalid keyword (the rule of "Keyword search", against the stream's own list) is reported on every call: score 0, start = end =
+ *   -1, traces 0, chunk result (0, -1, -1), status[b][q] raised to 8.  status is [B][Q] here -- lists differ per stream -- or NULL.
+ * What follows:
+ *   However X is cut into chunks, the last call's scores / starts / ends are ctcd_ctc_keywords' on X (shifted by F0), with equal bits:
+ *   m(t) is defined on the frame alone, every cell is one subtraction and one addition on carried float32 values, and nothing in the
+ *   definition looks at where a cut falls.  The traces of the calls, concatenated, are its traces.
+ *   A call with n_b == 0 returns the previous call's running result.
+ *
+ * ctcd_keyword_stream_create / _destroy: a stream, its record and its list on the decoder's device; the record is in place when create
+ * returns.  ctcd_keyword_stream_reset: a fresh stream with the same list, queued on `stream` (keyword_stream_init_kernel).
+ * ctcd_keyword_stream_find: states and is_eos are host arrays [B]; everything else is device memory and asynchronous on `stream`;
+ * nothing is read on the host.  probs [B][Tc][V] has the dtype ctcd_set_input_dtype set; the input modes are ctcd_ctc_keywords'.  The
+ * traces and the chunk results come together: all five tensors or none (the two traces may be NULL when Tc == 0).  One copy of the
+ * per-stream arguments, then for V <= 128 ONE kernel: it stages 32 frames at a time into LDS and finds every frame's m(t) there, 8
+ * lanes a frame, with the bits of ctcd_greedy_decode's argmax pass (the first index of the greatest value: equal maxima, -0.0 / +0.0
+ * and a frame of -inf included); for V > 128 that argmax pass runs in front, into the decoder's frame records, which then belong to
+ * this call as they belong to ctcd_ctc_keywords.  A keyword lies on a lane group of 8, 16, 32 or 64 lanes, which loads and stores its
+ * cells with one 16-byte access a lane.  Tc == 0 is a valid call (it may end streams).
+ * ctcd_last_keyword_kernel reports a stream call with bit 16 set over ctcd_ctc_keywords' code.
+ * ctcd_keyword_stream_info: waits for the device, then out = {frames fed (exact, unshifted), Q, L_stride, 1 if the stream has ended}.
+ * CTCD_EINVAL for bad shapes, a NULL state, a state of another device, a stream that has ended (until it is reset), the same stream
+ * twice in one call, or streams of one call that differ in Q or L_stride (their keywords may differ); CTCD_EUNSUPPORTED for
+ * L_stride > 64, V > 2^28, more than 65535 blocks of keywords, or F0 + the Tc of the stream's calls beyond 2^31 - 1.  Nothing is
+ * launched and no stream changes.  B == 0 is CTCD_OK.
+ * Not provided: keywords beyond 64 labels, save / restore of a keyword stream, the blank-frame filter, a scorer, non-maximum
+ * suppression, several workgroups on one stream's frames. */
+typedef struct ctcd_keyword_stream ctcd_keyword_stream;
+int ctcd_keyword_stream_create(ctcd_decoder *dec, ctcd_keyword_stream **out, const int32_t *keywords /* HOST [Q][L_stride] */,
+                               const int32_t *keyword_lens /* HOST [Q] */, int Q, int L_stride, long long first_frame);
+void ctcd_keyword_stream_destroy(ctcd_decoder *dec, ctcd_keyword_stream *st);
+int ctcd_keyword_stream_reset(ctcd_decoder *dec, ctcd_keyword_stream *st, long long first_frame, void *stream);
+int ctcd_keyword_stream_find(ctcd_decoder *dec, ctcd_keyword_stream **states, const unsigned char *is_eos /* HOST [B] */, const void *probs,
+                             const int32_t *seq_lens, int B, int Tc, int V, int blank_id, int log_input, float *out_scores, int32_t *out_starts,
+                             int32_t *out_ends /* [B][Q] */, float *out_end_scores, int32_t *out_end_starts /* [B][Q][Tc] or NULL */,
+                             float *out_chunk_scores, int32_t *out_chunk_starts, int32_t *out_chunk_ends /* [B][Q] or NULL */,
+                             int32_t *status /* [B][Q] zeroed by the caller, or NULL */, void *stream);
+int ctcd_keyword_stream_info(ctcd_decoder *dec, const ctcd_keyword_stream *st, long long out[4]); /* waits */
 
 /* Tuning / introspection. */
 int ctcd_set_threads(ctcd_decoder *dec, int threads_per_workgroup); /* 0 = automatic (default); else a power of two in [64, 1024] */
