@@ -395,6 +395,7 @@ class CTCBeamDecoder(object):
         # float32 log_softmax (include/ctcdecode_amd.h ctcd_log_softmax) before decoding
         self._log_probs = 2 if logits_input else (1 if log_probs_input else 0)
         self._cutoff_prob = cutoff_prob
+        self._long_keywords = False  # set_long_keywords
         if not torch.cuda.is_available():
             raise RuntimeError("ctcdecode_amd: no HIP device visible; this decoder has no CPU path")
         self._device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
@@ -956,14 +957,16 @@ class CTCBeamDecoder(object):
         results are on the device when ``keywords`` is, otherwise CPU.  Follows the decoder's ``blank_id`` and input mode; half dtypes
         on the device are read as they are.  No language model, no vocabulary prune and no ``blank_skip`` take part.  Raises
         ``ValueError`` for a keyword with a label outside the vocabulary, a blank label or a length outside [1, Lk], and
-        ``NotImplementedError`` for ``Lk > 64``."""
+        ``NotImplementedError`` for ``Lk > 64`` -- with ``set_long_keywords`` on for ``Lk > 2048``: a list of ``65 <= Lk <= 2048`` then
+        runs on the long keyword kernel (eight labels per lane, 1, 2 or 4 waves per keyword), with the same results."""
         if probs.dim() != 3:
             raise ValueError("probs must be [batch, time, labels]")
         if keywords.dim() != 2 or keyword_lens.dim() != 1 or keyword_lens.shape[0] != keywords.shape[0]:
             raise ValueError("keywords must be [keywords, labels] and keyword_lens [keywords]")
         Q, Lk = int(keywords.shape[0]), int(keywords.shape[1])
-        if Lk > 64:
-            raise NotImplementedError("ctcdecode_amd: find_keywords: keywords of more than 64 labels are not built")
+        if (Lk > 64 and not self._long_keywords) or Lk > 2048:
+            raise NotImplementedError("ctcdecode_amd: find_keywords: keywords of more than %d labels are not built%s"
+                                      % ((64, " (set_long_keywords() lifts the limit to 2048)") if Lk <= 2048 else (2048, "")))
         on_device = keywords.is_cuda
         probs = _input_rows(self, probs)
         B, T, V = probs.shape
@@ -993,9 +996,19 @@ class CTCBeamDecoder(object):
                              "[1, %d] (CTCD_ALIGN_BAD_ROW)" % (bad[:8], Lk))
         return tuple(outs) if on_device else tuple(o.cpu() for o in outs)
 
+    def set_long_keywords(self, on=True):
+        """Keywords of 65 .. 2048 labels for ``find_keywords`` (include/ctcdecode_amd.h ctcd_set_long_keywords): off by default.  On, a
+        keyword list of ``65 <= Lk <= 2048`` runs on the long keyword kernel; ``Lk <= 64`` takes the kernel it always took, and with the
+        setting off nothing changes.  Keyword streams (``KeywordState``) keep 64 labels.  ``on`` is True / False (or 1 / 0)."""
+        if on not in (0, 1):
+            raise ValueError("ctcdecode_amd: set_long_keywords: on must be True or False")
+        _native.check(_native.lib.ctcd_set_long_keywords(self._handle, int(on)))
+        self._long_keywords = bool(on)
+
     def last_keyword_kernel(self):
         """Test hook (include/ctcdecode_amd.h ctcd_last_keyword_kernel): ``(dtype, probabilities?, staged?, lane-group width)`` of the
-        kernel the last ``find_keywords`` launched; None before the first."""
+        kernel the last ``find_keywords`` launched -- the long keyword kernel reports 128 + its waves per keyword (129, 130, 132) as
+        the width; None before the first."""
         code = int(_native.lib.ctcd_last_keyword_kernel(self._handle))
         return None if code < 0 else ((code >> 8) & 3, bool(code >> 8 & 4), bool(code >> 8 & 8), code & 255)
 

@@ -42,7 +42,7 @@ SYMBOLS = ["ctcd_log_softmax", "ctcd_compact_label_capacity", "ctcd_beam_decode_
            "ctcd_edit_distance", "ctcd_last_edit_pairs", "ctcd_set_edit_grid", "ctcd_last_edit_grid",
            "ctcd_edit_counts", "ctcd_edit_align", "ctcd_set_edit_scratch", "ctcd_last_edit_slots",
            "ctcd_set_edit_long", "ctcd_last_edit_long",
-           "ctcd_ctc_keywords", "ctcd_last_keyword_kernel",
+           "ctcd_ctc_keywords", "ctcd_last_keyword_kernel", "ctcd_set_long_keywords",
            "ctcd_keyword_stream_create", "ctcd_keyword_stream_destroy", "ctcd_keyword_stream_reset", "ctcd_keyword_stream_find", "ctcd_keyword_stream_info"]
 
 
@@ -237,6 +237,7 @@ def _load():
     # out_starts, out_ends, out_end_scores, out_end_starts, status, stream
     lib.ctcd_ctc_keywords.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_int] * 5 + [ctypes.c_void_p] * 2 + [ctypes.c_int] * 2 + [ctypes.c_void_p] * 7
     lib.ctcd_last_keyword_kernel.argtypes = [ctypes.c_void_p]
+    lib.ctcd_set_long_keywords.argtypes = [ctypes.c_void_p, ctypes.c_int]
     # keyword search of live streams (keyword_stream.hip).  create: dec, out, keywords, keyword_lens (host), Q, L_stride, first_frame.
     # find: dec, states, is_eos, probs, seq_lens, B, Tc, V, blank_id, log_input, out_scores, out_starts, out_ends, out_end_scores,
     # out_end_starts, out_chunk_scores, out_chunk_starts, out_chunk_ends, status, stream

@@ -45,6 +45,7 @@
 #include "posterior.h"
 #include "greedy.h"
 #include "keyword.h"
+#include "keyword_long.h"
 #include "editdist.h"
 #include "editops.h"
 #include "editlong.h"
@@ -384,6 +385,8 @@ struct ctcd_decoder {
   Buf gr_frames;
   // ctcd_ctc_keywords (keyword.h): the kernel its last call launched (ctcd_last_keyword_kernel; -1: none yet).  Its m(t) are gr_frames.
   int kw_kernel = -1;
+  // ... and whether keywords of 65 .. 2048 labels run (keyword_long.h; ctcd_set_long_keywords, off by default)
+  bool kw_long = false;
   // ctcd_edit_distance (editdist.h): the pairs its last call ran (ctcd_last_edit_pairs)
   long long ed_pairs = 0;
   // ... the cap of its grid (ctcd_set_edit_grid; 0 = the default) and the workgroups of its last launch (ctcd_last_edit_grid)
@@ -486,6 +489,7 @@ void post_note_grid(ctcd_decoder *d, long long grid) { d->po_grid = grid; }
 // ... and the keyword search's (keyword.hip), beyond the alignment's and the greedy decode's hooks: the kernel of its last call
 namespace ctckw {
 void keyword_note_kernel(ctcd_decoder *d, int code) { d->kw_kernel = code; }
+bool keyword_long_on(const ctcd_decoder *d) { return d->kw_long; }
 }  // namespace ctckw
 
 // ... and the edit distance's (editdist.hip): the decoder's device and compute units, and the count of its last call's pairs
@@ -896,6 +900,11 @@ long long ctcd_last_edit_long(ctcd_decoder *d) {
 }
 
 int ctcd_last_keyword_kernel(const ctcd_decoder *d) { return d ? d->kw_kernel : -1; }
+int ctcd_set_long_keywords(ctcd_decoder *d, int on) {
+  if (!d || (on != 0 && on != 1)) return fail(CTCD_EINVAL, "ctcd_set_long_keywords: a decoder and on = 0 (off) or 1 required");
+  d->kw_long = on == 1;
+  return CTCD_OK;
+}
 
 int ctcd_set_cu_sharing(ctcd_decoder *d, int mode) {
   if (!d || mode < -1 || mode > 1) return fail(CTCD_EINVAL, "cu sharing mode must be -1 (automatic), 0 or 1");

@@ -14,6 +14,7 @@
 //     gathered (V > 128): a lane prefetches its own label's values of the next F frames into registers, F loads in flight; lane j of
 //             a wave loads frame j's blank value and m, and the frame's turn takes them by readlane.
 // Nothing is loaded from HBM on a frame's critical path.  Every store is a plain C++ store; there is no inline assembly.
+// With ctcd_set_long_keywords on, a call of 65 <= L_stride <= 2048 goes to keyword_long.hip's kernel behind the same argmax pass.
 #include <hip/hip_runtime.h>
 
 #include <string>
@@ -21,6 +22,7 @@
 #include "../../include/ctcdecode_amd.h"
 #include "device_guard.h"
 #include "keyword.h"
+#include "keyword_long.h"
 
 namespace ctckw {
 
@@ -257,9 +259,11 @@ int ctcd_ctc_keywords(ctcd_decoder *d, const void *probs, const int32_t *seq_len
   if (B == 0 || Q == 0) return CTCD_OK;
   if ((!keywords && L_stride > 0) || !keyword_lens || !out_scores || !out_starts || !out_ends || (T > 0 && !probs) || (!out_end_scores != !out_end_starts))
     return align_fail(CTCD_EINVAL, (f + "null tensor").c_str());
-  if (L_stride > kKwMaxLabels) return align_fail(CTCD_EUNSUPPORTED, (f + "keywords of more than 64 labels (L_stride > 64) are not built").c_str());
+  const bool long_kw = L_stride > kKwMaxLabels && keyword_long_on(d);  // (keyword_long.hip: ctcd_set_long_keywords)
+  if (L_stride > kKwMaxLabels && !long_kw) return align_fail(CTCD_EUNSUPPORTED, (f + "keywords of more than 64 labels (L_stride > 64) are not built").c_str());
+  if (L_stride > kKwLongMaxLabels) return align_fail(CTCD_EUNSUPPORTED, (f + "keywords of more than 2048 labels (L_stride > 2048) are not built").c_str());
   if (V > (1 << 28)) return align_fail(CTCD_EUNSUPPORTED, (f + "V > 2^28").c_str());
-  const int lg = lane_group_log2(L_stride), per_wg = kw_per_workgroup(lg);
+  const int lg = lane_group_log2(L_stride), per_wg = long_kw ? kwl_per_workgroup(kwl_waves(L_stride)) : kw_per_workgroup(lg);
   const long long blocks = ((long long)Q + per_wg - 1) / per_wg;
   if (blocks > 65535) return align_fail(CTCD_EUNSUPPORTED, (f + "too many keywords for one launch").c_str());
   ctcalign::AlignDecoderInfo inf;
@@ -285,6 +289,12 @@ int ctcd_ctc_keywords(ctcd_decoder *d, const void *probs, const int32_t *seq_len
   const dim3 grid((unsigned)B, (unsigned)blocks);
   const size_t lds = kw_lds_bytes(V);
   const int dt = dtype == CTCD_DTYPE_F16 ? kSkipF16 : (dtype == CTCD_DTYPE_BF16 ? kSkipBF16 : kSkipF32);
+  if (long_kw) {
+    keyword_note_kernel(d, launch_keyword_long(dt, prob, probs, seq_lens, B, T, V, blank_id, (const FrameRec *)rec, keywords, keyword_lens, Q, L_stride, out_scores,
+                                               out_starts, out_ends, out_end_scores, out_end_starts, status, stream));
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? CTCD_OK : align_fail(CTCD_EHIP, (std::string("long keyword search: ") + hipGetErrorString(e)).c_str());
+  }
   auto go = [&](auto tag) {
     launch_dt<decltype(tag)::value>(prob, staged, grid, lds, s, probs, seq_lens, T, V, blank_id, (const FrameRec *)rec, keywords, keyword_lens, Q, L_stride, lg,
                                     out_scores, out_starts, out_ends, out_end_scores, out_end_starts, status);

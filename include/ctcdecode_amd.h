@@ -984,7 +984,7 @@ long long ctcd_last_edit_long(ctcd_decoder *dec);
  *   r(t, c) is -inf where lp(t, c) == -inf, otherwise lp(t, c) - m(t): one float32 subtraction.
  *   NaN and +inf inputs are undefined.  Nothing is read or written out of bounds because of one.
  * The states:
- *   Keyword k[0..L), 1 <= L <= 64, has S = 2L - 1 states: z[2i] = k[i], z[2i+1] = blank_id.  A state 2i >= 2 may be entered from
+ *   Keyword k[0..L), 1 <= L <= 64 (2048 with ctcd_set_long_keywords on), has S = 2L - 1 states: z[2i] = k[i], z[2i+1] = blank_id.  A state 2i >= 2 may be entered from
  *   state 2i - 2 iff k[i] != k[i-1].  A cell is a pair (v, start).  Before frame 0 every cell is (-inf, -1).
  * The cell update:
  *   d[t][s] = (r(t, z[s]) + best.v, best.start), one float32 addition, where best is the greatest of the allowed candidates: stay
@@ -1014,18 +1014,31 @@ long long ctcd_last_edit_long(ctcd_decoder *dec);
  * workgroup per item and block of keywords, a keyword on a lane group of 8, 16, 32 or 64 lanes (the least that holds L_stride), the
  * rows staged through LDS for V <= 128 and gathered per lane beyond.  The frame records belong to this call until it finishes, as
  * they belong to the decoder's next greedy call: queue such a call on the same stream, or wait.
+ * ctcd_set_long_keywords(dec, on): on = 0 (the default) leaves everything above as it is, the refusal of L_stride > 64 included; on = 1
+ * lets ctcd_ctc_keywords accept 65 <= L_stride <= 2048 and run such a call on the long keyword kernel.  L_stride <= 64 takes the
+ * kernel above either way, with the same code from ctcd_last_keyword_kernel.  Any other value of `on`, or dec == NULL, is CTCD_EINVAL.
+ * The definition, the outputs, the traces, the status, the input modes and the element types are the same; so is the argmax pass in
+ * front.  The long kernel holds eight consecutive labels on a lane (16 cells in registers) and gives a keyword 1, 2 or 4 waves of
+ * the workgroup's four, by L_stride:
+ *   L_stride <=  512   1 wave  per keyword, 4 keywords per workgroup
+ *   L_stride <= 1024   2 waves per keyword, 2 keywords per workgroup
+ *   L_stride <= 2048   4 waves per keyword, 1 keyword  per workgroup
+ * The waves of a keyword walk the item's frames one step of frames behind each other and hand the boundary cells over through LDS,
+ * one workgroup barrier per step.  The rows are staged through LDS for V <= 128 and gathered per lane beyond, as above.
  * ctcd_last_keyword_kernel (test hook): the kernel the last ctcd_ctc_keywords launched, ((dtype | 4 * (log_input == 0) | 8 * staged)
- * << 8) | lane-group width; -1: none yet, or dec == NULL.
+ * << 8) | lane-group width; the long kernel reports 128 + its waves per keyword (129, 130, 132) in place of the width; -1: none yet,
+ * or dec == NULL.
  * CTCD_EINVAL for bad shapes (negative sizes, V < 1, blank_id outside [0, V), log_input outside 0 .. 2, a NULL tensor, one trace
- * without the other), and nothing is launched.  CTCD_EUNSUPPORTED for L_stride > 64, V > 2^28 or more than 65535 blocks of keywords.
- * B == 0 or Q == 0 is CTCD_OK and launches nothing.
- * Not provided: keywords beyond 64 labels, several workgroups on one item's frames, non-maximum suppression of
+ * without the other), and nothing is launched.  CTCD_EUNSUPPORTED for L_stride > 64 (> 2048 with ctcd_set_long_keywords on),
+ * V > 2^28 or more than 65535 blocks of keywords.  B == 0 or Q == 0 is CTCD_OK and launches nothing.
+ * Not provided: keywords beyond 2048 labels, long keywords on live streams, several workgroups on one item's frames, non-maximum suppression of
  * several occurrences (the traces are the hook for that), a scorer, a vocabulary prune, the blank-frame filter. */
 int ctcd_ctc_keywords(ctcd_decoder *dec, const void *probs, const int32_t *seq_lens, int B, int T, int V, int blank_id, int log_input,
                       const int32_t *keywords /* [Q][L_stride] */, const int32_t *keyword_lens /* [Q] */, int Q, int L_stride,
                       float *out_scores, int32_t *out_starts, int32_t *out_ends /* [B][Q] */, float *out_end_scores,
                       int32_t *out_end_starts /* [B][Q][T] or NULL */, int32_t *status /* [Q] or NULL */, void *stream);
 int ctcd_last_keyword_kernel(const ctcd_decoder *dec);
+int ctcd_set_long_keywords(ctcd_decoder *dec, int on); /* 0 = off (the default), 1 = on */
 
 /* ---- Keyword search of live streams: "Keyword search" for a stream that arrives chunk by chunk -- a wake word, a command, a watch
  * list over a call in progress.  A chunk call costs O(chunk), not O(frames so far): a cell of "Keyword search" is (value, start) and
