@@ -15,7 +15,7 @@ import torch
 from . import _native
 from ._native import NativeError  # noqa: F401
 
-__all__ = ["CTCBeamDecoder", "OnlineCTCBeamDecoder", "DecoderState", "GreedyState", "KeywordState", "NativeError", "CallbackScorer", "KenlmScorer", "DecodePipeline", "snapshot_info"]
+__all__ = ["CTCBeamDecoder", "OnlineCTCBeamDecoder", "DecoderState", "GreedyState", "KeywordState", "PrefixState", "NativeError", "CallbackScorer", "KenlmScorer", "DecodePipeline", "snapshot_info"]
 HAVE_LM = True  # the external-scorer tier (model_path / alpha / beta) is part of this build
 
 
@@ -297,6 +297,16 @@ def _last_kernel(handle):
 PREPASS_KERNELS = {1: "prob_to_log", 2: "widen", 3: "lsm_wave", 4: "lsm_wg", 5: "prune_rows", 6: "prune_wg", 7: "prune_logits", 8: "resolve"}
 PREPASS_STAGES = ("elementwise", "log_softmax", "prune", "resolve")
 DTYPE_NAMES = {DTYPE_F32: "f32", DTYPE_F16: "f16", DTYPE_BF16: "bf16"}
+
+
+class PrefixState(object):
+    """The prefixes of a label-synchronous decode between two steps (``CTCBeamDecoder.prefix_init`` / ``prefix_scores`` /
+    ``prefix_advance``; include/ctcdecode_amd.h "CTC prefix scores"), as device tensors: ``cols`` float32 [B, R, T, 2], the forward
+    values ``(r_n[t], r_b[t])`` of each prefix's last two lattice states (entries at or beyond an item's length are undefined);
+    ``last`` int32 [B, R], each prefix's last label (-1: none); ``lens`` int32 [B, R], its length (-1: an unused slot)."""
+
+    def __init__(self, cols, last, lens):
+        self.cols, self.last, self.lens = cols, last, lens
 
 
 def _last_prepass(handle):
@@ -867,6 +877,132 @@ class CTCBeamDecoder(object):
     def last_loglik_grid(self):
         """Test hook: the workgroups of the widest launch of the last ``log_likelihood``."""
         return int(_native.lib.ctcd_last_loglik_grid(self._handle))
+
+    def _prefix_rows(self, probs, seq_lens):
+        """What the three prefix operations share: the rows as the library reads them, and the lengths on the device."""
+        if probs.dim() != 3:
+            raise ValueError("probs must be [batch, time, labels]")
+        probs = _input_rows(self, probs)
+        B, T, V = probs.shape
+        if V != self._num_labels:
+            raise ValueError("probs.shape[2] (%d) does not match the number of labels (%d)" % (V, self._num_labels))
+        if not 0 <= int(self._blank_id) < V:
+            raise ValueError("ctcdecode_amd: blank_id must index the vocabulary")
+        if seq_lens is not None:
+            seq_lens = seq_lens.to(device=self._device, dtype=torch.int32).contiguous()
+            if seq_lens.numel() != B:
+                raise ValueError("seq_lens must have one entry per batch item")
+        return probs, seq_lens
+
+    def _prefix_state(self, state, B, T):
+        if not isinstance(state, PrefixState) or state.cols.dim() != 4 or tuple(state.cols.shape[::3]) != (B, 2) or state.cols.shape[2] != T:
+            raise ValueError("state must be a PrefixState of these rows (cols [batch, slots, time, 2])")
+        if tuple(state.last.shape) != tuple(state.cols.shape[:2]) or tuple(state.lens.shape) != tuple(state.cols.shape[:2]):
+            raise ValueError("state.last and state.lens must be [batch, slots]")
+        return PrefixState(state.cols.to(device=self._device, dtype=torch.float32).contiguous(),
+                           state.last.to(device=self._device, dtype=torch.int32).contiguous(), state.lens.to(device=self._device, dtype=torch.int32).contiguous())
+
+    def _prefix_status(self, name, status, B, own):
+        """``status`` as the entry point gets it: the caller's word per item (``own`` false: raised for an invalid entry, never read
+        here), or a zeroed one that ``_prefix_raise`` reads back after the call."""
+        if own:
+            return torch.zeros((max(B, 1),), dtype=torch.int32, device=self._device)
+        if status.dtype != torch.int32 or tuple(status.shape) != (B,) or not status.is_cuda or not status.is_contiguous():
+            raise ValueError("status must be a contiguous int32 [batch] tensor on the decoder's device")
+        return status
+
+    def _prefix_raise(self, name, status, B):
+        bad = torch.nonzero(status[:B]).flatten().tolist() if B else []
+        if bad:
+            raise ValueError("ctcdecode_amd: %s: items %s have a candidate, a label or a prefix's last label outside the vocabulary, or a parent "
+                             "that is no live slot (CTCD_ALIGN_BAD_ROW)" % (name, bad[:8]))
+
+    def prefix_init(self, probs, seq_lens, R=1):
+        """CTC prefix scoring on the device (include/ctcdecode_amd.h "CTC prefix scores"), for decoders that grow their hypotheses one
+        label per step -- joint CTC/attention decoding, LLM-driven decoding.  Returns the ``PrefixState`` of the empty prefix: ``R``
+        slots per item, slot 0 the empty prefix, the others unused.  Then, per step, ``prefix_scores`` asks what each candidate next
+        label would score and ``prefix_advance`` extends the chosen (slot, label) pairs into the next step's state.  The tensors stay
+        on the device; by default ``prefix_scores`` and ``prefix_advance`` read one status word per item back after the call (a
+        synchronisation per step) to raise ``ValueError`` -- pass ``status=`` to them to check it yourself, or never.
+
+        Follows the decoder's ``blank_id`` and input mode; half dtypes on the device are read as they are.  With ``logits_input`` every
+        call runs the log-softmax pass again: take ``log_softmax()`` once and use a ``log_probs_input=True`` decoder for the steps."""
+        probs, seq_lens = self._prefix_rows(probs, seq_lens)
+        B, T, V = probs.shape
+        if int(R) < 1:
+            raise ValueError("R must be at least 1")
+        with torch.cuda.device(self._device):
+            st = PrefixState(torch.empty((B, int(R), T, 2), dtype=torch.float32, device=self._device),
+                             torch.empty((B, int(R)), dtype=torch.int32, device=self._device), torch.empty((B, int(R)), dtype=torch.int32, device=self._device))
+            stream = torch.cuda.current_stream(self._device).cuda_stream
+            _native.check(_native.lib.ctcd_ctc_prefix_init(self._handle, probs.data_ptr(), seq_lens.data_ptr() if seq_lens is not None else None, B, T, V,
+                                                           int(self._blank_id), self._log_probs, int(R), st.cols.data_ptr(), st.last.data_ptr(), st.lens.data_ptr(), stream))
+        return st
+
+    def prefix_scores(self, probs, seq_lens, state, candidates=None, status=None):
+        """For every prefix ``g`` of ``state`` and every candidate ``c``: ``scores[b, r, k]`` = the log of the CTC probability that the
+        transcript of item ``b`` starts with ``g . c`` (the CTC prefix score), and ``eos[b, r]`` = the log-probability that it is
+        ``g`` -- bit for bit ``log_likelihood`` of ``g``.  Returns ``(scores, eos)``, float32 [B, R, C] and [B, R], on the device.
+
+        ``candidates``: int32 [B, R, C], a list per prefix (``-1`` entries score ``-inf``), or ``None`` for every label: ``C = V`` and
+        the blank's column is ``-inf``.  Unused slots score ``-inf`` throughout.  ``exp(psi(g)) = exp(eos(g)) + sum_c exp(psi(g . c))``
+        over all labels, up to float32 rounding.  Raises ``ValueError`` for a candidate outside ``[-1, V)`` or a prefix whose last label
+        is not in the vocabulary (such an entry scores ``-inf``) -- which reads the status words back, so the call waits for the
+        device.  With ``status``, an int32 [B] device tensor the caller has zeroed, nothing is read and nothing raised: the item's word
+        is set to 8 (CTCD_ALIGN_BAD_ROW) instead, for the caller to look at when it suits."""
+        probs, seq_lens = self._prefix_rows(probs, seq_lens)
+        B, T, V = probs.shape
+        st = self._prefix_state(state, B, T)
+        R = int(st.cols.shape[1])
+        if candidates is not None:
+            if candidates.dim() != 3 or tuple(candidates.shape[:2]) != (B, R):
+                raise ValueError("candidates must be [batch, slots, candidates]")
+            candidates = candidates.to(device=self._device, dtype=torch.int32).contiguous()
+        C = V if candidates is None else int(candidates.shape[2])
+        with torch.cuda.device(self._device):
+            scores = torch.empty((B, R, C), dtype=torch.float32, device=self._device)
+            eos = torch.empty((B, R), dtype=torch.float32, device=self._device)
+            own, status = status is None, self._prefix_status("prefix_scores", status, B, status is None)
+            stream = torch.cuda.current_stream(self._device).cuda_stream
+            _native.check(_native.lib.ctcd_ctc_prefix_scores(self._handle, probs.data_ptr(), seq_lens.data_ptr() if seq_lens is not None else None, B, T, V,
+                                                             int(self._blank_id), self._log_probs, st.cols.data_ptr(), st.last.data_ptr(), st.lens.data_ptr(), R,
+                                                             candidates.data_ptr() if candidates is not None else None, C, scores.data_ptr(), eos.data_ptr(),
+                                                             status.data_ptr(), stream))
+            if own:
+                self._prefix_raise("prefix_scores", status, B)
+        return scores, eos
+
+    def prefix_advance(self, probs, seq_lens, state, parents, labels, status=None):
+        """The next step's ``PrefixState``: slot ``j`` of item ``b`` is the prefix in slot ``parents[b, j]`` of ``state`` extended by
+        ``labels[b, j]``.  ``parents`` / ``labels``: int32 [B, R'] -- parents may repeat and come in any order, ``-1`` leaves the slot
+        unused, and R' may differ from the state's R.  The gather from the parent slot happens inside the kernel.  Raises ``ValueError``
+        for a label outside the vocabulary or equal to the blank, and for a parent that is no live slot (the child is then unused);
+        ``status`` as in ``prefix_scores``."""
+        probs, seq_lens = self._prefix_rows(probs, seq_lens)
+        B, T, V = probs.shape
+        st = self._prefix_state(state, B, T)
+        R = int(st.cols.shape[1])
+        if parents.dim() != 2 or parents.shape[0] != B or tuple(labels.shape) != tuple(parents.shape):
+            raise ValueError("parents and labels must be [batch, new slots]")
+        parents = parents.to(device=self._device, dtype=torch.int32).contiguous()
+        labels = labels.to(device=self._device, dtype=torch.int32).contiguous()
+        Rn = int(parents.shape[1])
+        with torch.cuda.device(self._device):
+            out = PrefixState(torch.empty((B, Rn, T, 2), dtype=torch.float32, device=self._device),
+                              torch.empty((B, Rn), dtype=torch.int32, device=self._device), torch.empty((B, Rn), dtype=torch.int32, device=self._device))
+            own, status = status is None, self._prefix_status("prefix_advance", status, B, status is None)
+            stream = torch.cuda.current_stream(self._device).cuda_stream
+            _native.check(_native.lib.ctcd_ctc_prefix_advance(self._handle, probs.data_ptr(), seq_lens.data_ptr() if seq_lens is not None else None, B, T, V,
+                                                              int(self._blank_id), self._log_probs, st.cols.data_ptr(), st.last.data_ptr(), st.lens.data_ptr(), R,
+                                                              parents.data_ptr(), labels.data_ptr(), Rn, out.cols.data_ptr(), out.last.data_ptr(),
+                                                              out.lens.data_ptr(), status.data_ptr(), stream))
+            if own:
+                self._prefix_raise("prefix_advance", status, B)
+        return out
+
+    def last_prefix_kernel(self):
+        """Test hook: the kernel the last ``prefix_init`` / ``prefix_scores`` / ``prefix_advance`` launched (ctcd_last_prefix_kernel)."""
+        return int(_native.lib.ctcd_last_prefix_kernel(self._handle))
 
     def label_posteriors(self, probs, seq_lens, beam_results, out_lens):
         """CTC forward-backward per label on the device (include/ctcdecode_amd.h "Label posteriors"): for every label ``i`` of every row

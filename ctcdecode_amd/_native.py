@@ -43,7 +43,8 @@ SYMBOLS = ["ctcd_log_softmax", "ctcd_compact_label_capacity", "ctcd_beam_decode_
            "ctcd_edit_counts", "ctcd_edit_align", "ctcd_set_edit_scratch", "ctcd_last_edit_slots",
            "ctcd_set_edit_long", "ctcd_last_edit_long",
            "ctcd_ctc_keywords", "ctcd_last_keyword_kernel", "ctcd_set_long_keywords",
-           "ctcd_keyword_stream_create", "ctcd_keyword_stream_destroy", "ctcd_keyword_stream_reset", "ctcd_keyword_stream_find", "ctcd_keyword_stream_info"]
+           "ctcd_keyword_stream_create", "ctcd_keyword_stream_destroy", "ctcd_keyword_stream_reset", "ctcd_keyword_stream_find", "ctcd_keyword_stream_info",
+           "ctcd_ctc_prefix_init", "ctcd_ctc_prefix_scores", "ctcd_ctc_prefix_advance", "ctcd_last_prefix_kernel"]
 
 
 def _load():
@@ -248,6 +249,13 @@ def _load():
     lib.ctcd_keyword_stream_reset.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p]
     lib.ctcd_keyword_stream_find.argtypes = [ctypes.c_void_p] * 5 + [ctypes.c_int] * 5 + [ctypes.c_void_p] * 10
     lib.ctcd_keyword_stream_info.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_longlong)]
+    # CTC prefix scores (prefix.hip).  init: dec, probs, seq_lens, B, T, V, blank_id, log_input, R, out_cols, out_last, out_lens, stream
+    lib.ctcd_ctc_prefix_init.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_int] * 6 + [ctypes.c_void_p] * 4
+    # scores: dec, probs, seq_lens, B, T, V, blank_id, log_input, cols, last, lens, R, candidates, C, out_scores, out_eos, status, stream
+    lib.ctcd_ctc_prefix_scores.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_int] * 5 + [ctypes.c_void_p] * 3 + [ctypes.c_int, ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 4
+    # advance: dec, probs, seq_lens, B, T, V, blank_id, log_input, cols, last, lens, R, parents, labels, R_new, out_cols, out_last, out_lens, status, stream
+    lib.ctcd_ctc_prefix_advance.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_int] * 5 + [ctypes.c_void_p] * 3 + [ctypes.c_int] + [ctypes.c_void_p] * 2 + [ctypes.c_int] + [ctypes.c_void_p] * 5
+    lib.ctcd_last_prefix_kernel.argtypes = [ctypes.c_void_p]
     return lib
 
 

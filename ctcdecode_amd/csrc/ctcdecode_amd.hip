@@ -46,6 +46,7 @@
 #include "greedy.h"
 #include "keyword.h"
 #include "keyword_long.h"
+#include "prefix.h"
 #include "editdist.h"
 #include "editops.h"
 #include "editlong.h"
@@ -387,6 +388,8 @@ struct ctcd_decoder {
   int kw_kernel = -1;
   // ... and whether keywords of 65 .. 2048 labels run (keyword_long.h; ctcd_set_long_keywords, off by default)
   bool kw_long = false;
+  // the CTC prefix scores (prefix.h): the kernel its last call launched (ctcd_last_prefix_kernel; -1: none yet)
+  int px_kernel = -1;
   // ctcd_edit_distance (editdist.h): the pairs its last call ran (ctcd_last_edit_pairs)
   long long ed_pairs = 0;
   // ... the cap of its grid (ctcd_set_edit_grid; 0 = the default) and the workgroups of its last launch (ctcd_last_edit_grid)
@@ -491,6 +494,11 @@ namespace ctckw {
 void keyword_note_kernel(ctcd_decoder *d, int code) { d->kw_kernel = code; }
 bool keyword_long_on(const ctcd_decoder *d) { return d->kw_long; }
 }  // namespace ctckw
+
+// ... and the prefix scores' (prefix.hip), beyond the alignment's hooks: the kernel of its last call
+namespace ctcprefix {
+void prefix_note_kernel(ctcd_decoder *d, int code) { d->px_kernel = code; }
+}  // namespace ctcprefix
 
 // ... and the edit distance's (editdist.hip): the decoder's device and compute units, and the count of its last call's pairs
 namespace ctcedit {
@@ -900,6 +908,7 @@ long long ctcd_last_edit_long(ctcd_decoder *d) {
 }
 
 int ctcd_last_keyword_kernel(const ctcd_decoder *d) { return d ? d->kw_kernel : -1; }
+int ctcd_last_prefix_kernel(const ctcd_decoder *d) { return d ? d->px_kernel : -1; }
 int ctcd_set_long_keywords(ctcd_decoder *d, int on) {
   if (!d || (on != 0 && on != 1)) return fail(CTCD_EINVAL, "ctcd_set_long_keywords: a decoder and on = 0 (off) or 1 required");
   d->kw_long = on == 1;

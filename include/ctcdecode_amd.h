@@ -1094,6 +1094,72 @@ int ctcd_keyword_stream_find(ctcd_decoder *dec, ctcd_keyword_stream **states, co
                              int32_t *status /* [B][Q] zeroed by the caller, or NULL */, void *stream);
 int ctcd_keyword_stream_info(ctcd_decoder *dec, const ctcd_keyword_stream *st, long long out[4]); /* waits */
 
+/* ---- CTC prefix scores (no reference counterpart): scoring a hypothesis while it is being built.  A label-synchronous decoder -- an
+ * attention decoder run jointly with CTC, an LLM-driven decoder -- grows its hypotheses one label per step and asks at every step:
+ * given this prefix g and these candidate next labels c, what is the CTC probability that the transcript STARTS with g.c?  That is
+ * the CTC prefix score (Watanabe et al., "Hybrid CTC/attention architecture for end-to-end speech recognition"); eos(g) is the
+ * probability that the transcript IS g.  ctcd_ctc_loglik on rows one label longer recomputes the whole lattice per candidate and
+ * returns the wrong quantity; here a prefix carries T pairs of floats from step to step, and a candidate costs one expf per frame.
+ *
+ * Definition, bit for bit in float32; n, lp(t, c), lse3, expf and logf are those of "CTC log-likelihood".
+ * The state of a prefix g of L labels over an item of n frames is, for t in [0, n): r_n[t], the forward value of the prefix's last
+ * label state, and r_b[t], that of the blank state behind it -- a[t][S-2] and a[t][S-1] of the log-likelihood's recurrence for y = g
+ * (for L == 0: r_n[t] = -inf) -- with `last`, its last label, and L.
+ * Init (the empty prefix): r_n[t] = -inf.   r_b[0] = lp(0, blank).   r_b[t] = lp(t, blank) + lse3(r_b[t-1], -inf, -inf).
+ * Advance by the label c; (r_n, r_b, last, L) is the parent's state and (r_n', r_b') the child's:
+ *   r_n'[0] = lp(0, c) if L == 0, else -inf.   r_b'[0] = -inf.
+ *   r_n'[t] = lp(t, c) + lse3(r_n'[t-1], r_b[t-1], r_n[t-1] if L == 0 or c != last, else -inf).
+ *   r_b'[t] = lp(t, blank) + lse3(r_b'[t-1], r_n'[t-1], -inf).
+ * The end score: eos = lse3(r_b[n-1], r_n[n-1] (if L >= 1), -inf), the bits of ctcd_ctc_loglik for y = g.  n == 0: 0 for L == 0,
+ * else -inf.
+ * The prefix score of the candidate c: psi = log sum_t exp(v[t]) over t in [0, n), where
+ *   v[0] = lp(0, c) if L == 0, else -inf.   v[t] = lp(t, c) + phi[t-1], one float32 addition.
+ *   phi[t] = r_b[t] if L >= 1 and c == last, else lse3(r_b[t], r_n[t], -inf).
+ * The sum is one sequential pass in ascending t over a pair (m, s), from m = -inf, s = 0:
+ *   a term v == -inf is skipped;   if v > m: s = s * expf(m - v) + 1.0f (two float32 operations; expf(-inf) = 0), then m = v;
+ *   otherwise s = s + expf(v - m).
+ * psi = logf(s) + m, or -inf if m is still -inf.  s lies in [1, n]; csrc/exact_math.h logf_normal restates glibc's logf for every
+ * normal float, so its domain covers it.  An expf below 2^-126 cannot change s (s >= 1) and may be taken as 0.
+ * A candidate equal to blank_id or to -1 scores -inf.  NaN and +inf inputs are undefined.
+ * The validity rules.  A slot with lens < 0 is UNUSED: its scores and its eos are -inf, its column is not read.  A prefix of L >= 1
+ * whose `last` is outside [0, V) or equal to blank_id, and a candidate outside [-1, V), raise the item's word of `status` to
+ * CTCD_ALIGN_BAD_ROW; the prefix's scores and eos, or the candidate's score, are -inf.  `last` of an empty prefix is not looked at.
+ * In ctcd_ctc_prefix_advance parents[b][j] == -1 leaves child j unused (lens -1, last -1, its column untouched); a parent outside
+ * [-1, R), a parent slot that is unused or invalid, or a label outside [0, V) or equal to blank_id does the same and raises the
+ * item's word.  Nothing is ever read through an unchecked index.
+ *
+ * The entry points: everything is device memory and asynchronous on `stream`; nothing is read on the host.  cols is float
+ * [B][R][T][2] = (r_n[t], r_b[t]), 8-byte aligned; entries at t >= n are never read and never written.  last and lens are int32
+ * [B][R] (last -1: none; lens -1: unused).  R is the number of prefix slots per item.
+ * ctcd_ctc_prefix_init: slot 0 of every item becomes the empty prefix, the other slots unused.
+ * ctcd_ctc_prefix_scores: candidates int32 [B][R][C], or NULL for every label as a candidate (C is then V, and column blank_id is
+ *   -inf); out_scores float [B][R][C], out_eos float [B][R].
+ * ctcd_ctc_prefix_advance: parents and labels int32 [B][R_new]; child j of item b is slot parents[b][j] of the item advanced by
+ *   labels[b][j].  Parents may repeat and come in any order; R_new may differ from R.  The gather from the parent slot is part of
+ *   the kernel.  out_cols [B][R_new][T][2] must not overlap cols.
+ * probs, seq_lens, the three log_input modes, the argument checks and the error codes are ctcd_ctc_loglik's; there is no limit on T
+ * or on a prefix's length.  log_input == 2 runs the log-softmax pass into the decoder-owned rows on EVERY call -- correct, and
+ * wasteful over the steps of a decode: take ctcd_log_softmax once and pass its rows with log_input == 1.  CTCD_EUNSUPPORTED also for
+ * more than 65535 tiles of candidates or of prefixes.  B x R == 0 (advance: B x R_new == 0) is CTCD_OK and launches nothing.
+ * The scores kernel: a workgroup of four waves takes one item, a tile of prefixes and a tile of candidates, one candidate per lane
+ * in lane groups of 32 .. 256; per chunk of 32 frames it folds the prefixes' columns into LDS, one frame per lane, and then every
+ * lane walks the chunk on its own.  With all labels as candidates one row value serves up to 8 prefixes; rows of V <= 128 labels are
+ * staged in LDS.  The advance kernel runs one new prefix per lane and moves the columns through LDS tiles of 64 prefixes x 16 frames.
+ * ctcd_last_prefix_kernel (test hook): the kernel the last of the three calls launched: dtype | 4 * (log_input == 0) | 8 * staged
+ * | 16 * listed | 32 * kind (0 scores, 1 advance, 2 init) | log2(lane group) << 8 | prefixes per lane group << 12 (the last three
+ * fields for the scores kernel only).  -1: none yet, or dec == NULL. */
+int ctcd_ctc_prefix_init(ctcd_decoder *dec, const void *probs, const int32_t *seq_lens, int B, int T, int V, int blank_id, int log_input, int R,
+                         float *out_cols /* [B][R][T][2] */, int32_t *out_last, int32_t *out_lens /* [B][R] */, void *stream);
+int ctcd_ctc_prefix_scores(ctcd_decoder *dec, const void *probs, const int32_t *seq_lens, int B, int T, int V, int blank_id, int log_input,
+                           const float *cols /* [B][R][T][2] */, const int32_t *last, const int32_t *lens /* [B][R] */, int R,
+                           const int32_t *candidates /* [B][R][C], or NULL: all labels */, int C, float *out_scores /* [B][R][C] */,
+                           float *out_eos /* [B][R] */, int32_t *status /* [B] zeroed by the caller, or NULL */, void *stream);
+int ctcd_ctc_prefix_advance(ctcd_decoder *dec, const void *probs, const int32_t *seq_lens, int B, int T, int V, int blank_id, int log_input,
+                            const float *cols, const int32_t *last, const int32_t *lens, int R, const int32_t *parents,
+                            const int32_t *labels /* [B][R_new] */, int R_new, float *out_cols /* [B][R_new][T][2] */, int32_t *out_last,
+                            int32_t *out_lens /* [B][R_new] */, int32_t *status /* [B] zeroed by the caller, or NULL */, void *stream);
+int ctcd_last_prefix_kernel(const ctcd_decoder *dec);
+
 /* Tuning / introspection. */
 int ctcd_set_threads(ctcd_decoder *dec, int threads_per_workgroup); /* 0 = automatic (default); else a power of two in [64, 1024] */
 /* Two workgroups per CU.  The fixed-layout class (beam <= 128, <= 32 labels) has a second build of its kernel that fits
