@@ -843,7 +843,7 @@ class CTCBeamDecoder(object):
         """Long rows for ``align`` and ``log_likelihood`` (include/ctcdecode_amd.h ctcd_set_long_rows): with a band of 256, 1024 or 4096
         states, rows of up to 2^20 - 1 labels are accepted -- a row of more than ``band`` states (2 x labels + 1) runs in bands of that
         many -- instead of 2047; 0 turns the mode off (the default).  The band width never changes a result.  ``align`` then needs
-        about ``T x (min(L, T) / 2 + 16)`` bytes of scratch per row in flight (``set_align_scratch``).  ``label_posteriors`` keeps its limit.
+        about ``T x (min(L, T) / 2 + 16)`` bytes of scratch per row in flight (``set_align_scratch``).  ``label_posteriors`` keeps its limit: its switch is ``set_long_posteriors``.
         Raises ``ValueError`` for any other band."""
         _native.check(_native.lib.ctcd_set_long_rows(self._handle, int(band)))
 
@@ -1034,6 +1034,23 @@ class CTCBeamDecoder(object):
     def last_posterior_grid(self):
         """Test hook: the workgroups the last ``label_posteriors`` launched."""
         return int(_native.lib.ctcd_last_posterior_grid(self._handle))
+
+    def set_long_posteriors(self, band=4096, block=0):
+        """Long rows for ``label_posteriors`` (include/ctcdecode_amd.h ctcd_set_long_posteriors), a switch of its own next to
+        ``set_long_rows``: with a band of 256, 1024 or 4096 states, rows of up to 2^20 - 1 labels are accepted instead of 2047 -- a row of
+        more than ``band`` states runs in bands of that many and in blocks of ``block`` frames (0: automatic, near ``sqrt(T)``; else a
+        multiple of 8 in [8, 4096]), keeping about ``(T / block + block) x (2 min(L, T) + 1)`` floats for such a row instead of every
+        frame's.  A scratch slot (``set_posterior_scratch``) is that or ``T x band`` floats, whichever is more -- the rows up to the band
+        still keep every frame: 10000 labels in 30000 frames take 31 MB per row in flight at band 256, 123 MB at 1024, 491 MB at
+        4096, where every frame's values would take 2.4 GB.  Band 0 turns the mode off (the default).  Neither value changes a bit
+        of any output.  Raises ``ValueError`` for any other value."""
+        _native.check(_native.lib.ctcd_set_long_posteriors(self._handle, int(band), int(block)))
+
+    def last_long_posteriors(self):
+        """``(band, block)`` the last ``label_posteriors`` ran its banded kernel at; ``(0, 0)`` if it launched none."""
+        band, block = ctypes.c_int(0), ctypes.c_int(0)
+        _native.check(_native.lib.ctcd_last_long_posteriors(self._handle, ctypes.byref(band), ctypes.byref(block)))
+        return int(band.value), int(block.value)
 
     def greedy_decode_device(self, probs, seq_lens=None, details=False):
         """Greedy (best-path) CTC decoding on the device (include/ctcdecode_amd.h "Greedy decode"): every frame's most probable label,

@@ -14,7 +14,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB_DIR = os.path.join(HERE, "_lib")
 # CTCDECODE_AMD_LIB: load another build of the library (kernel experiments: tools/build_variants.sh)
 LIB_PATH = os.environ.get("CTCDECODE_AMD_LIB") or os.path.join(LIB_DIR, "libctcdecode_amd.so")
-SOURCES = ["ctcdecode_amd.hip", "decode_kernel_exact.hip", "prepass.hip", "stream_peek.hip", "stream_compact.hip", "stream_commit.hip", "stream_snapshot.hip", "blank_skip.hip", "stream_blank_skip.hip", "nbest.hip", "align.hip", "loglik.hip", "posterior.hip", "greedy.hip", "greedy_stream.hip", "editdist.hip", "editops.hip", "editlong.hip", "keyword.hip", "keyword_long.hip", "keyword_stream.hip", "prefix.hip"]
+SOURCES = ["ctcdecode_amd.hip", "decode_kernel_exact.hip", "prepass.hip", "stream_peek.hip", "stream_compact.hip", "stream_commit.hip", "stream_snapshot.hip", "blank_skip.hip", "stream_blank_skip.hip", "nbest.hip", "align.hip", "loglik.hip", "posterior.hip", "posterior_long.hip", "greedy.hip", "greedy_stream.hip", "editdist.hip", "editops.hip", "editlong.hip", "keyword.hip", "keyword_long.hip", "keyword_stream.hip", "prefix.hip"]
 # (decode_kernel_exact.hip: the exact-shape twins of the north-star kernel, decode_kernel.h CTC_EXACT_SHAPES)
 KERNEL_SOURCE = "decode_kernels.hip"  # compiled once per group of kernel instantiations (decode_kernel.h CTC_KERNEL_LIST), in parallel
 KERNEL_GROUPS = 12

@@ -205,7 +205,8 @@ namespace ctcalign {
 // What ctcd_ctc_align and ctcd_ctc_loglik do alike before their launch (align.hip): the checks of the arguments they share -- `fn`, the
 // entry point's name, stands in the messages; `outputs`: its output tensors are there -- the decoder's info, its device entered
 // through `guard`, and for raw logits the log-softmax pass.  -> CTCD_OK with e filled in (rows == 0: nothing to do), or the failure.
-// long_rows: the entry point has a banded kernel, so ctcd_set_long_rows lifts its limit on min(L_stride, T).
+// long_rows: the entry point has a banded kernel, so ctcd_set_long_rows lifts its limit on min(L_stride, T).  own_band: the band of an
+// entry point whose banded kernel has a switch of its own (ctcd_ctc_posteriors: ctcd_set_long_posteriors), which lifts it alike.
 struct AlignEntry {
   long long rows;     // B * R
   int band;           // launch_band: the band of the banded kernel this call launches, 0 if it launches none
@@ -214,7 +215,8 @@ struct AlignEntry {
   AlignDecoderInfo inf;
 };
 int align_entry(const char *fn, ctcd_decoder *d, const void *probs, const int32_t *seq_lens, int B, int T, int V, int blank_id, int log_input, const int32_t *tokens,
-                const int32_t *lens, int R, int L_stride, bool outputs, void *stream, ctcdev::DeviceGuard *guard, AlignEntry *e, bool long_rows = false);
+                const int32_t *lens, int R, int L_stride, bool outputs, void *stream, ctcdev::DeviceGuard *guard, AlignEntry *e, bool long_rows = false,
+                int own_band = 0);
 int align_decoder_info(const ctcd_decoder *d, AlignDecoderInfo *out);
 int align_fail(int code, const char *msg);
 // the decoder's back-pointer scratch, grown to `bytes`

@@ -139,7 +139,7 @@ __global__ void __launch_bounds__(kAlignThreads) ctc_align_banded_kernel(const v
 
 // What ctcd_ctc_align and ctcd_ctc_loglik do alike before their launch; `fn`: the entry point's name, for the messages.
 int align_entry(const char *fn, ctcd_decoder *d, const void *probs, const int32_t *seq_lens, int B, int T, int V, int blank_id, int log_input, const int32_t *tokens,
-                const int32_t *lens, int R, int L_stride, bool outputs, void *stream, ctcdev::DeviceGuard *guard, AlignEntry *e, bool long_rows) {
+                const int32_t *lens, int R, int L_stride, bool outputs, void *stream, ctcdev::DeviceGuard *guard, AlignEntry *e, bool long_rows, int own_band) {
   const std::string f = std::string(fn) + ": ";
   e->rows = 0;
   e->band = 0;
@@ -151,7 +151,7 @@ int align_entry(const char *fn, ctcd_decoder *d, const void *probs, const int32_
   if (e->rows == 0) return CTCD_OK;
   if ((!tokens && L_stride > 0) || !lens || !outputs || (T > 0 && !probs)) return align_fail(CTCD_EINVAL, (f + "null tensor").c_str());
   if (const int rc = align_decoder_info(d, &e->inf)) return rc;
-  const int band = long_rows ? e->inf.band : 0;
+  const int band = long_rows ? e->inf.band : own_band;
   if (band > 0 && align_lmax(T, L_stride) > kAlignLongMaxLabels)
     return align_fail(CTCD_EUNSUPPORTED, (f + "rows of more than 2^20 - 1 labels (min(L_stride, T) > 1048575) are not built").c_str());
   if (band == 0 && align_lmax(T, L_stride) > kAlignMaxLabels)

@@ -382,6 +382,9 @@ struct ctcd_decoder {
   // (ctcd_set_posterior_scratch; 0 = the default) and the grid of the last call (ctcd_last_posterior_grid)
   Buf po_alpha;
   long long po_budget = 0, po_grid = 0;
+  // long posteriors (posterior.h): the band and the frames per block ctcd_set_long_posteriors set (0: off / automatic), and what the
+  // last ctcd_ctc_posteriors ran its banded kernel at (ctcd_last_long_posteriors; 0 / 0: the mode-off launch)
+  int po_band = 0, po_block = 0, po_last_band = 0, po_last_block = 0;
   // ctcd_greedy_decode (greedy.h): the frame records its argmax pass leaves its collapse pass
   Buf gr_frames;
   // ctcd_ctc_keywords (keyword.h): the kernel its last call launched (ctcd_last_keyword_kernel; -1: none yet).  Its m(t) are gr_frames.
@@ -487,6 +490,14 @@ int post_scratch(ctcd_decoder *d, size_t bytes, void **p) {
   return CTCD_OK;
 }
 void post_note_grid(ctcd_decoder *d, long long grid) { d->po_grid = grid; }
+void post_long_mode(const ctcd_decoder *d, int *band, int *block) {
+  *band = d->po_band;
+  *block = d->po_block;
+}
+void post_note_long(ctcd_decoder *d, int band, int block) {
+  d->po_last_band = band;
+  d->po_last_block = block;
+}
 }  // namespace ctcpost
 
 // ... and the keyword search's (keyword.hip), beyond the alignment's and the greedy decode's hooks: the kernel of its last call
@@ -872,6 +883,20 @@ int ctcd_set_posterior_scratch(ctcd_decoder *d, long long bytes) {
   return CTCD_OK;
 }
 long long ctcd_last_posterior_grid(const ctcd_decoder *d) { return d ? d->po_grid : -1; }
+// Long posteriors (posterior_long.hip): the band of the banded kernel and its frames per block, and what the last call ran it at.
+int ctcd_set_long_posteriors(ctcd_decoder *d, int band, int block) {
+  if (!d || (band != 0 && !ctcalign::band_ok(band)) || !ctcpost::post_block_ok(block))
+    return fail(CTCD_EINVAL, "ctcd_set_long_posteriors: a decoder, a band of 0 (off), 256, 1024 or 4096 and a block of 0 (automatic) or a multiple of 8 in [8, 4096] required");
+  d->po_band = band;
+  d->po_block = block;
+  return CTCD_OK;
+}
+int ctcd_last_long_posteriors(const ctcd_decoder *d, int *band, int *block) {
+  if (!d) return fail(CTCD_EINVAL, "ctcd_last_long_posteriors: decoder == NULL");
+  if (band) *band = d->po_last_band;
+  if (block) *block = d->po_last_block;
+  return CTCD_OK;
+}
 
 // Edit distance (editdist.hip): the pairs its last call ran.
 long long ctcd_last_edit_pairs(const ctcd_decoder *d) { return d ? d->ed_pairs : -1; }

@@ -352,6 +352,146 @@ __device__ __forceinline__ void walk_row_banded(P &pol, const void *probs, size_
   pol.finish(last, before, L, tid);
 }
 
+// ---- a segment of a band: some of the frames, in either direction (the long posteriors, posterior_long.hip) ---------------------------
+// The labels as a walk sees them: the row's own, or -- for the backward recurrence -- reversed.
+struct RowLabels {
+  const int32_t *y;
+  __device__ __forceinline__ int operator[](int i) const { return y[i]; }
+};
+struct ReversedLabels {
+  const int32_t *y;
+  int L;
+  __device__ __forceinline__ int operator[](int i) const { return y[L - 1 - i]; }
+};
+
+// walk_band over the walk's frames w0 .. w1 only (0 <= w0 <= w1 <= n - 1).  REV: walk frame w is the item's frame n - 1 - w and `lab` the
+// reversed labels, as in walk_row; the hooks see the item's frame.  `a`: the thread's states at walk frame w0, in and out -- the caller
+// loads them from a row in memory and finds the states of frame w1 there afterwards; from_def (w0 == 0): they are the definition's
+// instead, and the policy sees them through first() and frame() as walk_row's FIRST does.  The cells of the frames w0 + 1 .. w1 follow.
+// The edge columns are the segment's: pair w - w0 is frame w's, so edge_out gets w1 - w0 + 1 pairs, the first from the states the
+// walk starts with.  The same cells in the same order as walk_row and walk_band, the same memory discipline.
+template <int NPL, int DT, bool PROB, bool REV, class Y, class P>
+__device__ __forceinline__ void walk_segment(P &pol, const void *probs, size_t row0, int n, int V, int blank, Y lab, int S, int base, int w0, int w1, bool from_def,
+                                             float (&a)[NPL], const unsigned long long *edge_in, float2 *edge_out, int tid) {
+  constexpr int CH = NPL == 1 ? 8 : (NPL == 4 ? 4 : 2);
+  constexpr int WAVES = kAlignWaves;
+  const int lane = tid & 63, wave = tid >> 6;
+  const int s0 = base + tid * NPL;
+  const bool takes_edge = edge_in != nullptr && tid < (NPL == 1 ? 2 : 1);
+  __shared__ float s_sxch[2 * kAlignWaves * 2];
+  float *xch = s_sxch;
+  constexpr unsigned kElem = DT == ctcskip::kSkipF32 ? 4u : 2u;
+  unsigned zo[NPL];
+  unsigned has2 = 0u;
+#pragma unroll
+  for (int k = 0; k < NPL; ++k) {
+    const int s = s0 + k;
+    zo[k] = (unsigned)blank * kElem;
+    if (s < S && (s & 1)) {
+      const int y = lab[s >> 1];
+      zo[k] = (unsigned)y * kElem;
+      if (s >= 3 && y != lab[(s >> 1) - 1]) has2 |= 1u << k;  // (state_skips; a band's first odd state looks at a label of the band before it)
+    }
+  }
+  auto load = [&](float(&dst)[NPL], int w) {  // (a frame beyond w1: frame w1's, unused)
+    const int ww = w <= w1 ? w : w1;
+    const char *fr = (const char *)probs + (row0 + (size_t)(REV ? n - 1 - ww : ww)) * (size_t)V * kElem;
+#pragma unroll
+    for (int k = 0; k < NPL; ++k) dst[k] = ctcskip::widen_at<DT>(fr + (size_t)zo[k], 0);
+  };
+  auto convert = [&](float(&v)[NPL]) {
+    if (PROB) {
+#pragma unroll
+      for (int k = 0; k < NPL; ++k) v[k] = prob_to_lp(v[k]);
+    }
+  };
+  // what frame w (> w0) needs of the band before: its pair of frame w - 1
+  auto edge = [&](EdgePair &dst, int w) {
+    if (takes_edge) dst = edge_load(edge_in, (w <= w1 ? w : w1) - 1 - w0);
+  };
+  auto publish = [&](int w) {
+    const float before = NPL >= 2 ? a[NPL >= 2 ? NPL - 2 : 0] : __shfl_up(a[0], 1, 64);
+    if (lane == 63) {
+      xch[((w & 1) * WAVES + wave) * 2] = a[NPL - 1];
+      xch[((w & 1) * WAVES + wave) * 2 + 1] = before;
+    }
+    if (edge_out != nullptr && tid == kAlignThreads - 1) edge_out[w - w0] = make_float2(a[NPL - 1], before);
+    __syncthreads();
+  };
+
+  float cur[CH][NPL], nxt[CH][NPL];
+  EdgePair ecur[CH], enxt[CH];
+#pragma unroll
+  for (int c = 0; c < CH; ++c) ecur[c] = enxt[c] = EdgePair{neg_inf(), neg_inf()};
+  if (from_def) {
+    load(cur[0], w0);
+    convert(cur[0]);
+#pragma unroll
+    for (int k = 0; k < NPL; ++k) a[k] = (s0 + k < 2 && s0 + k < S) ? cur[0][k] : neg_inf();
+#pragma unroll
+    for (int k = 0; k < NPL; ++k) pol.first(k, cur[0][k], a[k]);
+    pol.frame(REV ? n - 1 - w0 : w0, s0, lane);
+  }
+  publish(w0);
+  if (w1 == w0) return;  // (the same for every thread)
+#pragma unroll
+  for (int c = 0; c < CH; ++c) {
+    load(cur[c], w0 + 1 + c);
+    edge(ecur[c], w0 + 1 + c);
+  }
+#pragma unroll
+  for (int c = 0; c < CH; ++c) convert(cur[c]);
+  for (int t0 = w0 + 1; t0 <= w1; t0 += CH) {
+#pragma unroll
+    for (int c = 0; c < CH; ++c) {
+      load(nxt[c], t0 + CH + c);
+      edge(enxt[c], t0 + CH + c);
+    }
+#pragma unroll
+    for (int c = 0; c < CH; ++c) {
+      const int w = t0 + c;
+      if (w <= w1) {
+        float a_in, b_in;
+        if (NPL == 1) {
+          a_in = __shfl_up(a[0], 1, 64);
+          b_in = __shfl_up(a[0], 2, 64);
+        } else {
+          a_in = __shfl_up(a[NPL - 1], 1, 64);
+          b_in = __shfl_up(a[NPL >= 2 ? NPL - 2 : 0], 1, 64);
+        }
+        if (wave > 0) {
+          const int at = (((w - 1) & 1) * WAVES + wave - 1) * 2;
+          if (lane == 0) {
+            a_in = xch[at];
+            b_in = xch[at + 1];
+          }
+          if (NPL == 1 && lane == 1) b_in = xch[at];
+        }
+        if (tid == 0) {  // (the first band: -inf, which never exceeds what it is compared with)
+          a_in = ecur[c].last;
+          b_in = ecur[c].before;
+        }
+        if (NPL == 1 && tid == 1) b_in = ecur[c].last;
+#pragma unroll
+        for (int k = NPL - 1; k >= 0; --k) {
+          const float p1 = k >= 1 ? a[k >= 1 ? k - 1 : 0] : a_in;
+          const float p2 = k >= 2 ? a[k >= 2 ? k - 2 : 0] : (k == 1 ? a_in : b_in);
+          a[k] = pol.cell(k, cur[c][k], a[k], p1, p2, (has2 >> k) & 1u);
+        }
+        pol.frame(REV ? n - 1 - w : w, s0, lane);
+        publish(w);
+      }
+    }
+#pragma unroll
+    for (int c = 0; c < CH; ++c) {
+#pragma unroll
+      for (int k = 0; k < NPL; ++k) cur[c][k] = nxt[c][k];
+      convert(cur[c]);
+      ecur[c] = enxt[c];
+    }
+  }
+}
+
 // The rows fall into four classes, and each class has a kernel of its own (CLS), so that each gets the registers its class needs and
 // no more: 0 = the rows of a group of four consecutive rows that all fit a wave (S <= 64, and the rows that run no recurrence), one
 // per wave side by side without a barrier (workgroup g takes the groups g, g + grid, ...); 1 / 4 / 16 = the rows of every other group,

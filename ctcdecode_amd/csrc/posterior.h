@@ -74,6 +74,49 @@ CTC_HD long long post_grid(long long rows, long long budget, size_t slot_bytes) 
 CTC_HD int label_state(int i) { return 2 * i + 1; }
 CTC_HD int mirrored_state(int S, int s) { return S - 1 - s; }
 
+// ---- long posteriors (ctcd_set_long_posteriors): a row of S > W states in bands of W, its frames in blocks of F ------------------------
+// Keeping a of every frame costs T x S floats, which no budget pays at 10000 labels in 30000 frames.  The banded kernel
+// (posterior_long.hip) keeps a of every F-th frame only -- checkpoint row r is a[(r + 1) F - 1] -- and, block by block from the last to
+// the first, walks a again from the checkpoint before the block into a block buffer of F x S floats and then b over the block's frames
+// from a carry row (b of the first frame of the block behind).  The labels' accumulators wait between two band visits in an array of
+// 16 bytes per label.  The cells and their order are the definition's, so neither the band nor F changes a bit of any output.
+// A slot, from its start: the accumulators | pass 1's two edge columns (align.h: T pairs each) | the two edge columns of a block (F + 1
+// pairs each: a walk's start frame and the block's F) | the checkpoint rows | the block buffer | the carry row; the float rows are
+// indexed by the row's own S.  The register classes up to the band run in the same launch and keep T x min(S, W) floats in the slot's
+// first bytes, so the slot is the larger of the two.
+constexpr int kPostMinBlock = 8, kPostMaxBlock = 4096;
+CTC_HD bool post_block_ok(int block) { return block == 0 || (block >= kPostMinBlock && block <= kPostMaxBlock && block % 8 == 0); }
+// block == 0: the power of two nearest sqrt(T) from above sqrt(T / 2), in [32, 1024] -- checkpoints and block buffer about the same size
+CTC_HD int post_auto_block(int T) {
+  int p = 32;
+  while (p < 1024 && (long long)p * p * 2 < (long long)T) p *= 2;
+  return p;
+}
+CTC_HD int post_block_frames(int block, int T) { return block > 0 ? block : post_auto_block(T); }
+CTC_HD size_t post_ckpt_rows(int T, int F) { return ((size_t)T + (size_t)F - 1) / (size_t)F; }
+CTC_HD size_t post_block_edge_bytes(int F) { return ((size_t)F + 2) / 2 * 16; }  // F + 1 pairs, a multiple of 16 bytes
+CTC_HD size_t post_long_acc_offset() { return 0; }
+CTC_HD size_t post_long_edge_offset(int T, int L_stride, int parity) {
+  return (size_t)ctcalign::align_lmax(T, L_stride) * 16 + (size_t)parity * ctcalign::edge_col_bytes(T);
+}
+CTC_HD size_t post_long_block_edge_offset(int T, int L_stride, int F, int parity) {
+  return post_long_edge_offset(T, L_stride, 2) + (size_t)parity * post_block_edge_bytes(F);
+}
+CTC_HD size_t post_long_ckpt_offset(int T, int L_stride, int F) { return post_long_block_edge_offset(T, L_stride, F, 2); }
+CTC_HD size_t post_long_buf_offset(int T, int L_stride, int F) {
+  return post_long_ckpt_offset(T, L_stride, F) + post_ckpt_rows(T, F) * (size_t)ctcalign::n_states(ctcalign::align_lmax(T, L_stride)) * 4;
+}
+CTC_HD size_t post_long_carry_offset(int T, int L_stride, int F) {
+  return post_long_buf_offset(T, L_stride, F) + (size_t)F * (size_t)ctcalign::n_states(ctcalign::align_lmax(T, L_stride)) * 4;
+}
+CTC_HD size_t post_long_slot_bytes(int T, int L_stride, int band, int F) {
+  const size_t banded = post_long_carry_offset(T, L_stride, F) + (size_t)ctcalign::n_states(ctcalign::align_lmax(T, L_stride)) * 4;
+  const size_t smax = (size_t)ctcalign::n_states(ctcalign::align_lmax(T, L_stride)), four = (size_t)ctcalign::kAlignWaves * 64;
+  const size_t row = smax < (size_t)band ? smax : (size_t)band;  // (the register classes of this launch end at the band)
+  const size_t reg = (size_t)T * (row > four ? row : four) * 4;
+  return ((banded > reg ? banded : reg) + 255) / 256 * 256;
+}
+
 // ---- one hypothesis, sequentially (the host twin) ------------------------------------------------------------------------------------
 // Row `tok` (L_stride words, `len` of them labels) of item b against the item's rows; slot: post_slot_bytes(T, L_stride) bytes of
 // scratch.  peaks / occ / conf: L_stride words each, all written.  Returns 0, or ALIGN_BAD_ROW.
@@ -137,5 +180,26 @@ long long post_budget(const ctcd_decoder *d);  // ctcd_set_posterior_scratch (0:
 // the decoder's scratch for a, grown to `bytes`
 int post_scratch(ctcd_decoder *d, size_t bytes, void **p);
 void post_note_grid(ctcd_decoder *d, long long grid);  // ctcd_last_posterior_grid
+// ctcd_set_long_posteriors: the band (0: off) and the block (0: automatic); what the last call ran at (ctcd_last_long_posteriors)
+void post_long_mode(const ctcd_decoder *d, int *band, int *block);
+void post_note_long(ctcd_decoder *d, int band, int block);
+
+// The launch of posterior_long.hip's kernel: the rows of more than 256 * npl states of the launch, `grid` workgroups with a slot of
+// slot_bytes (post_long_slot_bytes) each, F frames per block.  dtype: CTCD_DTYPE_*; prob: log_input == 0.
+struct PostLongLaunch {
+  const void *probs;
+  const int32_t *seq_lens;
+  int T, V, blank;
+  const int32_t *tokens, *lens;
+  int R, L_stride;
+  long long rows;
+  char *scratch;
+  size_t slot_bytes;
+  int F;
+  int32_t *out_pk;
+  float *out_occ, *out_conf, *out_ll;
+  int32_t *status;
+};
+void post_launch_banded(int dtype, bool prob, int npl, const PostLongLaunch &a, long long grid, void *stream);
 
 }  // namespace ctcpost

@@ -184,22 +184,33 @@ int ctcd_ctc_posteriors(ctcd_decoder *d, const void *probs, const int32_t *seq_l
                         int32_t *status, void *stream) {
   ctcdev::DeviceGuard guard;
   AlignEntry en;
+  int long_band = 0, long_block = 0;
+  if (d) post_long_mode(d, &long_band, &long_block);
   const int rc = align_entry("ctcd_ctc_posteriors", d, probs, seq_lens, B, T, V, blank_id, log_input, tokens, lens, R, L_stride,
-                             out_loglik && (L_stride == 0 || (out_peaks && out_occupancy && out_confidence)), stream, &guard, &en);
-  if (rc != CTCD_OK || en.rows == 0) return rc;
-  const size_t slot = post_slot_bytes(T, L_stride);
+                             out_loglik && (L_stride == 0 || (out_peaks && out_occupancy && out_confidence)), stream, &guard, &en, false, long_band);
+  if (rc != CTCD_OK) return rc;
+  // long posteriors: en.band is the band of the banded kernel this launch needs (0: the mode-off launch), F its frames per block
+  const int F = en.band ? post_block_frames(long_block, T) : 0;
+  post_note_long(d, en.band, F);
+  if (en.rows == 0) return rc;
+  const size_t slot = en.band ? post_long_slot_bytes(T, L_stride, en.band, F) : post_slot_bytes(T, L_stride);
   const long long grid = post_grid(en.rows, post_budget(d), slot);
   void *scratch = nullptr;
   if (const int rc2 = post_scratch(d, (size_t)grid * slot, &scratch)) return rc2;
   post_note_grid(d, grid);
   // class 0 takes a group of four rows per workgroup at a time (at most the groups), the other classes one row
   const long long groups = align_groups(en.rows);
-  const hipError_t e = ctclattice::launch_classes(en.dtype, log_input == 0, T, L_stride, [&](auto dt, auto prob, auto cls) {
-    const long long g = decltype(cls)::value == 0 && grid > groups ? groups : grid;
-    hipLaunchKernelGGL((ctc_posterior_kernel<decltype(dt)::value, decltype(prob)::value, decltype(cls)::value>), dim3((unsigned)g), dim3(kAlignThreads), 0,
-                       (hipStream_t)stream, en.probs, seq_lens, T, V, blank_id, tokens, lens, R, L_stride, en.rows, (char *)scratch, slot, out_peaks, out_occupancy,
-                       out_confidence, out_loglik, status);
-  });
+  const hipError_t e = ctclattice::launch_classes<true>(en.dtype, log_input == 0, T, L_stride, [&](auto dt, auto prob, auto cls) {
+    constexpr int CLS = decltype(cls)::value;
+    const long long g = CLS == 0 && grid > groups ? groups : grid;
+    if constexpr (CLS < 0)
+      post_launch_banded(en.dtype, decltype(prob)::value, -CLS, PostLongLaunch{en.probs, seq_lens, T, V, blank_id, tokens, lens, R, L_stride, en.rows, (char *)scratch, slot, F,
+                                                                              out_peaks, out_occupancy, out_confidence, out_loglik, status}, g, stream);
+    else
+      hipLaunchKernelGGL((ctc_posterior_kernel<decltype(dt)::value, decltype(prob)::value, CLS>), dim3((unsigned)g), dim3(kAlignThreads), 0, (hipStream_t)stream,
+                         en.probs, seq_lens, T, V, blank_id, tokens, lens, R, L_stride, en.rows, (char *)scratch, slot, out_peaks, out_occupancy, out_confidence,
+                         out_loglik, status);
+  }, en.band);
   return e == hipSuccess ? CTCD_OK : align_fail(CTCD_EHIP, (std::string("label posteriors: ") + hipGetErrorString(e)).c_str());
 }
 

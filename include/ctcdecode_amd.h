@@ -731,13 +731,34 @@ long long ctcd_last_loglik_grid(const ctcd_decoder *dec);
  * more than 2^31 - 1 rows.  B x R == 0 is CTCD_OK and launches nothing.  Streams are out of scope.
  * ctcd_set_posterior_scratch: the budget of that scratch in bytes; 0 = the default (2 GiB: one workgroup per compute unit at
  * T = L_stride = 1000).  The results do not depend on it.
- * ctcd_last_posterior_grid: the workgroups the last ctcd_ctc_posteriors launched (0: none yet; -1: dec == NULL). */
+ * ctcd_last_posterior_grid: the workgroups the last ctcd_ctc_posteriors launched (0: none yet; -1: dec == NULL).
+ *
+ * Long posteriors.  ctcd_set_long_posteriors(dec, band, block) lifts the limit for ctcd_ctc_posteriors, a switch of its own:
+ * ctcd_set_long_rows changes nothing here.  band = 256, 1024 or 4096 turns the mode on, 0 turns it off (the default: everything
+ * above, the CTCD_EUNSUPPORTED at 2048 included).  block is the frames per block F: 0 = automatic (a power of two near sqrt(T), in
+ * [32, 1024]), otherwise a multiple of 8 in [8, 4096].  Any other value of either is CTCD_EINVAL.  With the mode on the limit is
+ * min(L_stride, T) <= 2^20 - 1, one step beyond is CTCD_EUNSUPPORTED, and a row of more than `band` states runs in bands of that many
+ * states and blocks of F frames: a forward walk keeps a of every F-th frame; then, block by block from the last frame to the first,
+ * a of the block's frames is computed again from the kept frame before it and b walks the block backwards.  Every cell is the
+ * definition's and every label sees its frames in the order n-1 .. 0: NEITHER THE BAND NOR THE BLOCK CHANGES A BIT OF ANY OUTPUT, and
+ * neither does the mode.  Rows of at most `band` states run as with the mode off.  When the shape admits a row beyond the band
+ * (2 min(L_stride, T) + 1 > band), a slot of the scratch is, with Lm = min(L_stride, T) and Sm = 2 Lm + 1,
+ *   16 Lm + 16 T + 2 x 16 ceil((F + 1) / 2) bytes + (ceil(T / F) + F + 1) x Sm floats,
+ * or T x max(min(Sm, band), 256) floats if that is more (the rows up to the band keep a of every frame there), rounded up to 256 bytes:
+ * for 10000 labels in 30000 frames at F = 128 the first term is 29.8 MB where a of every frame would take 2.4 GB, and the second
+ * decides the slot: 30.7 MB at band 256, 123 MB at band 1024, 491 MB at band 4096.  The budget rule is unchanged
+ * (min(B x R, budget / slot bytes) workgroups, at least one; only grid x slot bytes are allocated), and a slot the device cannot
+ * allocate fails the call with the allocation's error.  Otherwise the launch is the mode-off launch.
+ * ctcd_last_long_posteriors: the band and the frames per block the last ctcd_ctc_posteriors ran its banded kernel at, or 0 and 0 if
+ * that launch was the mode-off launch (either pointer may be NULL); CTCD_EINVAL: dec == NULL. */
 int ctcd_ctc_posteriors(ctcd_decoder *dec, const void *probs, const int32_t *seq_lens, int B, int T, int V, int blank_id, int log_input,
                         const int32_t *tokens /* [B][R][L_stride] */, const int32_t *lens /* [B][R] */, int R, int L_stride,
                         int32_t *out_peaks, float *out_occupancy, float *out_confidence /* [B][R][L_stride] */,
                         float *out_loglik /* [B][R] */, int32_t *status /* [B] zeroed by the caller, or NULL */, void *stream);
 int ctcd_set_posterior_scratch(ctcd_decoder *dec, long long bytes);   /* budget of the scratch; 0 = the default */
 long long ctcd_last_posterior_grid(const ctcd_decoder *dec);
+int ctcd_set_long_posteriors(ctcd_decoder *dec, int band, int block);   /* band 0 = off (the default), or 256 / 1024 / 4096; block 0 = automatic */
+int ctcd_last_long_posteriors(const ctcd_decoder *dec, int *band, int *block);
 
 /* ---- Greedy decode (no reference counterpart; the reference's test file defines a greedy_result it never uses): the best-path
  * decode -- every frame's most probable label, repeats collapsed, blanks dropped -- in one read of the input.  No beam, no language
