@@ -276,6 +276,30 @@ def _to_host(tensors):
     return tuple(outs)
 
 
+class _LogLikelihood(torch.autograd.Function):
+    """``CTCBeamDecoder.differentiable_log_likelihood``: forward is ``log_likelihood``; backward is ``log_likelihood_grad`` with the
+    incoming gradient as the rows' weights, then the chain rule from the log-probabilities the kernels see to the input."""
+
+    @staticmethod
+    def forward(ctx, probs, decoder, seq_lens, beam_results, out_lens):
+        ctx.decoder, ctx.rows = decoder, (seq_lens, beam_results, out_lens)
+        ctx.save_for_backward(probs)
+        return decoder.log_likelihood(probs.detach(), seq_lens, beam_results, out_lens)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        probs, = ctx.saved_tensors
+        seq_lens, beam_results, out_lens = ctx.rows
+        grad, _ = ctx.decoder.log_likelihood_grad(probs.detach(), seq_lens, beam_results, out_lens, weights=grad_out)
+        grad = grad.to(probs.device)
+        mode = ctx.decoder._log_probs
+        if mode == 2:  # logits: lp = x - logsumexp(x)
+            grad = grad - torch.softmax(probs.detach().float(), dim=-1) * grad.sum(-1, keepdim=True)
+        elif mode == 0:  # probabilities: lp = log p (a label of probability 0 lies on no alignment: its grad is 0)
+            grad = torch.where(grad != 0, grad / probs.detach().float(), torch.zeros_like(grad))
+        return grad.to(probs.dtype), None, None, None, None
+
+
 def _last_scorer_pairs(handle):
     q, d, r = ctypes.c_longlong(), ctypes.c_longlong(), ctypes.c_longlong()
     _native.check(_native.lib.ctcd_last_scorer_pairs(handle, ctypes.byref(q), ctypes.byref(d), ctypes.byref(r)))
@@ -775,10 +799,13 @@ class CTCBeamDecoder(object):
                                                        B, T, V, out.data_ptr(), stream))
         return out
 
-    def _score_rows(self, name, entry, probs, seq_lens, beam_results, out_lens, outputs):
+    def _score_rows(self, name, entry, probs, seq_lens, beam_results, out_lens, outputs, weights=None):
         """What ``align``, ``log_likelihood`` and ``label_posteriors`` (``name``, for the error text) share: the shape checks, the tensors
         moved to the device, the call of ``entry`` (ctcd_ctc_align / ctcd_ctc_loglik / ctcd_ctc_posteriors) and the status read.  ``outputs``: (one value per label?, dtype) for each
-        output tensor of the entry point.  -> the output tensors, [B, R, L] or [B, R], on the device."""
+        output tensor of the entry point.  -> the output tensors, [B, R, L] or [B, R], on the device.
+
+        ``weights`` [B, R] makes it ``log_likelihood_grad``'s call (ctcd_ctc_loglik_grad): the rows go row index first -- tokens
+        [R, B, L], lengths and weights [R, B] -- the weights follow the lengths, and the outputs are grad [B, T, V] and loglik [R, B]."""
         if probs.dim() != 3:
             raise ValueError("probs must be [batch, time, labels]")
         if beam_results.dim() != 3 or out_lens.dim() != 2 or tuple(out_lens.shape) != tuple(beam_results.shape[:2]):
@@ -798,12 +825,23 @@ class CTCBeamDecoder(object):
         tokens = beam_results.to(device=self._device, dtype=torch.int32).contiguous()
         lens = out_lens.to(device=self._device, dtype=torch.int32).contiguous()
         R, L = int(tokens.shape[1]), int(tokens.shape[2])
+        extra = ()
+        if weights is not None:
+            if tuple(weights.shape) != (B, R):
+                raise ValueError("weights must be [batch, rows]")
+            tokens, lens = tokens.permute(1, 0, 2).contiguous(), lens.t().contiguous()
+            weights = weights.detach().to(device=self._device, dtype=torch.float32).t().contiguous()
+            extra = (weights.data_ptr(),)
         with torch.cuda.device(self._device):
-            outs = [torch.empty((B, R, L) if per_label else (B, R), dtype=dtype, device=self._device) for per_label, dtype in outputs]
+            if weights is not None:  # (a call without rows launches nothing: the zeroes are made here)
+                outs = [(torch.empty if R else torch.zeros)((B, T, V), dtype=torch.float32, device=self._device),
+                        torch.empty((R, B), dtype=torch.float32, device=self._device)]
+            else:
+                outs = [torch.empty((B, R, L) if per_label else (B, R), dtype=dtype, device=self._device) for per_label, dtype in outputs]
             status = torch.zeros((max(B, 1),), dtype=torch.int32, device=self._device)
             stream = torch.cuda.current_stream(self._device).cuda_stream
             _native.check(entry(self._handle, probs.data_ptr(), seq_lens.data_ptr() if seq_lens is not None else None, B, T, V, int(self._blank_id),
-                                self._log_probs, tokens.data_ptr(), lens.data_ptr(), R, L, *[o.data_ptr() for o in outs], status.data_ptr(), stream))
+                                self._log_probs, tokens.data_ptr(), lens.data_ptr(), *extra, R, L, *[o.data_ptr() for o in outs], status.data_ptr(), stream))
             bad = torch.nonzero(status[:B]).flatten().tolist() if B else []
         if bad:
             raise ValueError("ctcdecode_amd: %s: items %s have a row with a label outside the vocabulary, a blank label or a length outside "
@@ -1051,6 +1089,32 @@ class CTCBeamDecoder(object):
         band, block = ctypes.c_int(0), ctypes.c_int(0)
         _native.check(_native.lib.ctcd_last_long_posteriors(self._handle, ctypes.byref(band), ctypes.byref(block)))
         return int(band.value), int(block.value)
+
+    def log_likelihood_grad(self, probs, seq_lens, beam_results, out_lens, weights=None):
+        """The gradient of the CTC log-likelihood on the device (include/ctcdecode_amd.h "Log-likelihood gradient").  Returns
+        ``(grad, loglik)``: ``grad`` float32 [B, T, V], the derivative of ``sum_r weights[b, r] * log P(beam_results[b, r] | probs[b])``
+        with respect to the log-probability the input mode defines for ``(b, t, v)`` -- the input itself for log-probabilities, the
+        ``log_softmax`` row for ``logits_input``, the logarithm of the input for probabilities (``differentiable_log_likelihood``
+        applies the rest of the chain rule) -- and ``loglik`` float32 [B, R], bit for bit what ``log_likelihood`` returns.
+
+        ``weights`` [B, R]; ``None`` means ones.  Frames at or beyond ``seq_lens[b]`` and labels no row holds are 0.  A row no alignment
+        fits (``loglik`` = ``-inf``) contributes nothing.  An item's rows are added in row order and every sum has a fixed order, with
+        no atomics: the result is reproducible bit for bit and does not depend on ``set_posterior_scratch``, whose scratch and budget
+        this call shares with ``label_posteriors``.  One launch per row index and class of row length; rows of at most 2047 labels
+        (``NotImplementedError`` beyond, whatever ``set_long_rows`` and ``set_long_posteriors`` say).  Tensor handling and the
+        ``ValueError`` for an invalid row are those of ``align``."""
+        on_device = beam_results.is_cuda
+        if weights is None:
+            weights = torch.ones(tuple(out_lens.shape), dtype=torch.float32)
+        grad, loglik = self._score_rows("log_likelihood_grad", _native.lib.ctcd_ctc_loglik_grad, probs, seq_lens, beam_results, out_lens, (), weights=weights)
+        loglik = loglik.t().contiguous()
+        return (grad, loglik) if on_device else (grad.cpu(), loglik.cpu())
+
+    def differentiable_log_likelihood(self, probs, seq_lens, beam_results, out_lens):
+        """``log_likelihood`` as a function autograd differentiates: returns ``loglik`` [B, R], and ``backward`` sends its gradient to
+        ``probs`` through ``log_likelihood_grad`` (``weights`` = the incoming gradient) and the chain rule of the decoder's input mode.
+        The gradient has ``probs``' dtype and device.  For an MWER loss: ``(softmax(loglik, 1) * word_errors).sum().backward()``."""
+        return _LogLikelihood.apply(probs, self, seq_lens, beam_results, out_lens)
 
     def greedy_decode_device(self, probs, seq_lens=None, details=False):
         """Greedy (best-path) CTC decoding on the device (include/ctcdecode_amd.h "Greedy decode"): every frame's most probable label,

@@ -37,6 +37,7 @@ SYMBOLS = ["ctcd_log_softmax", "ctcd_compact_label_capacity", "ctcd_beam_decode_
            "ctcd_ctc_align", "ctcd_set_align_scratch", "ctcd_last_align_grid", "ctcd_set_long_rows", "ctcd_last_long_rows",
            "ctcd_ctc_loglik", "ctcd_set_loglik_grid", "ctcd_last_loglik_grid",
            "ctcd_ctc_posteriors", "ctcd_set_posterior_scratch", "ctcd_last_posterior_grid", "ctcd_set_long_posteriors", "ctcd_last_long_posteriors",
+           "ctcd_ctc_loglik_grad",
            "ctcd_greedy_decode",
            "ctcd_greedy_stream_create", "ctcd_greedy_stream_destroy", "ctcd_greedy_stream_reset", "ctcd_greedy_stream_decode", "ctcd_greedy_stream_info",
            "ctcd_edit_distance", "ctcd_last_edit_pairs", "ctcd_set_edit_grid", "ctcd_last_edit_grid",
@@ -208,6 +209,9 @@ def _load():
     lib.ctcd_last_posterior_grid.restype = ctypes.c_longlong
     lib.ctcd_set_long_posteriors.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int]
     lib.ctcd_last_long_posteriors.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
+    # log-likelihood gradient (loglik_grad.hip): dec, probs, seq_lens, B, T, V, blank_id, log_input, tokens, lens, weights, R, L_stride,
+    # out_grad, out_loglik, status, stream
+    lib.ctcd_ctc_loglik_grad.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_int] * 5 + [ctypes.c_void_p] * 3 + [ctypes.c_int] * 2 + [ctypes.c_void_p] * 4
     # greedy decode (greedy.hip): dec, probs, seq_lens, B, T, V, blank_id, log_input, out_tokens, out_starts, out_ends, out_label_scores,
     # out_scores, out_lens, stream
     lib.ctcd_greedy_decode.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_int] * 5 + [ctypes.c_void_p] * 7

@@ -760,6 +760,40 @@ long long ctcd_last_posterior_grid(const ctcd_decoder *dec);
 int ctcd_set_long_posteriors(ctcd_decoder *dec, int band, int block);   /* band 0 = off (the default), or 256 / 1024 / 4096; block 0 = automatic */
 int ctcd_last_long_posteriors(const ctcd_decoder *dec, int *band, int *block);
 
+/* ---- Log-likelihood gradient (no reference counterpart): the derivative of a weighted sum of an item's row log-likelihoods with
+ * respect to the item's log-probabilities -- what minimum-word-error-rate and plain CTC fine-tuning need of an n-best list.
+ *
+ * Definition.  Every row (b, r) has z, S, a, b, ll and g[t][s] exactly as "Label posteriors" defines them; here g[t][s] is taken for
+ * EVERY state s = 0 .. S-1, the even (blank) ones included, by the same rule.  With w = weights[r][b]:
+ *   x[t][s] = (w * g[t][s]) + 0.0f          two float32 operations; the + 0.0f turns -0.0 into +0.0.
+ *   G_r[t][v], for a label v != blank that the row holds at the positions i_0 < i_1 < .. < i_k:
+ *     ((x[t][2 i_0 + 1] + x[t][2 i_1 + 1]) + ..) + x[t][2 i_k + 1], left to right, starting from the first value.
+ *   G_r[t][blank]: the blank states counted from the row's end, u_e = x[t][S - 1 - 2e] for e = 0 .. L, summed pairwise level by level:
+ *     u_m <- u_{2m} + u_{2m+1}, a missing right element counting as +0.0, until one value is left.
+ *   grad[b][t][v] = ((G_0[t][v] + G_1[t][v]) + ..) + G_{R-1}[t][v] over the rows r = 0, 1, .. that contribute to (t, v), in that order,
+ *     starting from the first; +0.0 where none does: the frames t >= n and the labels no contributing row holds.
+ * A row contributes nothing if it is INVALID (its item's word of `status` is raised to CTCD_ALIGN_BAD_ROW, as in "Forced alignment",
+ * and the item's other rows count as usual), if it runs no recurrence (n == 0 or L > n), if its ll is -inf, or if its weight is 0.
+ * A row without labels is a row like any other: its one state is the blank's.
+ * Every sum above is float32 in the order written, so grad is a function of the inputs alone, bit for bit: it does not depend on the
+ * grid, the scratch budget or which workgroup took which row.  No atomic touches grad.  NaN and infinite weights are undefined.
+ * grad[b][t][v] is the derivative of sum_r w[r][b] * ll(b, r) with respect to lp(t, v) of item b: for log_input == 2 that is the
+ * log-softmax row the call computes, for log_input == 0 the logarithm of the probability; the chain rule to the input is the caller's.
+ *
+ * ctcd_ctc_loglik_grad: everything is device memory and asynchronous on `stream`.  probs, seq_lens and status are as for
+ * ctcd_ctc_posteriors.  tokens, lens, weights and out_loglik are laid out ROW INDEX FIRST -- [R][B][L_stride], [R][B], [R][B], [R][B]
+ * -- because row r of all items runs as one launch (per class of row length), R launches behind each other on the stream: no two
+ * workgroups of a launch share an item, so grad is accumulated by plain loads and stores in launch order.  The first launch zeroes
+ * each item's [T][V] floats itself; the caller need not.  out_loglik holds ll, bit for bit what ctcd_ctc_loglik writes.  The two
+ * walks, the scratch slots, the budget (ctcd_set_posterior_scratch) and ctcd_last_posterior_grid are those of ctcd_ctc_posteriors,
+ * for the B rows of a launch.  Rows are limited to 2047 labels whatever ctcd_set_long_rows and ctcd_set_long_posteriors say:
+ * min(L_stride, T) > 2047 is CTCD_EUNSUPPORTED; the other error codes are ctcd_ctc_align's.  B x R == 0 is CTCD_OK and launches
+ * nothing: out_grad is then not written.  Long rows, streams and splitting one row over workgroups are out of scope. */
+int ctcd_ctc_loglik_grad(ctcd_decoder *dec, const void *probs, const int32_t *seq_lens, int B, int T, int V, int blank_id, int log_input,
+                         const int32_t *tokens /* [R][B][L_stride] */, const int32_t *lens /* [R][B] */, const float *weights /* [R][B] */,
+                         int R, int L_stride, float *out_grad /* [B][T][V] */, float *out_loglik /* [R][B] */,
+                         int32_t *status /* [B] zeroed by the caller, or NULL */, void *stream);
+
 /* ---- Greedy decode (no reference counterpart; the reference's test file defines a greedy_result it never uses): the best-path
  * decode -- every frame's most probable label, repeats collapsed, blanks dropped -- in one read of the input.  No beam, no language
  * model, no vocabulary prune and no blank-frame filter take part.
